@@ -18,7 +18,13 @@ the frame to the host.  Inputs (reference orbit, LA
 table) are generated on the host with GMP *before* the timed region and are resident in HBM when it starts;
 `value` = W*H*K / t with t = max over ranks of the barrier-bracketed wall time.  Prints ONE JSON line on rank 0.
 
-Extra objects (round contract):
+A plain run does only what `value` needs: inputs, one untimed frame whose recorded tile costs order the frames that follow,
+the --warmup frames, the --steps timed frames, and the line (metric, value, unit, higher_is_better, dtype, ms_per_step, the
+configuration).  --dump-outputs DIR writes the iteration buffer of the last timed frame as DIR/iterations.npy (see
+dump_outputs).  Everything else below -- the counted launch behind the roofline, latencies, the warm figure of the cold
+workloads, the secondary frame, the CPU baseline and every check against the oracle -- runs with --full only.
+
+Extra objects (--full):
   roofline      dominant kernel of the workload.  The perturbation kernels are VALU-bound (scalar complex arithmetic,
                 no dense contraction; orbit + table are L2 resident), so `bound` is "valu": achieved = executed
                 pixel-steps x 18 FP32 flop / average kernel duration measured with HIP
@@ -105,6 +111,27 @@ def frame_crc32(frame, H, W):
 
     import numpy as np
     return "%08x" % (zlib.crc32(np.ascontiguousarray(frame[:H, :W]).astype("<u4", copy=False).tobytes()) & 0xFFFFFFFF)
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_DRAWS = 1 << 21   # pixel draws of the sample of a frame too large to write whole (seeded: the same pixels every run)
+
+
+def dump_outputs(out_dir, frame, H, W, n_iterations):
+    """--dump-outputs: what a caller of the timed path receives from its last step, the iteration buffer (rows 0..H-1, columns
+    0..W-1), as out_dir/iterations.npy.  float32 while every count is exact in it (cap below 2^24), float64 otherwise.  A frame
+    larger than DUMP_LIMIT_BYTES in that type is written as a sample: the pixels at out_dir/pixel_index.npy (row-major indices,
+    float64, ascending), drawn by a generator with a fixed seed from H and W alone, so that two runs with the same arguments
+    write the same pixels."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    dt = np.float32 if n_iterations < (1 << 24) else np.float64
+    if H * W * np.dtype(dt).itemsize <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "iterations.npy"), frame[:H, :W].astype(dt))
+        return
+    idx = np.unique(np.random.default_rng(0).integers(0, H * W, size=DUMP_SAMPLE_DRAWS, dtype=np.int64))
+    np.save(os.path.join(out_dir, "iterations.npy"), frame[idx // W, idx % W].astype(dt))
+    np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
 
 
 def make_inputs(wl, view_id=-1, width=0, height=0, iter_cap=0, parity=None):
@@ -212,6 +239,12 @@ def parse():
                          "gather, no re-order kernel, N links instead of one.  Same frame either way")
     ap.add_argument("--no-build", action="store_true",
                     help="never spawn a compiler (same as FS_NO_BUILD=1): required under rocprofv3, see tools/pmc_passes.sh")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline (counted launch), latencies, warm and cold figures, the "
+                         "secondary frame, the CPU baseline and the checks against the oracle (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the iteration buffer of the last timed frame to DIR/iterations.npy "
+                         "(float32 or float64; a frame over 64 MB as a fixed, seeded sample with DIR/pixel_index.npy)")
     return ap.parse_args()
 
 
@@ -366,8 +399,9 @@ def main():
         else:
             assert lib.fs_upload_bla(r._h, T_HDR32, None, None, 0, 0) == 0
     # informational: the same LA table built on the device (fs_build_la) instead of the host builder
+    full = args.full
     la_device_ms = None
-    if is_lav2 and not is2x32 and orbit.count < 100000:  # below the reference's multi-threading threshold the tables agree
+    if full and is_lav2 and not is2x32 and orbit.count < 100000:  # below the reference's multi-threading threshold the tables agree
         t1 = time.perf_counter()
         if r.BuildLAOnDevice(orbit) == 0:
             la_device_ms = round((time.perf_counter() - t1) * 1e3, 3)
@@ -587,12 +621,16 @@ def main():
     if not tile_order_on:
         r.set_kernel_variant(1 if "literal" in vsel else (2 if "noscale" in vsel else 0), lds_orbit="lds_orbit" in vsel,
                              refill="refill" in vsel, natural_tile_order=True)
-    st = count_steps(parity)
+    if full:
+        st = count_steps(parity)
+    else:
+        one_frame(parity)  # (the uninstrumented form of count_steps' launch: the view's first frame, whose costs are recorded)
     for _ in range(args.warmup):
         one_frame(parity)
     # ... up to the view's steady state: the pixel order of the HDRFloat<double> / <CudaDblflt> frames is made for a view that is
-    # rendered a second time (its first frame runs as it is, its second records and sorts, the third and later ones run ordered)
-    if tile_order_on and wl in ("c4_hdr64", "c4_2x32"):
+    # rendered a second time (its first frame runs as it is, its second records and sorts, the third and later ones run ordered).
+    # Only the warm figure of --full needs it: the cold frames of `value` forget whatever was recorded
+    if full and tile_order_on and wl in ("c4_hdr64", "c4_2x32"):
         for _ in range(3):
             if r.last_frame_tile_ordered():
                 break
@@ -604,49 +642,52 @@ def main():
     # the COLD figure -- every timed frame a first frame -- and the warm one is reported beside it (value_warm).  The
     # HDRFloat<float> tile costs are keyed without the coordinates and do carry over from frame to frame of a zoom: warm.
     cold_headline = wl in ("c4_hdr64", "c4_2x32") and tile_order_on
-    elapsed_warm = kernel_ms_warm = None
+    elapsed_warm = kernel_ms_warm = warm_split = None
     if cold_headline:
-        elapsed_warm, kernel_ms_warm = timed(parity)
-        warm_split = r.kernel_ms_split_history(min(args.steps, 64))
+        if full:
+            elapsed_warm, kernel_ms_warm = timed(parity)
+            warm_split = r.kernel_ms_split_history(min(args.steps, 64))
         elapsed, kernel_ms = timed(parity, cold=True)
-        kernel_split = r.kernel_ms_split_history(min(args.steps, 64))
+    else:
+        elapsed, kernel_ms = timed(parity)
+    kernel_split = r.kernel_ms_split_history(min(args.steps, 64))
+    if rank == 0 and args.dump_outputs:  # (before a later frame reuses the buffer)
+        dump_outputs(args.dump_outputs, host_np[state["last"]], H, W, n_iter)
+    if full and cold_headline:
         for _ in range(3):  # (leave the renderer warm again for the latency figures below)
             if r.last_frame_tile_ordered():
                 break
             one_frame(parity)
-    else:
-        elapsed, kernel_ms = timed(parity)
-        kernel_split = r.kernel_ms_split_history(min(args.steps, 64))
-        warm_split = None
     avg_kernel_ms = max_over_ranks(sum(kernel_ms) / len(kernel_ms))
     is_po = wl == "c2_po"
-    ordered_frames = bool(r.last_frame_tile_ordered()) if (is_lav2 or is_po) else False
-    if cold_headline:
-        ordered_frames = True  # (the warm frames above were; the latency figures below measure both)
-    perturb_steps, at_iters, la_steps = float(st["perturb_steps"]), float(st["at_iterations"]), float(st["la_steps"])
-    # HDRFloat<double> / <CudaDblflt> LAv2: the AT iterations the launch actually RAN (statistics word 5 of k_lav2_lit / k_lav2_2x32: the AT loop's cycle search
-    # spares a pixel inside the set most of the iterations the limit asks of it -- same state, same count, same frame).  The
-    # roofline prices executed work; at_iterations_per_launch stays what the reference's loop would run.
-    at_iters_executed = float(st.get("careful_steps", 0)) if (wl in ("c4_hdr64", "c4_2x32") and st.get("careful_steps")) else at_iters
-    if wl == "c4_hdr64" and tile_order_on and not cold_headline and st.get("scaled_steps"):
-        # the timed frames run PerformAT in a pass of its own, whose lanes are grouped by what each pixel needs by itself
-        # (statistics word 6 of the counting launch, which iterates inside the frame's kernel and waits for the wave's slowest)
-        at_iters_executed = float(st["scaled_steps"])
-    lane_slots = st["lane_slots"]
-    b_main = state["last"]
-    checksum = int(host_np[b_main][:H, :W].astype(np.uint64).sum()) if rank == 0 else None
-    frame_main = host_np[b_main].copy() if rank == 0 else None
-    crc_main = frame_crc32(frame_main, H, W) if rank == 0 else None
-    # latency of ONE frame (launch -> host, nothing overlapped), warm and cold (natural tile order: what the FIRST frame of a
-    # view costs; fs_forget_tile_costs before every frame)
-    n_lat = max(1, min(args.steps, 5))
-    lat_warm_ms, lat_warm_k = latency(parity, n_lat)
-    lat_cold_ms = lat_cold_k = None
-    if ordered_frames and not args.no_cold:
-        lat_cold_ms, lat_cold_k = latency(parity, n_lat, cold=True)
-        one_frame(parity)  # (leave the renderer warm again)
+    if full:
+        ordered_frames = bool(r.last_frame_tile_ordered()) if (is_lav2 or is_po) else False
+        if cold_headline:
+            ordered_frames = True  # (the warm frames above were; the latency figures below measure both)
+        perturb_steps, at_iters, la_steps = float(st["perturb_steps"]), float(st["at_iterations"]), float(st["la_steps"])
+        # HDRFloat<double> / <CudaDblflt> LAv2: the AT iterations the launch actually RAN (statistics word 5 of k_lav2_lit / k_lav2_2x32: the AT loop's cycle search
+        # spares a pixel inside the set most of the iterations the limit asks of it -- same state, same count, same frame).  The
+        # roofline prices executed work; at_iterations_per_launch stays what the reference's loop would run.
+        at_iters_executed = float(st.get("careful_steps", 0)) if (wl in ("c4_hdr64", "c4_2x32") and st.get("careful_steps")) else at_iters
+        if wl == "c4_hdr64" and tile_order_on and not cold_headline and st.get("scaled_steps"):
+            # the timed frames run PerformAT in a pass of its own, whose lanes are grouped by what each pixel needs by itself
+            # (statistics word 6 of the counting launch, which iterates inside the frame's kernel and waits for the wave's slowest)
+            at_iters_executed = float(st["scaled_steps"])
+        lane_slots = st["lane_slots"]
+        b_main = state["last"]
+        checksum = int(host_np[b_main][:H, :W].astype(np.uint64).sum()) if rank == 0 else None
+        frame_main = host_np[b_main].copy() if rank == 0 else None
+        crc_main = frame_crc32(frame_main, H, W) if rank == 0 else None
+        # latency of ONE frame (launch -> host, nothing overlapped), warm and cold (natural tile order: what the FIRST frame of a
+        # view costs; fs_forget_tile_costs before every frame)
+        n_lat = max(1, min(args.steps, 5))
+        lat_warm_ms, lat_warm_k = latency(parity, n_lat)
+        lat_cold_ms = lat_cold_k = None
+        if ordered_frames and not args.no_cold:
+            lat_cold_ms, lat_cold_k = latency(parity, n_lat, cold=True)
+            one_frame(parity)  # (leave the renderer warm again)
     frame_timing = None
-    if rank == 0:
+    if rank == 0 and full:
         frame_timing = {
             "sustained_ms_per_frame": round(elapsed / args.steps * 1e3, 3),
             "latency_ms_warm": round(lat_warm_ms, 3), "latency_kernel_ms_warm": round(sum(lat_warm_k) / len(lat_warm_k), 3),
@@ -666,7 +707,7 @@ def main():
     # ---- secondary: the same frame with the LA stages in use (GPU-direction stage test), driver-timed like `value`
     secondary = None
     frame_secondary = None
-    if wl == "c3_lav2" and args.parity == "cpu" and not args.no_secondary:
+    if full and wl == "c3_lav2" and args.parity == "cpu" and not args.no_secondary:
         st2 = count_steps(PARITY_CPU_GPUSTAGE)
         one_frame(PARITY_CPU_GPUSTAGE)
         el2, km2 = timed(PARITY_CPU_GPUSTAGE)
@@ -693,7 +734,7 @@ def main():
     cpu_baseline = None
     cpu_baseline_patched = None
     parity_rows_ok = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and full and not args.no_cpu:
         import _oracle
         threads = effective_cpus()
         # rows per host thread chosen per workload so that the sample is about 10 s of CPU work on the box's 16 threads (the
@@ -737,7 +778,7 @@ def main():
             cpu_baseline_patched = line(cpu_t2, "the same function with LAReference::isLAStageInvalid in the GPU direction")
 
     traffic = None
-    if rank == 0:
+    if rank == 0 and full:
         # HBM bytes per launch from the rocprofv3 PMC passes committed under profiles/ (collected in separate
         # --pmc runs by tools/pmc_passes.sh); null for workloads that have not been profiled.
         key = "view%d_%dx%d_%s" % (args.view, W, H, wl_tag)
@@ -752,6 +793,26 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = W * H * args.steps / elapsed / 1e6
+        dtype = "2xf32+i32exp" if is2x32 else ("f64+i32exp" if is64 else ("f64" if is_direct else "f32+i32exp"))
+        # what a plain run measures and prints (a --full line carries the same keys with the same meaning, and everything else)
+        headline = {
+            "metric": "Mpix/s (iteration buffer), View #5 3840x2160 HDRx32 LAv2" if wl == "c3_lav2"
+            else "Mpix/s (iteration buffer), " + wl,
+            "value": round(value, 4), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong", "dtype": dtype,
+            "data": "built-in view %d of the reference (deterministic: no dataset or randomness on this path)" % args.view,
+            "window": "kernel launch -> iteration buffer in (page-locked) host memory, SURVEY.md 8(d); K frames back to back "
+                      "(sustained; frame_timing of a --full line holds the latency of one frame)",
+            "full": full,
+        }
+    if rank == 0 and not full:
+        headline["config"] = {"workload": "view%d_%dx%d_%s" % (args.view, W, H, wl_tag), "parity": args.parity,
+                              "kernel_variant": args.variant or "tuned", "n_iterations": n_iter,
+                              "host_path": ("one device" if not distributed else args.host_path),
+                              "frames": ("cold: every timed frame is the first frame of its view" if cold_headline
+                                         else "warm: frames of one view back to back")}
+        result_line = json.dumps(headline)
+    if rank == 0 and full:
         flops_issued = None
         if is2x32:
             # SURVEY.md 8(d)'s ALGORITHMIC count, the same for every numeric type: AT iteration 10, perturbation step 18, LA step
@@ -805,10 +866,7 @@ def main():
         wl_key = "view%d_%dx%d_%s" % (args.view, W, H, wl_tag)
         orc = oracle_frame_record(wl_key, args.parity, n_iter)
         out = {
-            "metric": "Mpix/s (iteration buffer), View #5 3840x2160 HDRx32 LAv2" if wl == "c3_lav2"
-            else "Mpix/s (iteration buffer), " + wl,
-            "value": round(value, 4), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong",
+            **headline,
             # a view's FIRST frame beside the sustained figure (frame_timing.latency_ms_cold: one frame, launch -> host, nothing
             # overlapped, nothing recorded by an earlier frame); for the two workloads whose `value` is cold already, the warm
             # sustained figure and its kernel time
@@ -820,10 +878,6 @@ def main():
                                       "k_lav2_hdr64": round(sum(warm_split[1]) / len(warm_split[1]), 3)}
                                      if cold_headline and wl == "c4_hdr64" and any(warm_split[0]) else None),
             "vs_baseline": None,
-            "dtype": "2xf32+i32exp" if is2x32 else ("f64+i32exp" if is64 else ("f64" if is_direct else "f32+i32exp")),
-            "data": "built-in view %d of the reference (deterministic: no dataset or randomness on this path)" % args.view,
-            "window": "kernel launch -> iteration buffer in (page-locked) host memory, SURVEY.md 8(d); K frames back to back "
-                      "(sustained, see frame_timing for the latency of one frame)",
             "config": {"workload": "view%d_%dx%d_%s" % (args.view, W, H, wl_tag),
                        "parity": args.parity, "kernel_variant": args.variant or "tuned", "n_iterations": n_iter,
                        "orbit_entries": orbit.count if orbit is not None else 0,

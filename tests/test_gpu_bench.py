@@ -15,12 +15,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--width", "960", "--height", "544", "--steps", "3", "--warmup", "1", "--no-secondary", "--cpu-sample-rows", "4"]
 
 
-def _run(extra_args, extra_env=None, timeout=900):
+def _run(extra_args, extra_env=None, timeout=900, full=True):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["FS_NO_BUILD"] = "1"
     env.update(extra_env or {})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, *extra_args], stdout=subprocess.PIPE,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, *(["--full"] if full else []), *extra_args],
+                       stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, env=env, timeout=timeout, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
@@ -111,7 +112,8 @@ def test_c1_direct_line(native_libs):
     frame rendered in the same run and == the committed oracle CRC."""
     env = dict(os.environ)
     env["FS_NO_BUILD"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1_direct", "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1_direct", "--steps", "3", "--warmup", "1",
+                        "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     d = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.strip()][-1])
@@ -119,3 +121,21 @@ def test_c1_direct_line(native_libs):
     assert d["cpu_sample_rows_bit_exact"] is True and d["frame_crc32_equals_oracle_frame"] is True
     assert d["roofline"]["kernel"] == "k_direct_f64" and d["roofline"]["frac"] > 0
     assert d["cpu_baseline"]["value"] > 0
+
+
+def test_plain_line_and_dumped_outputs(single, tmp_path):
+    """Without --full the line is the headline alone, for exactly --steps timed frames; --dump-outputs writes the iteration
+    buffer of the last timed frame, which is the frame of the --full run (same sum), and the same file on every run."""
+    import numpy as np
+    a = _run(["--steps", "2", "--dump-outputs", str(tmp_path / "a")], full=False)
+    assert a["full"] is False and a["steps"] == 2 and a["n_gpus"] == 1
+    assert a["metric"] == single["metric"] and a["unit"] == "Mpix/s" and a["higher_is_better"] is True
+    assert a["dtype"] == single["dtype"] == "f32+i32exp"
+    assert a["ms_per_step"] > 0 and abs(a["value"] - 960 * 544 / a["ms_per_step"] / 1e3) <= 1e-3 * a["value"]
+    assert a["config"]["workload"] == single["config"]["workload"]
+    assert "roofline" not in a and "cpu_baseline" not in a and "frame_timing" not in a
+    it = np.load(tmp_path / "a" / "iterations.npy")
+    assert it.shape == (544, 960) and it.dtype == np.float32
+    assert int(it.astype(np.float64).sum()) == single["frame_checksum"]
+    _run(["--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")], full=False)
+    assert np.array_equal(np.load(tmp_path / "b" / "iterations.npy"), it)

@@ -23,7 +23,7 @@ def _bench(workload, rows, timeout=1500):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["FS_NO_BUILD"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "2", "--warmup", "1",
-           "--no-secondary", "--cpu-sample-rows", str(rows)]
+           "--no-secondary", "--cpu-sample-rows", str(rows), "--full"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=timeout, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]

@@ -2,19 +2,33 @@
 vectors -- the CRC-64s of the PNG files in FractalSharkTest/TestRenderGoldens.cpp:84-97 -- and against the
 committed fixtures.  A matching CRC pins the whole chain view -> GMP orbit -> LA/BLA table -> CPU render ->
 palette -> PNG bit-exactly."""
+import json
 import os
 
 import numpy as np
 import pytest
 
 import _oracle
+import golden_cases
 from fractalshark_amd import inputs
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "golden_small.npz"))
 W = H = 256  # kGoldenWidth / kGoldenHeight
 
-needs_pin = pytest.mark.skipif(_oracle.pin_lib() is None,
-                               reason="oracle/_ref/libpngpin.so not built (needs /root/reference)")
+GOLDEN_CRC = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "golden_crc.json")))
+
+
+def assert_golden(it, name, crc64, num_iterations, aa=1):
+    """The oracle's buffer for the reference's golden case `name`: its CRC-32 and sum are those committed in
+    tests/golden/golden_crc.json (written only after the oracle's PNG reproduced the reference's CRC-64 literal), and where the
+    pin library was built (oracle/_ref/libpngpin.so) the PNG of that buffer has the literal CRC-64 itself."""
+    g = GOLDEN_CRC[name]
+    assert g["png_crc64"] == crc64 and g["antialiasing"] == aa
+    assert list(it.shape) == g["iter_buffer_shape"]
+    assert golden_cases.buffer_crc32(it) == g["iter_buffer_crc32"], name
+    assert int(it.astype(np.uint64).sum()) == g["iter_sum"], name
+    if _oracle.pin_lib() is not None:
+        assert _oracle.png_crc64(it, W, H, aa, num_iterations) == crc64
 
 
 @pytest.fixture(scope="module")
@@ -24,28 +38,25 @@ def view5(native_libs):
     return v, ob
 
 
-@needs_pin
 @pytest.mark.parametrize("aa,expected", [(1, "1275500d639ad02e"), (4, "39671027bacf2567")])
 def test_golden_view0_cpu64(native_libs, aa, expected):
     v = inputs.View.builtin(0, W, H, antialiasing=aa)
     it = _oracle.direct_f64(v, aa=aa)
-    assert _oracle.png_crc64(it, W, H, aa, v.num_iterations) == expected
+    assert_golden(it, "view0-cpu64" if aa == 1 else "view0-cpu64-aa%d" % aa, expected, v.num_iterations, aa)
 
 
-@needs_pin
 def test_golden_view5_cpu32_perturbed_blav2_hdr(view5):
     v, ob = view5
     la = inputs.LATable(ob)
     it = _oracle.lav2_hdr32(v, ob, la, stage_test=0)
-    assert _oracle.png_crc64(it, W, H, 1, v.num_iterations) == "1233a56b293e7b08"
+    assert_golden(it, "view5-cpu-bla-v2", "1233a56b293e7b08", v.num_iterations)
 
 
-@needs_pin
 def test_golden_view5_cpu32_perturbed_bla_hdr(view5):
     v, ob = view5
     bla = inputs.BLATable(ob)
     it = _oracle.bla_hdr32(v, ob, bla)
-    assert _oracle.png_crc64(it, W, H, 1, v.num_iterations) == "634d826801d54979"
+    assert_golden(it, "view5-cpu32-bla-hdr", "634d826801d54979", v.num_iterations)
 
 
 def test_view5_inputs_match_fixture(native_libs):
@@ -99,43 +110,38 @@ def test_la_table_threading_replay_equivalent(native_libs):
 
 
 # ---- HDRFloat<double> family and the HDR direct functions: five more of the reference's golden CRCs
-@needs_pin
 def test_golden_view5_cpu64_perturbed_blav2_hdr(native_libs):
     v = inputs.View.builtin(5, W, H)
     ob = inputs.Orbit(v, is64=True)
     la = inputs.LATable(ob)
     it = _oracle.lav2_hdr32(v, ob, la, stage_test=0)
-    assert _oracle.png_crc64(it, W, H, 1, v.num_iterations) == "ca7ad7c5f9cf750e"
+    assert_golden(it, "view5-cpu64-bla-v2", "ca7ad7c5f9cf750e", v.num_iterations)
 
 
-@needs_pin
 def test_golden_view5_cpu64_perturbed_bla_hdr(native_libs):
     v = inputs.View.builtin(5, W, H)
     ob = inputs.Orbit(v, is64=True)
     bla = inputs.BLATable(ob)
     it = _oracle.bla_hdr32(v, ob, bla)
-    assert _oracle.png_crc64(it, W, H, 1, v.num_iterations) == "c91e33c3eb85b33d"
+    assert_golden(it, "view5-cpu64-bla-hdr", "c91e33c3eb85b33d", v.num_iterations)
 
 
-@needs_pin
 def test_golden_view1_cpu64_perturbed_bla_hdr(native_libs):
     v = inputs.View.builtin(1, W, H)
     ob = inputs.Orbit(v, is64=True)
     bla = inputs.BLATable(ob)
     it = _oracle.bla_hdr32(v, ob, bla)
-    assert _oracle.png_crc64(it, W, H, 1, v.num_iterations) == "d0c8921c878f6dc3"
+    assert_golden(it, "view1-cpu-bla", "d0c8921c878f6dc3", v.num_iterations)
 
 
-@needs_pin
 @pytest.mark.parametrize("is64,expected", [(False, "66ba2caaaa7f8013"), (True, "1275500d639ad02e")])
 def test_golden_view0_cpuhdr(native_libs, is64, expected):
     v = inputs.View.builtin(0, W, H)
     it = _oracle.direct_hdr(v, is64)
-    assert _oracle.png_crc64(it, W, H, 1, v.num_iterations) == expected
+    assert_golden(it, "view0-cpuhdr64" if is64 else "view0-cpuhdr", expected, v.num_iterations)
 
 
 # ---- PerturbExtras::SimpleCompression ("RC" algorithms): compressed reference orbit + runtime decompression
-@needs_pin
 @pytest.mark.parametrize("is64,expected", [(False, "b956600cfdfe431a"), (True, "68df9ceecaf1a667")])
 def test_golden_view5_rc_blav2_hdr(native_libs, is64, expected):
     v = inputs.View.builtin(5, W, H)
@@ -143,13 +149,12 @@ def test_golden_view5_rc_blav2_hdr(native_libs, is64, expected):
     assert ob.compressed_count < ob.count
     la = inputs.LATable(ob)
     it = _oracle.lav2_hdr32(v, ob, la, stage_test=0)
-    assert _oracle.png_crc64(it, W, H, 1, v.num_iterations) == expected
+    assert_golden(it, "view5-cpu64-rc-bla-v2" if is64 else "view5-cpu32-rc-bla-v2", expected, v.num_iterations)
 
 
-@needs_pin
 def test_golden_view5_cpu64_perturbed_bla_plain_double(native_libs):
     """The twelfth golden: plain-double perturbation + BLA (Cpu64PerturbedBLA)."""
     v = inputs.View.builtin(5, W, H)
     ob = inputs.OrbitF64(v)
     it = _oracle.bla_f64(v, ob)
-    assert _oracle.png_crc64(it, W, H, 1, v.num_iterations) == "f201db00ade569fc"
+    assert_golden(it, "view5-cpu-perturbed-bla", "f201db00ade569fc", v.num_iterations)

@@ -7,6 +7,7 @@
 # profiled process must never spawn a compiler (the profiler's preload has initialised the GPU; exec from such a
 # process tree takes the box down).
 tag=$1; shift
+set -- --full "$@"  # (the launches of a --full bench run)
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 python3 -c 'from fractalshark_amd import _build; _build.build_all()' || exit 1

@@ -13,6 +13,7 @@ python3 -c 'import sys; sys.path.insert(0, "tests"); import _oracle; _oracle.bui
 export FS_NO_BUILD=1
 run_stats() { # name, bench args...
   name=$1; shift
+  set -- --full "$@"  # (the launches and the line of a --full bench run)
   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag}_${name} -- python3 bench.py "$@" --no-build > gpurun_out/prof_${tag}_${name}.json 2> gpurun_out/prof_${tag}_${name}.err
 }
 run_stats c3_default
