@@ -71,31 +71,21 @@ def _render_headers():
                   [os.path.join(ROOT, "include", f) for f in ("fsmi355.h", "fsmi355_internal.h", "fs_layout.h")])
 
 
-def _render_flags():
-    # FS_PROFILE_CYCLES=1: the instrumented (step-counting) kernel variants also report shader-clock cycles per phase
-    # (tools/cycle_probe.py); never set for the product build
-    extra = ["-DFS_PROFILE_CYCLES"] if os.environ.get("FS_PROFILE_CYCLES") == "1" else []
-    if os.environ.get("FS_VERIFY_BLOCK_BOUND") == "1":  # tools/block_bound_check.py: the untested loop off, violations counted
-        extra.append("-DFS_VERIFY_BLOCK_BOUND")
-    if os.environ.get("FS_BACKOFF_CAP"):  # A/B: back-off cap of the scaled-run attempts (scaled_runs.hpp; 0 = off)
-        extra.append("-DFS_BACKOFF_CAP=%d" % int(os.environ["FS_BACKOFF_CAP"]))
-    if os.environ.get("FS_TRACE_WAVES") == "1":  # tools/wave_trace.py: per-wave start / end / SIMD records
-        extra.append("-DFS_TRACE_WAVES")
-    if os.environ.get("FS_VERIFY_FLOOR") == "1":  # tools/floor_check.py: trips whose untested first state is below the every-state floor
-        extra.append("-DFS_VERIFY_FLOOR")
-    if os.environ.get("FS_BLA_FAST_PROBE") == "1":  # tools/bla_fast_check.py: how often the hand-written BLA loop is left (statistics words 20..23)
-        extra.append("-DFS_BLA_FAST_PROBE")
-    if os.environ.get("FS_FD_LANE_BOUND") == "1":  # A/B: round 4's per-lane block test in C3's untested loop
-        extra.append("-DFS_FD_LANE_BOUND")
-    if os.environ.get("FS_FD16_SERIAL") == "1":  # A/B: round 4's 16-step body (wait right behind the request) instead of the pipelined one
-        extra.append("-DFS_FD16_SERIAL")
-    if os.environ.get("FS_2X32_PROBE") == "1":  # counts the 2x32 perturbation loop's literal steps (statistics word 12)
-        extra.append("-DFS_2X32_PROBE")
-    for name in ("FS_FL_EVERY", "FS_FL_SHIFT", "FS_FL_FLOOR_EXP", "FS_HOT_RUN_STEPS", "FS_PO_CHUNK", "FS_AT_CYCLE_CHUNK", "FS_HOT_AFTER_FAIL"):  # A/B: form and scale of the scaled runs' floor tests (kernels.hip)
-        if os.environ.get(name):
-            extra.append("-D%s=%d" % (name, int(os.environ[name])))
-    if os.environ.get("FS_SCALED_CHUNK"):  # tuning experiments only
-        extra.append("-DFS_SCALED_CHUNK=" + str(int(os.environ["FS_SCALED_CHUNK"])))
+# Build-time switches of the probe and verification builds that tools/ make (environment variable = 1 -> -D<name>); never set
+# for the product build
+_PROBE_SWITCHES = (
+    "FS_PROFILE_CYCLES",      # the instrumented (step-counting) kernel variants also report shader-clock cycles per phase (tools/cycle_probe.py)
+    "FS_VERIFY_BLOCK_BOUND",  # tools/block_bound_check.py: the untested loop off, violations counted
+    "FS_TRACE_WAVES",         # tools/wave_trace.py: per-wave start / end / SIMD records
+    "FS_VERIFY_FLOOR",        # tools/floor_check.py: the every-second-state floor form, trips whose untested first state is below the every-state floor counted
+    "FS_BLA_FAST_PROBE",      # tools/bla_fast_check.py: how often the hand-written BLA loop is left (statistics words 20..23)
+    "FS_2X32_PROBE",          # counts the 2x32 perturbation loop's literal steps (statistics word 12)
+)
+
+
+def _render_flags(env=None):
+    env = os.environ if env is None else env
+    extra = ["-D" + name for name in _PROBE_SWITCHES if env.get(name) == "1"]
     return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", *extra]
 
 
@@ -105,53 +95,44 @@ def _render_flags():
 _UNIT_FLAGS = {"kernels_scaled.hip": ["-fno-slp-vectorize"]}
 
 
-# Units whose DEVICE code goes through tools/asm_peephole.py between the compiler and the assembler (v_cndmask_b32_e32 -> _e64).
-# EMPTY: back to back the 32-bit encoding of the select issues five times slower than the 64-bit one on gfx950
-# (profiles/r06_valu_issue_rates_f64.jsonl), but in a kernel -- k_lav2_hdr64, 838 selects rewritten, same box -- the frame time did not
-# move (33.33 against 33.28 ms, profiles/r06_c4_hdr64_kernel_ab_same_box.jsonl): the selects of real code are not back to back.  The
-# step stays for A/B builds (FS_PEEPHOLE_UNITS=kernels_x.hip,... in the environment of tools/build_variant.py).
-PEEPHOLE_TOOL = os.path.join(ROOT, "tools", "asm_peephole.py")
-_PEEPHOLE_UNITS = set(u for u in os.environ.get("FS_PEEPHOLE_UNITS", "").split(",") if u)
-LLVM_BIN = "/opt/rocm/lib/llvm/bin"
+def _unit_flags(src):
+    return _UNIT_FLAGS.get(os.path.basename(src), [])
 
 
-def _peephole_state():
-    return "peephole:" + (",".join(sorted(_PEEPHOLE_UNITS)) if os.environ.get("FS_PEEPHOLE", "1") != "0" else "off")
+def _unit_digest(src, hdr_digest, extra=()):
+    return _digest([src], [hdr_digest, *_unit_flags(src), *extra])
 
 
-def _peephole_on(src):
-    return src.endswith(".hip") and os.path.basename(src) in _PEEPHOLE_UNITS and os.environ.get("FS_PEEPHOLE", "1") != "0"
-
-
-def compile_one(hipcc, src, obj, flags, peephole):
-    """One translation unit -> object.  Plain: hipcc -c.  With the peephole: the driver's own steps taken apart -- device code to
-    assembly, the rewrite, assembler, lld (code object), clang-offload-bundler (fat binary), then the host pass with that binary."""
+def _compile(hipcc, src, obj, flags):
     # renderer.cpp / group.cpp are host-only C++ that include HIP runtime headers: compiled by hipcc as HIP so
     # that <hip/hip_runtime.h> types (float4, hipStream_t) match the kernels' launchers
     lang = [] if src.endswith(".hip") else ["-x", "hip"]
-    if not peephole:
-        _run([hipcc, *flags, "-c", *lang, src, "-o", obj])
-        return
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("fs_asm_peephole", PEEPHOLE_TOOL)
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
-    base = obj[:-2] if obj.endswith(".o") else obj
-    asm, asm2, dev, hsaco, fb = base + ".dev.s", base + ".dev.pp.s", base + ".dev.o", base + ".hsaco", base + ".hipfb"
-    _run([hipcc, *flags, "--cuda-device-only", "-S", *lang, src, "-o", asm])
-    text, n = tool.rewrite(open(asm).read())
-    open(asm2, "w").write(text)
-    _run([os.path.join(LLVM_BIN, "clang"), "-x", "assembler", "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950", "-c", asm2, "-o", dev])
-    _run([os.path.join(LLVM_BIN, "lld"), "-flavor", "gnu", "-m", "elf64_amdgpu", "--no-undefined", "-shared", "-o", hsaco, dev])
-    _run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "-type=o", "-bundle-align=4096",
-          "-targets=host-x86_64-unknown-linux-gnu,hipv4-amdgcn-amd-amdhsa--gfx950", "-input=/dev/null", "-input=" + hsaco,
-          "-output=" + fb])
-    _run([hipcc, *flags, "--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", fb, "-c", *lang, src, "-o", obj])
-    for f in (asm, dev, hsaco, fb):  # (the rewritten assembly stays next to the object: what was assembled can be read)
-        try:
-            os.remove(f)
-        except OSError:
-            pass
+    _run([hipcc, *flags, *_unit_flags(src), "-c", *lang, src, "-o", obj])
+
+
+def _hipcc():
+    return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+def _compile_all(jobs, force=False):
+    """jobs: (src, obj, flags, digest) -- each object is compiled unless its stamp already matches its digest."""
+    hipcc = _hipcc()
+
+    def one(job):
+        src, obj, flags, d = job
+        if force or not _stamp_ok(obj, d):
+            _compile(hipcc, src, obj, flags)
+            _write_stamp(obj, d)
+        return obj
+
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+        return list(ex.map(one, jobs))
+
+
+def _link(lib, objs):
+    # RCCL (the multi-GPU gather behind fs_group_*) is resolved at run time with dlopen, so the library loads on hosts
+    # without it; -ldl only
+    _run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs, "-ldl", "-lpthread"])
 
 
 def _inputs_sources():
@@ -163,11 +144,14 @@ def _inputs_sources():
 _INPUTS_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 
+def _render_digest(units, headers, flags):
+    return _digest(units + headers, flags + [repr(sorted(_UNIT_FLAGS.items()))])
+
+
 def up_to_date():
     """True when both libraries exist and were built from the current sources (no compiler is started)."""
     units = [u for u in _render_units() if os.path.exists(u)]
-    return (_stamp_ok(LIB_RENDER, _digest(units + _render_headers() + [PEEPHOLE_TOOL],
-                                          _render_flags() + [repr(sorted(_UNIT_FLAGS.items())), _peephole_state()])) and
+    return (_stamp_ok(LIB_RENDER, _render_digest(units, _render_headers(), _render_flags())) and
             _stamp_ok(LIB_INPUTS, _digest(_inputs_sources(), _INPUTS_FLAGS)))
 
 
@@ -175,30 +159,41 @@ def build_render(force=False):
     units = [u for u in _render_units() if os.path.exists(u)]
     headers = _render_headers()
     flags = _render_flags()
-    digest = _digest(units + headers + [PEEPHOLE_TOOL], flags + [repr(sorted(_UNIT_FLAGS.items())), _peephole_state()])
+    digest = _render_digest(units, headers, flags)
     if not force and _stamp_ok(LIB_RENDER, digest):
         return LIB_RENDER
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     os.makedirs(OBJ, exist_ok=True)
     hdr_digest = _digest(headers, flags)
-
-    def compile_unit(src):
-        obj = os.path.join(OBJ, os.path.basename(src) + ".o")
-        unit_flags = _UNIT_FLAGS.get(os.path.basename(src), [])
-        peep = _peephole_on(src)
-        d = _digest([src] + ([PEEPHOLE_TOOL] if peep else []), [hdr_digest, *unit_flags, "peephole" if peep else ""])
-        if force or not _stamp_ok(obj, d):
-            compile_one(hipcc, src, obj, [*flags, *unit_flags], peep)
-            _write_stamp(obj, d)
-        return obj
-
-    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        objs = list(ex.map(compile_unit, units))
-    # RCCL (the multi-GPU gather behind fs_group_*) is resolved at run time with dlopen, so the library loads on hosts
-    # without it; -ldl only
-    _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_RENDER, *objs, "-ldl", "-lpthread"])
+    jobs = [(src, os.path.join(OBJ, os.path.basename(src) + ".o"), flags, _unit_digest(src, hdr_digest)) for src in units]
+    _link(LIB_RENDER, _compile_all(jobs, force))
     _write_stamp(LIB_RENDER, digest)
     return LIB_RENDER
+
+
+def build_variant(name, units, defs):
+    """build/ab/libfsmi355_<name>.so: the product with the translation units named in `units` (base names) compiled with the extra
+    flags `defs` (and the probe switches of the environment); select it at run time with FSMI355_LIB.  Writes under build/ab/ only:
+    the other units come from the product's objects where their stamps say they were built from the current sources with the
+    product's flags, else they are compiled into build/ab/<name>/.  Returns the path."""
+    out_dir = os.path.join(ROOT, "build", "ab", name)
+    os.makedirs(out_dir, exist_ok=True)
+    headers = _render_headers()
+    flags, product_flags = _render_flags(), _render_flags({})
+    hdr_digest, product_hdr_digest = _digest(headers, flags), _digest(headers, product_flags)
+    jobs = []
+    for src in _render_units():
+        base = os.path.basename(src)
+        if base in units:
+            jobs.append((src, os.path.join(out_dir, base + ".o"), [*flags, *defs], _unit_digest(src, hdr_digest, defs)))
+            continue
+        d = _unit_digest(src, product_hdr_digest)
+        obj = os.path.join(OBJ, base + ".o")
+        if not _stamp_ok(obj, d):
+            obj = os.path.join(out_dir, base + ".o")
+        jobs.append((src, obj, product_flags, d))
+    lib = os.path.join(ROOT, "build", "ab", "libfsmi355_%s.so" % name)
+    _link(lib, _compile_all(jobs))
+    return lib
 
 
 def build_inputs(force=False):
@@ -217,25 +212,19 @@ def build_all(force=False):
     return build_render(force), build_inputs(force)
 
 
-if __name__ == "__main__":
-    print(build_all(force=True))
-
-
 def status2_test_variant():
     """build/ab/libfsmi355_h64st2.so: the library with k_lav2_hdr64's hand-written statements taking their rarest exit (status 2) on
-    EVERY step (-DFS_H64_ASM_TINY=1e300) -- what tests/test_gpu_hdr64_statement_exits.py renders with.  Built by tools/build_variant.py
-    when its content stamp does not match the sources; returns the path."""
-    import sys
+    EVERY step (-DFS_H64_ASM_TINY=1e300) -- what tests/test_gpu_hdr64_statement_exits.py renders with.  Built (build_variant) when its
+    content stamp does not match the sources; returns the path."""
     defs = ["-DFS_H64_ASM_TINY=1e300"]
     lib = os.path.join(ROOT, "build", "ab", "libfsmi355_h64st2.so")
-    stamp = lib + ".stamp"  # (by content, as the product's own stamp: file times mean nothing on a freshly copied tree)
+    # (by content, as the product's own stamp: file times mean nothing on a freshly copied tree)
     digest = _digest(_render_units() + _render_headers(), _render_flags() + defs)
-    if not os.path.exists(lib) or not os.path.exists(stamp) or open(stamp).read().strip() != digest:
-        env = {k: v for k, v in os.environ.items() if k != "FSMI355_LIB"}
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "build_variant.py"), "h64st2", "kernels_hdr64.hip", *defs], cwd=ROOT,
-                           env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        if p.returncode != 0:
-            raise RuntimeError("build of the status-2 test variant failed:\n" + p.stdout[-3000:])
-        with open(stamp, "w") as f:
-            f.write(digest + "\n")
+    if not _stamp_ok(lib, digest):
+        build_variant("h64st2", ["kernels_hdr64.hip"], defs)
+        _write_stamp(lib, digest)
     return lib
+
+
+if __name__ == "__main__":
+    print(build_all(force=True))

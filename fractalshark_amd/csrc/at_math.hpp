@@ -170,10 +170,8 @@ __device__ __forceinline__ void at_perform(const hcplx<F> c, const hreal<F> esc,
                         // statement's budget ends (every kAtCycleChunk = 16 iterations): compare with a kept state, keep a new one
                         // at doubling distances.  When every lane still iterating has found its cycle the wave leaves the loop
                         // and each lane walks its remainder.  Same states, same iteration count, same results.
-#ifndef FS_AT_CYCLE_CHUNK
-#define FS_AT_CYCLE_CHUNK 16 /* measured on C4 (ms per frame): 8: 46.0, 16: 45.8, 32: 46.1, 64: 46.7, 128: 48.1, 256: 51.3 */
-#endif
-                        constexpr uint32_t kAtCycleChunk = FS_AT_CYCLE_CHUNK;
+                        // (measured on C4, ms per frame: 8: 46.0, 16: 45.8, 32: 46.1, 64: 46.7, 128: 48.1, 256: 51.3)
+                        constexpr uint32_t kAtCycleChunk = 16;
                         uint64_t s_re = ~0ull, s_im = ~0ull; // the kept state (bit patterns; all ones = a NaN no state equals)
                         IterT s_it = 0, s_next = (IterT)kAtCycleChunk, cyc_p = 0, cyc_at = 0; // cyc_p != 0: this lane has found its cycle (at iteration cyc_at)
                         bool all_cyclic = false;

@@ -22,15 +22,7 @@ __device__ __forceinline__ uint32_t global_row(const FsFrame &f, uint32_t L)
 __device__ __forceinline__ void tile_pixel(uint32_t &X, uint32_t &L)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#ifdef FS_TILE_STRIDE
-    // (A/B build, round 6: workgroups take the tile blocks in a strided order -- block v of the launch renders block v * FS_TILE_STRIDE mod N --
-    // so that a region of long pixels is spread over the launch instead of ending it)
-    const uint32_t nb = gridDim.x * gridDim.y;
-    const uint32_t v = (uint32_t)(((uint64_t)(blockIdx.y * gridDim.x + blockIdx.x) * (uint64_t)(FS_TILE_STRIDE)) % nb);
-    const uint32_t bx = v % gridDim.x, by = v / gridDim.x;
-#else
     const uint32_t bx = blockIdx.x, by = blockIdx.y;
-#endif
     X = (bx * (blockDim.x >> 6) + wave) * 8u + (lane & 7u);
     L = by * 8u + (lane >> 3);
 }

@@ -354,8 +354,7 @@ void fsk_tile_order(const uint32_t *probe, uint32_t probe_pitch, uint32_t tiles_
 uint32_t fsk_tile_order_work_words(uint32_t n_tiles);
 void fsk_tile_order_by_cost(const uint32_t *cost, uint32_t n_tiles, uint32_t *tmp, uint32_t *order, uint32_t n_slots,
                             hipStream_t s);
-// wave slots of the fsk_lav2_hdr32 launch for this frame (>= its number of 8 x 8 tiles), 0 = the launch shape is not the
-// default one (FSMI355_BLOCK experiment): no tile order then
+// wave slots of the fsk_lav2_hdr32 launch for this frame (>= its number of 8 x 8 tiles)
 uint32_t fsk_lav2_hdr32_slots(const FsFrame &f);
 void fsk_lav2_hdr32(const FsLav2Args32 &A, int mode, bool stats, int variant, hipStream_t s);
 void fsk_lav2_hdr64(const FsLav2ArgsT<double> &A, int mode, bool stats, hipStream_t s);
@@ -412,7 +411,7 @@ void fsk_at_tile_sample64(const FsTileSampleArgs &A, hipStream_t s);
 void fsk_tile_order_finish(uint32_t *order, uint32_t n_slots, uint32_t n_tiles, hipStream_t s);
 size_t fsk_pixel_order_temp_bytes(uint32_t n);
 hipError_t fsk_pixel_order_build(const uint32_t *counts, uint32_t n, uint32_t *work, uint32_t *order, void *temp, size_t temp_bytes,
-                                 hipStream_t s, int key_bits = 32);
+                                 hipStream_t s);
 void fsk_lav2_lit32(const FsLav2Args32 &A, int mode, bool stats, dim3 g, dim3 b, hipStream_t s); // kernels.hip
 void fsk_lav2_hdr64_fast(const FsLav2ArgsT<double> &A, int mode, bool stats, hipStream_t s); // kernels_hdr64.hip
 void fsk_perturb_scalar_hdr64(const FsBlaArgsT<double> &A, bool use_bla, bool stats, int variant, hipStream_t s);

@@ -110,7 +110,7 @@ __global__ void k_make_quiet_orbit(const float4 *__restrict__ zref, float4 *__re
     // the "never" pattern.)
     zq[n + i] = make_float4(__builtin_amdgcn_ldexpf(v.x, e + 1), __builtin_amdgcn_ldexpf(v.y, e + 1), b0,
                             scaled_block_bound(zref, i, n));
-    // the compact form for the 16-step body of the untested loop (FS_FAST_LOOP_FD16): 2Z alone, and the block bounds a body
+    // the compact form for the 16-step body of the untested loop (FS_FAST_LOOP_FD16P): 2Z alone, and the block bounds a body
     // whose first arrival is entry i needs -- those of its entries 3, 7, 11 (the states its second to fourth blocks start
     // from) and 15 (the state the NEXT body starts from)
     zs2[i] = make_float2(__builtin_amdgcn_ldexpf(v.x, e + 1), __builtin_amdgcn_ldexpf(v.y, e + 1));

@@ -233,20 +233,18 @@ __global__ void __launch_bounds__(256) k_lav2_2x32(FsLav2Args2x32 A)
                                                               : __builtin_amdgcn_ldexpf(esc.m.head, esc_sh) * 0.9999847412109375f;
                         // CYCLE SEARCH (round 5; at_math.hpp has the HDRFloat<double> form and the argument): the loop is a pure
                         // function of zz, so a state that comes back bit for bit -- looked for where i is a multiple of
-                        // kAtCycleChunk, against a state kept at doubling distances -- means the lane will go round that
+                        // kAt2CycleChunk, against a state kept at doubling distances -- means the lane will go round that
                         // cycle for good: it cannot escape, and its state after ATMaxIt iterations is the state
                         // (ATMaxIt - i) mod P iterations further on.  The lane's loop limit drops to exactly that many.
-#ifndef FS_AT_CYCLE_CHUNK
-#define FS_AT_CYCLE_CHUNK 8 /* measured on C4 as specified (ms per frame): 8: 198.8, 16: 200.0, 32: 202.4, 128: 219.2 */
-#endif
-                        constexpr uint32_t kAtCycleChunk = FS_AT_CYCLE_CHUNK;
+                        // (measured on C4 as specified, ms per frame: 8: 198.8, 16: 200.0, 32: 202.4, 128: 219.2)
+                        constexpr uint32_t kAt2CycleChunk = 8;
                         IterT lim = ATMaxIt;      // this lane's loop limit: ATMaxIt, or where its remainder round the cycle ends
-                        IterT s_it = 0, s_next = (IterT)kAtCycleChunk;
+                        IterT s_it = 0, s_next = (IterT)kAt2CycleChunk;
                         df32x2 s_zz(df32(__builtin_nanf(""), 0.0f), df32(0.0f, 0.0f)); // the kept state (a NaN equals nothing)
                         bool cyc = false, out = false;
 #define FS_AT2_LOOP(UPDATE)                                                                                         \
     while (i < lim && !out) {                                                                                       \
-        const IterT stop_ = (i | (IterT)(kAtCycleChunk - 1u)) + 1u;                                                 \
+        const IterT stop_ = (i | (IterT)(kAt2CycleChunk - 1u)) + 1u;                                                \
         const IterT end_ = stop_ < lim ? stop_ : lim;                                                               \
         for (; i < end_; i++) {                                                                                     \
             const df32x2 lhs = df32x2(zz.head.xx, zz.tail.xx) * zz;           /* (rr, re im) */                     \

@@ -12,12 +12,12 @@
 //  * HDRFloatComplex::plus_mutable (HDRFloatComplex.h:219-247) is a four-armed function of the exponent gap d = a.e - b.e:
 //    a alone (d >= 120), a + b 2^-d, a 2^d + b, b alone (d <= -120).  Compiled literally every add is four divergent arms with their
 //    EXEC bookkeeping -- 50 scalar instructions per step went there (SQ_INSTS_SALU 1.29e10 against SQ_INSTS_VALU 2.45e10, round 5).
-//    Here: votes on the gap.  A wave whose lanes all take the SAME arm -- nearly every wave: its lanes hold neighbouring pixels
-//    at the same phase of their orbits -- runs that arm alone: "a alone" / "b alone" return the operand as it is, and the two
-//    sums are  hi + ldexp(lo, -gap)  -- the same IEEE operations as the literal arm: 2^-gap is an exact power of two inside the
-//    normal range, so the product lo 2^-gap and ldexp(lo, -gap) are the same correctly rounded value (also where it is
-//    subnormal), and the addition commutes.  A mixed wave selects hi / lo per lane (eight 32-bit selects) and runs the same sum
-//    with the shift forced to -4000 (ldexp -> +-0, which leaves hi as it is) in the lanes whose gap is 120 or more.
+//    Here: one vote on the SIGN of the gap.  A wave whose lanes all have a on top (or all b) -- nearly every wave: its lanes hold
+//    neighbouring pixels at the same phase of their orbits -- runs one sum  hi + ldexp(lo, -gap)  -- the same IEEE operations as
+//    the literal arm: 2^-gap is an exact power of two inside the normal range, so the product lo 2^-gap and ldexp(lo, -gap) are
+//    the same correctly rounded value (also where it is subnormal), and the addition commutes.  A mixed wave selects hi / lo per
+//    lane (eight 32-bit selects) first.  In every lane whose gap is 120 or more the shift is forced to -4000 (ldexp -> +-0, which
+//    leaves hi as it is: the "alone" arms).
 //    Sign of zero (mixed waves only): "hi alone" in the literal code returns hi's bits, there hi + (+-0): a -0.0 part of hi can
 //    come out as +0.0.
 //    No operation of this kernel tells the two apart -- every comparison treats them as equal, fabs and the exponent field
@@ -75,21 +75,12 @@ __device__ __forceinline__ C64 add_hi_lo(C64 hi, const C64 lo)
     return hi;
 }
 
-// HDRFloatComplex::plus_mutable by votes on the exponent gap (see the head of this file).  nd = b.e - a.e decides the arm of the
-// literal function: (-120, 0] a + b 2^nd; [1, 119] a 2^-nd + b; <= -120 a alone; >= 120 b alone.  A wave whose lanes agree on the arm
-// -- nearly every wave: the lanes hold neighbouring pixels at the same phase -- runs that arm alone: five instructions (or none)
-// instead of the four-way divergent function; each arm ends in an empty asm with its own comment so that the compiler keeps the
-// arms apart (it would otherwise sink their common tail into one sequence behind operand copies).  kFirst: which agreement is
-// asked for first -- 0: the sum with a on top (2 Z + dz, Z + dz), 1: a alone (dz (2 Z + dz) + dc at a deep zoom, where dc is
-// hundreds of binades below everything else).  Mixed waves: per-lane operand select, then the same sum with the gap clamped.
-#ifndef FS_H64_PT_ASM
-#define FS_H64_PT_ASM 1 /* the perturbation steps of the ordered frames by hand (pt_step_asm.hpp); 0: the compiled loop, A/B.  (A first version
-                           -- named registers, seven waves, the step committed with seven moves -- was slower than the compiled loop: 34.65
-                           against 31.77 ms, profiles/r06r_c4_hand_written_pt_loop_ab.jsonl) */
-#endif
-#ifndef FS_H64_LA_ASM
-#define FS_H64_LA_ASM 1 /* the LA steps of a wave whose lanes stand at one record by hand (la_step_asm.hpp); 0: the compiled loop, A/B */
-#endif
+// HDRFloatComplex::plus_mutable by one vote on the exponent gap (see the head of this file).  nd = b.e - a.e decides the arm of the
+// literal function: (-120, 0] a + b 2^nd; [1, 119] a 2^-nd + b; <= -120 a alone; >= 120 b alone.  A wave whose lanes agree on the
+// sign of the gap runs one sum with the gap clamped (which covers the "alone" arms); each of the two ends in an empty asm with its own
+// comment so that the compiler keeps them apart (it would otherwise sink their common tail into one sequence behind operand copies).
+// Mixed waves: per-lane operand select, then the same sum.  (Votes on the ARM, no clamp in the agreed arms: 33.85 against 33.38 ms on
+// one box, profiles/r06f_*, not kept.)
 #ifndef FS_H64_STAGE_SCALAR
 #define FS_H64_STAGE_SCALAR 1 /* the stage's words and its first record's threshold through the scalar cache (0: A/B) */
 #endif
@@ -97,21 +88,7 @@ __device__ __forceinline__ C64 add_hi_lo(C64 hi, const C64 lo)
 #define FS_H64_ASM_TINY 0x1p-1000 /* what the hand-written statements take for "a norm the value compare cannot be trusted with".  (Test build: 1e300 -- EVERY
                                      step then leaves its statement with status 2, the one exit no view reaches by itself, and the frames must not change.) */
 #endif
-#ifndef FS_H64_ASM_COLD
-#define FS_H64_ASM_COLD 1 /* the first frame of a view runs the hand-written loops too (0: A/B -- 52.6 against 50.6 ms once the statements had their "alone" arms; 54.8 against 52.3 before) */
-#endif
-#ifndef FS_H64_LA_SCALAR
-#define FS_H64_LA_SCALAR 1 /* LA records through the scalar cache where the wave's lanes agree on the record (0: A/B) */
-#endif
-#ifndef FS_H64_LA_PIPE
-#define FS_H64_LA_PIPE 1 /* the LA loop's step length travels one step ahead (0: A/B -- 33.74 against 32.41 ms; record j + 2's Ref and length two
-                            steps ahead as well: 36.5 ms with 8 waves and spills, 33.7 with 7 -- not kept) */
-#endif
-#ifndef FS_H64_ADDV
-#define FS_H64_ADDV 2 /* 2 = one vote on the SIGN of the gap, the sum with the shift clamped in every arm; 3 = votes on the ARM (a alone / a + b 2^nd / ...), no clamp in the agreed arms: 33.85 against 33.38 ms on one box (profiles/r06f_*), off */
-#endif
-#if FS_H64_ADDV == 2
-template <int kFirst = 0> __device__ __forceinline__ C64 hc_add_w(const C64 a, const C64 b)
+__device__ __forceinline__ C64 hc_add_w(const C64 a, const C64 b)
 {
     const bool lt = a.e < b.e;
     const uint64_t m = __builtin_amdgcn_ballot_w64(lt);
@@ -130,34 +107,6 @@ template <int kFirst = 0> __device__ __forceinline__ C64 hc_add_w(const C64 a, c
     lo.re = lt ? a.re : b.re, lo.im = lt ? a.im : b.im, lo.e = lt ? a.e : b.e;
     return add_hi_lo(hi, lo);
 }
-#else
-template <int kFirst = 0> __device__ __forceinline__ C64 hc_add_w(const C64 a, const C64 b)
-{
-    const int nd = b.e - a.e;
-    const uint64_t all = __builtin_amdgcn_ballot_w64(true);
-    if (kFirst == 1 && __builtin_amdgcn_ballot_w64(nd <= -kExpDiffIgnored) == all)
-        return a;
-    if (__builtin_amdgcn_ballot_w64((uint32_t)(nd + (kExpDiffIgnored - 1)) < (uint32_t)kExpDiffIgnored) == all) {
-        C64 r{a.re + __builtin_ldexp(b.re, nd), a.im + __builtin_ldexp(b.im, nd), a.e};
-        asm volatile("; hc_add_w: a + b 2^nd" : "+v"(r.re), "+v"(r.im));
-        return r;
-    }
-    if (__builtin_amdgcn_ballot_w64((uint32_t)(nd - 1) < (uint32_t)(kExpDiffIgnored - 1)) == all) {
-        C64 r{b.re + __builtin_ldexp(a.re, -nd), b.im + __builtin_ldexp(a.im, -nd), b.e};
-        asm volatile("; hc_add_w: a 2^-nd + b" : "+v"(r.re), "+v"(r.im));
-        return r;
-    }
-    if (kFirst != 1 && __builtin_amdgcn_ballot_w64(nd <= -kExpDiffIgnored) == all)
-        return a;
-    if (__builtin_amdgcn_ballot_w64(nd >= kExpDiffIgnored) == all)
-        return b;
-    const bool lt = nd > 0; // a.e < b.e
-    C64 hi, lo;
-    hi.re = lt ? b.re : a.re, hi.im = lt ? b.im : a.im, hi.e = lt ? b.e : a.e;
-    lo.re = lt ? a.re : b.re, lo.im = lt ? a.im : b.im, lo.e = lt ? a.e : b.e;
-    return add_hi_lo(hi, lo);
-}
-#endif
 
 // max(|a|, |b|) as ONE instruction (source modifiers; the C++ form first canonicalises each operand)
 __device__ __forceinline__ double max_abs64(double a, double b)
@@ -228,51 +177,13 @@ __device__ __forceinline__ C64 z_at_off(const FsZ64 *__restrict__ z, uint32_t by
     return C64{p->re, p->im, p->e};
 }
 
-// Lane -> pixel under a recorded order, XCD-aware.  The hardware hands workgroup b to XCD b mod 8, each XCD with an L2 of its own; in
-// plain launch order eight NEIGHBOURING workgroups -- whose pixels, adjacent in the count order, walk the same LA records -- land on
-// eight different L2s and every L2 sees the whole 15-MB table.  Here XCD x takes runs of FS_H64_XCD_RUN consecutive positions of the
-// order (virtual workgroup v = group * 8 R + x * R + r for the r-th workgroup the XCD receives in the group), so the workgroups that
-// share records share an L2, while every XCD still gets an even share of every stretch of the order.
-#ifndef FS_H64_XCD_RUN
-#define FS_H64_XCD_RUN 0
-#endif
-__device__ __forceinline__ void ordered_pixel_xcd(const FsFrame &f, const uint32_t *__restrict__ order, uint32_t &X, uint32_t &L)
-{
-    uint32_t b = blockIdx.y * gridDim.x + blockIdx.x;
-#if FS_H64_XCD_RUN > 0
-    constexpr uint32_t R = FS_H64_XCD_RUN, G = 8u * R;
-    const uint32_t nb = gridDim.x * gridDim.y;
-    if (b < nb / G * G) {
-        const uint32_t g = b / G, w = b % G;
-        b = g * G + (w % 8u) * R + w / 8u;
-    }
-#endif
-    const uint32_t slot = b * blockDim.x + threadIdx.x;
-    const uint32_t n = f.rounded_width * ((f.local_rows + 7u) & ~7u);
-    if (slot < n) {
-        const uint32_t id = order[slot];
-        L = id / f.rounded_width;
-        X = id - L * f.rounded_width;
-    } else {
-        X = 0xFFFFFFFFu, L = 0xFFFFFFFFu;
-    }
-}
-
 // Statistics words of the counting build (fs_read_step_count / tools): [8] steps whose adds ran the mixed (select) form, [9] wave
 // steps of the perturbation loop, [10] wave steps of the LA loop
-// FS_H64_WAVES (A/B builds): 8 = the register allocator is held to 64 registers (8 waves per SIMD; it spills three or four dwords),
-// 0 = left alone (67 registers, 7 waves)
-#ifndef FS_H64_WAVES
-#define FS_H64_WAVES 8
-#endif
-#if FS_H64_WAVES == 8
-#define FS_H64_OCCUPANCY __attribute__((amdgpu_waves_per_eu(8, 8)))
-#else
-#define FS_H64_OCCUPANCY
-#endif
+// amdgpu_waves_per_eu(8, 8): the register allocator is held to 64 registers (8 waves per SIMD; it spills three or four dwords) --
+// left alone it takes 67 registers, 7 waves
 // kAtInKernel: PerformAT is iterated here (at_perform; frames without the AT pass of their own) -- false: its results come from
 // A.at_res (fsk_at_pass64), and the instantiation carries neither the loop nor its registers
-template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_bounds__(256) FS_H64_OCCUPANCY k_lav2_hdr64(FsLav2ArgsT<double> A)
+template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_lav2_hdr64(FsLav2ArgsT<double> A)
 {
     using F = double;
     using LaRec = fs_la_hdr64_u32;
@@ -282,7 +193,7 @@ template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_boun
                   "la_step_asm.hpp reads the record by these offsets");
     uint32_t X, L;
     if (A.pixel_order)
-        ordered_pixel_xcd(A.frame, A.pixel_order, X, L);
+        ordered_pixel(A.frame, A.pixel_order, X, L);
     else if (A.tile_order) // (a first frame: tiles in the order of a sampled PerformAT count, kernels_tile_sample.hip)
         ordered_tile_pixel(A.tile_order, A.tiles_x, X, L);
     else
@@ -426,13 +337,8 @@ template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_boun
                     constexpr bool kUni = decltype(uni)::value;
 #define FS_LDC(P, F) C64{(P)->F.re, (P)->F.im, (P)->F.e}
 #define FS_LDR(P, F) R64{(P)->F.m, (P)->F.e}
-#if !FS_H64_LA_PIPE
-                    const uint32_t l = LAj->StepLength; // (A/B: the step waits for its own record's length first, as the literal kernel does)
-                    const C64 RJ = RJ_in;
-#else
                     const uint32_t l = kUni ? LAj->StepLength : lJ_in;
                     const C64 RJ = kUni ? FS_LDC(LAj, Ref) : RJ_in;
-#endif
                     const uint32_t next_stage = LAj->NextStageLAIndex;
                     const C64 ZCoeff = FS_LDC(LAj, ZCoeff), CCoeff = FS_LDC(LAj, CCoeff);
                     const R64 thr = FS_LDR(LAj, LAThreshold);
@@ -497,20 +403,16 @@ template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_boun
                 };
                 auto la_step = [&](const C64 &RJ, const uint32_t &lJ, C64 &RN, uint32_t &lN) __attribute__((always_inline)) -> bool {
                     const uint32_t off = base_off + j * (uint32_t)sizeof(LaRec);
-#if FS_H64_LA_SCALAR
                     const uint32_t uoff = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
                     if (__builtin_amdgcn_ballot_w64(off == uoff) == __builtin_amdgcn_ballot_w64(true)) {
                         typedef const __attribute__((address_space(4))) LaRec *CRec;
                         return la_body((CRec)((uintptr_t)A.las + uoff), std::true_type{}, RJ, lJ, RN, lN);
                     }
-#endif
                     return la_body(la_at_off(A.las, off), std::false_type{}, RJ, lJ, RN, lN);
                 };
-#if FS_H64_LA_ASM
-                // (frames in a recorded order only -- kAtInKernel is the first frame of a view, in the tile mapping, where a quarter of
-                // the LA steps have lanes at different records and every one of them would leave the statement for a compiled step and
-                // come back: 54.8 against 52.3 ms)
-                if constexpr ((!kStats || FS_H64_LA_ASM_DEBUG) && (!kAtInKernel || FS_H64_ASM_COLD)) {
+                // (the first frame of a view, in the tile mapping, too: 52.6 against 50.6 ms without the statements there, once they had
+                // their "alone" arms)
+                if constexpr (!kStats || FS_H64_LA_ASM_DEBUG) {
                     // the hand-written loop for the steps whose lanes stand at one record (la_step_asm.hpp); what it hands back --
                     // lanes at different records, a product that Reduce's fast form does not cover, a norm below 2^-1000 in the
                     // rebase test -- takes ONE compiled step (or its rebase test) and goes back in
@@ -568,9 +470,7 @@ template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_boun
                                 break;
                         }
                     }
-                } else
-#endif
-                {
+                } else {
                 C64 RefA = hc_zero<F>(), RefB = hc_zero<F>();
                 uint32_t lA = 0, lB = 0;
                 if (iterations < n_iterations) {
@@ -616,7 +516,7 @@ template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_boun
                 const C64 cur = hc_add_w(C64{ZH.re, ZH.im, ZH.e + 1}, dz); // (hc_mul2: x * 1.0 is x; e + 1 needs no clamp)
                 if (kStats)
                     w_mixB += mixed(arm_of(hc_mul(dz, cur), dc));
-                C64 q = hc_add_w<1>(hc_mul(dz, cur), dc);
+                C64 q = hc_add_w(hc_mul(dz, cur), dc);
                 hc_reduce_w(q);
                 dz = q;
                 if (kStats)
@@ -647,9 +547,8 @@ template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_boun
             C64 ZA = hc_zero<F>(), ZB = hc_zero<F>();
             if (iterations < n_iterations)
                 ZA = z_at_off(zr, zoff);
-#if FS_H64_PT_ASM
-            if constexpr ((!kStats || FS_H64_LA_ASM_DEBUG) && (!kAtInKernel || FS_H64_ASM_COLD)) {
-                // ---- the perturbation loop by hand (pt_step_asm.hpp) for the frames in a recorded order; what the statement hands
+            if constexpr (!kStats || FS_H64_LA_ASM_DEBUG) {
+                // ---- the perturbation loop by hand (pt_step_asm.hpp); what the statement hands
                 // back takes one compiled step (status 1, 3) or the compiled tests of the step it has computed (status 2)
                 const uint32_t z0re_lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)__builtin_bit_cast(uint64_t, zr[0].re));
                 const uint32_t z0re_hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)(__builtin_bit_cast(uint64_t, zr[0].re) >> 32));
@@ -721,7 +620,6 @@ template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_boun
                     run = __builtin_amdgcn_ballot_w64(running);
                 }
             } else
-#endif
             while (iterations < n_iterations) {
                 if (pt_step(ZA, ZB))
                     break;

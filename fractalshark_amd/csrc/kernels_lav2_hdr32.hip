@@ -263,8 +263,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
             FS_CYC(cyc_t0 = __builtin_readcyclecounter());
             FS_CYC(wall_t0 = wall_clock64());
             uint32_t sc_skip = 0, sc_penalty = 0; // (wave-uniform) back-off of the scaled-run attempts, see below
-            bool hot_next = false; // (wave-uniform) the step a scaled run has just failed on goes to a hot run first (FS_HOT_AFTER_FAIL)
-            bool fl_per_trip = false; // (wave-uniform) the next run attempt uses the per-trip floor verdicts (FS_FAST_LOOP_FD)
+            bool fl_per_trip = false; // (wave-uniform) the next run attempt uses the per-trip floor verdicts (FS_FAST_LOOP_FL)
             while (running) {
                 // ---- run of "scaled" quiet steps.  HDRFloat addition and multiplication are the correctly rounded binary32
                 // operations on the represented values (an exponent gap >= 120 drops an addend that is far below half an
@@ -286,8 +285,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                 // sits >= 2^80 below everything that result is made of.
                 // Anything else leaves the state of the last accepted step to the exponent-tracking loop below.
                 bool sc_stopped = false; // a scaled run ended on a step it could not take: that step goes to the careful path
-                if (kScaled && (sc_skip != 0u || hot_next)) {
-                    hot_next = false;
+                if (kScaled && sc_skip != 0u) {
                     // back-off: the last run attempts of this wave ended before their first step (a lane sits where dz is not
                     // small against the orbit -- near its escape, or between two near-zero orbit values): an attempt costs an
                     // entry, a trip and an exit, so a few careful steps are taken before the next one
@@ -644,7 +642,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                             // happens, and the block runs without them -- as the hand-scheduled body below (eight steps;
                             // it stops after four when the second block needs its bound tests).  Blocks that need them run
                             // the tested C++ form, four steps at a time.
-#if defined(FS_FD_LANE_BOUND) || defined(FS_VERIFY_BLOCK_BOUND) || defined(FS_VERIFY_FLOOR) || !FS_FL_EVERY
+#if defined(FS_VERIFY_BLOCK_BOUND) || defined(FS_VERIFY_FLOOR)
                             const int imdc = __float_as_int(fs_max_abs(dcs.x, dcs.y));
 #endif
                             // (FS_FAST_LOOP_FDU) the largest scale shift of the running lanes
@@ -663,15 +661,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
 #ifdef FS_VERIFY_BLOCK_BOUND
                                 // VERIFICATION BUILD (tools/block_bound_check.py): every block runs the tested form, and a block
                                 // whose block test passes while one of its four arrivals fails its own bound test is counted
-#ifdef FS_FD_LANE_BOUND
-                                const int vg_ = __float_as_int(mxS) > imdc ? __float_as_int(mxS) : imdc;
-                                const bool bt_pass = __builtin_amdgcn_ballot_w64(vg_ + Esh > pwi) == 0ull;
-#else
                                 // (the block test of FS_FAST_LOOP_FDU, restated)
                                 const long long bt_d = (long long)pwi - (long long)Esh_cap;
                                 const int bt_thr = sdc_bits > pwi ? -1 : (bt_d > 0x46800000ll ? 0x46800000 : (int)bt_d);
                                 const bool bt_pass = __builtin_amdgcn_ballot_w64(__float_as_int(mxS) > bt_thr) == 0ull;
-#endif
                                 if (kStats && bt_pass)
                                     c_blk_free++;
 #else
@@ -688,23 +681,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                     const uint32_t c_in = cs;
                                     uint32_t off = cs << 4;
                                     FS_CYC(cyc_t3 = __builtin_readcyclecounter());
-#if FS_FL_EVERY && !defined(FS_VERIFY_FLOOR)
+#ifndef FS_VERIFY_FLOOR
                                     if (!fl_per_trip) {
                                         {
-                                            // (the 16-step body of k_perturb_scalar, FS_FAST_LOOP_FD16, measures 2 % slower here --
+                                            // (round 4's 16-step body of k_perturb_scalar measures 2 % slower here --
                                             // 47.8 - 48.1 against 46.6 - 47.0 ms at N = 1, 6.79 against 6.70 ms on the slowest of
                                             // eight emulated ranks: with seven waves per SIMD the round trip it halves is hidden)
-#ifdef FS_FD_LANE_BOUND /* A/B: round 4's per-lane block test (five vector instructions per block) */
-                                            FS_FAST_LOOP_FD(FS_PF_NONE, FS_BT_DC_MAX, FS_BT_DC_ADD, FS_BT_H_CMP, FS_BT_H_OR);
-#else
                                             FS_FAST_LOOP_FDU(FS_PF_NONE);
-#endif
                                         }
                                         ebo = 0;
                                     } else
 #endif
                                     {
-#if !(defined(FS_FD_LANE_BOUND) || defined(FS_VERIFY_BLOCK_BOUND) || defined(FS_VERIFY_FLOOR) || !FS_FL_EVERY)
+#if !(defined(FS_VERIFY_BLOCK_BOUND) || defined(FS_VERIFY_FLOOR))
                                         // (max|dc| in the run's scale: only this loop's per-lane block test reads it)
                                         const int imdc = __float_as_int(fs_max_abs(dcs.x, dcs.y));
 #endif
@@ -896,7 +885,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                         }
                         if (failed) {
                             sc_stopped = true;
-                            hot_next = FS_HOT_AFTER_FAIL != 0;
                             if (c == 0u) {
                                 sc_penalty = sc_penalty < kScaledBackoffCap ? sc_penalty + 1u : kScaledBackoffCap;
                                 sc_skip = sc_penalty;
@@ -907,11 +895,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                         }
                     }
                     FS_CYC(cyc_run += __builtin_readcyclecounter() - cyc_t1);
-                    // The step the run failed on: a hot run takes it (per lane, exit tests exact, 32 vector instructions) where it
-                    // can -- 70 of a wave's 97 careful passes (130 vector instructions each, and a run entry behind every one)
-                    // found that nothing happens at such a step -- and the careful step below where it cannot.
-                    if (hot_next)
-                        continue;
                 }
                 // ---- run of "quiet" steps: when dz is at least 2^4 below the orbit value and the orbit value is < 8,
                 // neither exit test can fire and z itself is not needed:
@@ -1273,52 +1256,28 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
 // Host-callable launchers (called from renderer.cpp through kernels.h).
 static dim3 tile_grid(const FsFrame &f) { return dim3((f.width + 31) / 32, (f.local_rows + 7) / 8, 1); } // tile_pixel()
 
-static unsigned lds_pad()
-{
-    static const unsigned v = [] {
-        const char *e = getenv("FSMI355_LDS_PAD"); // occupancy-cap experiment: dynamic LDS bytes
-        const unsigned v = e ? (unsigned)atoi(e) : 0u;
-        return v <= 65536u ? v : 0u;
-    }();
-    return v;
-}
-
-static unsigned lav2_block_size()
-{
-    static const unsigned bs = [] {
-        const char *e = getenv("FSMI355_BLOCK"); // launch-shape experiment: 64, 128 or 256
-        const unsigned v = e ? (unsigned)atoi(e) : 256u;
-        return v == 64u || v == 128u ? v : 256u;
-    }();
-    return bs;
-}
-
 uint32_t fsk_lav2_hdr32_slots(const FsFrame &f)
 {
-    if (lav2_block_size() != 256u)
-        return 0;
     return ((f.width + 31u) / 32u) * 4u * ((f.local_rows + 7u) / 8u);
 }
 
 void fsk_lav2_hdr32(const FsLav2Args32 &A, int mode, bool stats, int variant, hipStream_t s)
 {
-    const unsigned pad = lds_pad();
-    const unsigned bs = lav2_block_size();
     // A/B flag of fs_set_kernel_variant: the wave-uniform scaled runs' orbit entries through LDS (see the kernel)
     const bool lds_orbit = (variant & FS_VARIANT_FLAG_LDS_ORBIT) != 0;
     variant &= FS_VARIANT_BASE_MASK;
-    const dim3 b(bs), g((A.frame.width + bs / 8 - 1) / (bs / 8), (A.frame.local_rows + 7) / 8, 1);
+    const dim3 b(256), g = tile_grid(A.frame);
 #define FS_LAUNCH_FAST(M, SC, LDS)                                                                                  \
     if (stats) {                                                                                                    \
         if (gs)                                                                                                     \
-            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, true, SC, LDS, true>), g, b, pad, s, A);                       \
+            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, true, SC, LDS, true>), g, b, 0, s, A);                         \
         else                                                                                                        \
-            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, true, SC, LDS, false>), g, b, pad, s, A);                      \
+            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, true, SC, LDS, false>), g, b, 0, s, A);                        \
     } else {                                                                                                        \
         if (gs)                                                                                                     \
-            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, false, SC, LDS, true>), g, b, pad, s, A);                      \
+            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, false, SC, LDS, true>), g, b, 0, s, A);                        \
         else                                                                                                        \
-            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, false, SC, LDS, false>), g, b, pad, s, A);                     \
+            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, false, SC, LDS, false>), g, b, 0, s, A);                       \
     }
 #define FS_LAUNCH(M)                                                                                                \
     do {                                                                                                            \

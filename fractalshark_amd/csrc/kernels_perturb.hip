@@ -763,7 +763,7 @@ __global__ void __launch_bounds__(256) k_perturb_scalar(FsBlaArgsT<F> A)
                     const uint32_t ref_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)RefIteration);
                     if (__builtin_amdgcn_ballot_w64(RefIteration != ref_u) == 0ull) {
                         // Entries through the scalar cache (all lanes read the same ones): the hand-scheduled untested loop
-                        // of k_lav2_hdr32_fast (FS_FAST_LOOP_FD / _FL; here with the next body's cache lines requested a body ahead:
+                        // of k_lav2_hdr32_fast (FS_FAST_LOOP_FDU / _FL; here with the next body's cache lines requested a body ahead:
                         // a wave that is alone on its SIMD -- the interior pixels' 4.7 M-step chains that decide C2's frame
                         // time -- pays per instruction issued and for every L2 round trip it waits out), and four-step
                         // blocks with their bound tests where the block test fails.  A failed trip ends the run at its start
@@ -802,15 +802,11 @@ __global__ void __launch_bounds__(256) k_perturb_scalar(FsBlaArgsT<F> A)
                                 int va_;
                                 uint32_t off = cs << 4;
                                 const uint32_t c_in = cs;
-#if FS_FL_EVERY && !defined(FS_VERIFY_FLOOR)
+#ifndef FS_VERIFY_FLOOR
                                 if (!fl_per_trip) {
                                     {
                                         FS_PO(po_t2 = __builtin_readcyclecounter(); po_n_asm++);
-#ifdef FS_FD16_SERIAL /* A/B: round 4's body -- one wait right behind the request, the next body's lines warmed */
-                                        FS_FAST_LOOP_FD16(FS_PF16_NEXT_BODY);
-#else
                                         FS_FAST_LOOP_FD16P;
-#endif
                                         FS_PO(po_asm += __builtin_readcyclecounter() - po_t2);
                                     }
                                     ebo = 0;
@@ -827,12 +823,6 @@ __global__ void __launch_bounds__(256) k_perturb_scalar(FsBlaArgsT<F> A)
                                 zS = (f2){__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(zS.x))),
                                           __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(zS.y)))};
                                 if (st == 3) {
-#ifdef FS_FD16_SERIAL
-                                    // (deferred verdict) a state of this invocation fell below the floor: nothing of the run
-                                    // has been committed -- the same run again with the per-trip verdicts
-                                    fl_redo = true;
-                                    break;
-#else
                                     // (deferred verdict, per body) a state of the last body fell below the floor: the statement
                                     // is back at its checkpoint -- the steps up to there are certified and committed, the next
                                     // run starts there with the per-trip verdicts
@@ -847,9 +837,7 @@ __global__ void __launch_bounds__(256) k_perturb_scalar(FsBlaArgsT<F> A)
                                     if (kStats)
                                         c_end[3]++;
                                     break;
-#endif
                                 }
-#ifndef FS_FD16_SERIAL
                                 if (st == 4) {
                                     // a block test inside the last body failed: the statement is back at the body's checkpoint.  Its
                                     // first block passed its test, so it runs once more -- through the tested form below, which is
@@ -865,9 +853,7 @@ __global__ void __launch_bounds__(256) k_perturb_scalar(FsBlaArgsT<F> A)
                                     st = 0;
                                     if (kStats)
                                         c_end[4]++;
-                                } else
-#endif
-                                {
+                                } else {
                                     cs = (uint32_t)__builtin_amdgcn_readfirstlane((int)off) >> 4;
                                     if (kStats)
                                         c_free_steps += cs - c_in;
@@ -1451,8 +1437,6 @@ template <class K> static dim3 persistent_grid(K kernel, const FsFrame &f)
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1)
         per_cu = 2;
-    if (const char *e = getenv("FSMI355_PERSIST_PER_CU")) // launch-shape experiment
-        per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
     const uint64_t tiles = (uint64_t)((f.width + 7u) >> 3) * ((f.local_rows + 7u) >> 3);
     uint64_t blocks = (uint64_t)cus * (uint64_t)per_cu;
     const uint64_t need = (tiles + 3u) / 4u;

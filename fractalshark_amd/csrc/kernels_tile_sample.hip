@@ -19,10 +19,9 @@
 
 namespace {
 
-#ifndef FS_TILE_SAMPLE_CAP
-#define FS_TILE_SAMPLE_CAP 512u /* measured on C4 (one box, first frame, HDRFloat<double> / <CudaDblflt>): uncut 45.2 / 208.3 ms, 8192: 44.0 / 207.5, 2048: 43.3 / 206.4, 1024: 43.1 / 208.1, 512: 43.0 / 205.2 */
-#endif
-constexpr uint32_t kSampleCap = FS_TILE_SAMPLE_CAP;
+// measured on C4 (one box, first frame, HDRFloat<double> / <CudaDblflt>): uncut 45.2 / 208.3 ms, 8192: 44.0 / 207.5, 2048: 43.3 / 206.4,
+// 1024: 43.1 / 208.1, 512: 43.0 / 205.2
+constexpr uint32_t kSampleCap = 512u;
 
 __global__ void __launch_bounds__(256) k_at_tile_sample64(FsTileSampleArgs A)
 {

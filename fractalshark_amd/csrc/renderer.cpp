@@ -2311,7 +2311,7 @@ static bool pix_buffers(fs_renderer *r, uint32_t n)
 }
 
 static void pix_order_after(fs_renderer *r, const FsFrame &f, const fs_renderer::PixKey &key, bool frame_was_ordered,
-                            const uint32_t *cost = nullptr, int key_bits = 32)
+                            const uint32_t *cost = nullptr)
 {
     if (frame_was_ordered || !pix_order_wanted(r, f))
         return; // (an ordered frame's buffer equals the one the order was made from: nothing new to learn)
@@ -2321,7 +2321,7 @@ static void pix_order_after(fs_renderer *r, const FsFrame &f, const fs_renderer:
         return;
     // sorted by the cost the frame recorded (round 5) -- or, without a record, by the counts as before
     if (fsk_pixel_order_build(cost ? cost : (const uint32_t *)r->iters(), n, r->pix_work, r->pix_order, r->pix_temp, r->pix_temp_bytes,
-                              r->compute, key_bits) != hipSuccess) {
+                              r->compute) != hipSuccess) {
         (void)hipGetLastError();
         return;
     }
@@ -2366,7 +2366,7 @@ static const uint32_t *cold_tile_order(fs_renderer *r, FsTileSampleArgs &S)
     }
     S.cost = r->cold_cost;
     fsk_at_tile_sample64(S, r->compute);
-    if (fsk_pixel_order_build(r->cold_cost, S.n_slots, r->cold_work, r->cold_order, r->cold_temp, r->cold_temp_bytes, r->compute, 32) !=
+    if (fsk_pixel_order_build(r->cold_cost, S.n_slots, r->cold_work, r->cold_order, r->cold_temp, r->cold_temp_bytes, r->compute) !=
         hipSuccess) {
         (void)hipGetLastError();
         return nullptr;
@@ -2588,7 +2588,7 @@ uint32_t fs_render_lav2(fs_renderer *r, int type_tag, int mode, int parity, cons
         const uint32_t n_tiles = tiles_x * tiles_y;
         const uint32_t n_slots = fsk_lav2_hdr32_slots(A.frame);
         const bool tuned = (r->variant & FS_VARIANT_BASE_MASK) != FS_VARIANT_LITERAL;
-        const bool record = tuned && n_slots != 0u && n_tiles >= kLav2OrderMinTiles &&
+        const bool record = tuned && n_tiles >= kLav2OrderMinTiles &&
                             (r->variant & FS_VARIANT_FLAG_NATURAL_ORDER) == 0;
         r->last_frame_ordered = false;
         if (record) {
@@ -2634,16 +2634,11 @@ uint32_t fs_render_lav2(fs_renderer *r, int type_tag, int mode, int parity, cons
         A.pixel_order = pix_order_for(r, A.frame, pk);
         // PerformAT in a pass of its own, in the order of the AT iterations every pixel needs by itself (recorded by the view's
         // first frame): the AT loop reads no memory, so its waves can be made of pixels from anywhere -- equal work per wave --
-        // while the frame's kernel keeps the order that keeps neighbours together (below).
-        static const bool at_split_off = [] { const char *e = getenv("FSMI355_AT_IN_KERNEL"); return e && e[0] == '1'; }();
-        // (A/B, off: FSMI355_AT_SPLIT_COLD=1 runs the pass of its own in the first frame of a view too -- natural order, nothing
-        // recorded.  Measured in round 6: AT pass 13.5 ms + the frame's kernel in the tile mapping 48.7 = 62.3 ms against 55.9 ms for the
-        // ONE kernel that iterates PerformAT itself: without an order the pass's waves wait for their slowest pixel just as the
-        // kernel's do, and the frame's kernel gains nothing from lanes that arrive together)
-        static const bool at_split_cold = [] { const char *e = getenv("FSMI355_AT_SPLIT_COLD"); return e && e[0] == '1'; }();
+        // while the frame's kernel keeps the order that keeps neighbours together (below).  A view's first frame has no such pass:
+        // without an order its waves wait for their slowest pixel just as the kernel's do.
         const bool second = A.pixel_order == nullptr && pix_second_sighting(r, A.frame, pk);
-        bool at_split = !at_split_off && mode != FS_LAV2_PO && A.use_at && A.la_valid && pix_order_wanted(r, A.frame) &&
-                        (at_split_cold || A.pixel_order != nullptr || second);
+        bool at_split = mode != FS_LAV2_PO && A.use_at && A.la_valid && pix_order_wanted(r, A.frame) &&
+                        (A.pixel_order != nullptr || second);
         if (at_split) {
             const size_t n = (size_t)A.frame.rounded_width * ((A.frame.local_rows + 7u) & ~7u);
             if (r->at_cap < n) {
@@ -2673,23 +2668,6 @@ uint32_t fs_render_lav2(fs_renderer *r, int type_tag, int mode, int parity, cons
         // -- other row bands, a table without AT in between -- without it)
         const bool at_warm = at_split && r->at_order_valid && r->at_key == pk;
         const bool at_record = at_split && !at_warm && (second || A.pixel_order != nullptr);
-        // (A/B, off: FSMI355_C4_INFRAME_ORDER=1 sorts the first frame of a view by its own AT iteration counts -- measured in round 6:
-        // the frame's kernel then takes 54 ms against 49.6 in the tile mapping and 35 in the order of the previous frame's COUNTS;
-        // what the count order knows and the AT count does not is how long a pixel's LA and perturbation phases are)
-        static const bool inframe_on = [] { const char *e = getenv("FSMI355_C4_INFRAME_ORDER"); return e && e[0] == '1'; }();
-        const bool inframe = inframe_on && at_split && A.pixel_order == nullptr;
-        bool inframe_done = false;
-        // (sorted by COUNT, not by a recorded cost as the 2x32 frames are: this kernel's steps are cheap enough for the loads of
-        // a wave whose lanes are scattered over the frame to cost more than the idle lanes they save -- 81 ms with the cost as
-        // the key, 68 with its binades, 53 with the counts, which keep the pixels inside the set side by side: DESIGN.md 7)
-        // The order's key (A/B, FSMI355_C4_ORDER_KEY=cost): the previous frame's COUNTS (default), or what the pixels cost the frame's
-        // kernel in that frame -- LA steps + perturbation steps, recorded by the second frame of the view
-        static const bool key_cost = [] { const char *e = getenv("FSMI355_C4_ORDER_KEY"); return e && e[0] == 'c' && e[1] == 'o' && e[2] == 's'; }();
-        uint32_t *cost_key = nullptr;
-        if (key_cost && second && at_split) {
-            cost_key = pix_cost_for(r, A.frame, false);
-            A.pixel_cost = cost_key;
-        }
         {
             TimedLaunch t(r);
             if (at_split) {
@@ -2706,31 +2684,9 @@ uint32_t fs_render_lav2(fs_renderer *r, int type_tag, int mode, int parity, cons
                     }
                     r->at_order_valid = false;
                 }
-                // In-frame order (round 6): a frame without an order makes its own from the AT pass it has just run -- the AT
-                // iteration count is the leading part of a pixel's final count (count = AT iterations x step length + LA steps +
-                // perturbation steps), so sorting by it groups the pixels as the previous frame's counts would, with nothing
-                // needed from an earlier frame.  key_bits: ATMaxIt bounds the key.
-                uint32_t *key = inframe && pix_buffers(r, n) ? pix_cost_for(r, A.frame, false) : nullptr;
-                P.pixel_cost = key;
                 fsk_at_pass64(P, r->compute);
                 t.mid();
                 A.at_res = r->at_res;
-                if (key) {
-                    uint64_t at_max = A.at.StepLength ? n_iterations / A.at.StepLength : 0;
-                    int bits = 1;
-                    while (bits < 32 && (at_max >> bits) != 0)
-                        bits++;
-                    if (fsk_pixel_order_build(key, n, r->pix_work, r->pix_order, r->pix_temp, r->pix_temp_bytes, r->compute,
-                                              bits) == hipSuccess) {
-                        r->pix_key = pk;
-                        r->pix_valid = true;
-                        A.pixel_order = r->pix_order;
-                        inframe_done = true;
-                        r->last_frame_ordered = true;
-                    } else {
-                        (void)hipGetLastError();
-                    }
-                }
             }
             if (A.pixel_order == nullptr && !second && !at_split && mode != FS_LAV2_PO && A.use_at && A.la_valid) {
                 // a view's first frame: tiles in the order of a sampled PerformAT count (kernels_tile_sample.hip)
@@ -2747,18 +2703,19 @@ uint32_t fs_render_lav2(fs_renderer *r, int type_tag, int mode, int parity, cons
                 A.tiles_x = S.tiles_x;
             }
             // the production kernel (kernels_hdr64.hip); FS_VARIANT_LITERAL keeps the operation-by-operation one for A/B
-            // (FSMI355_HDR64_LITERAL=1: the literal kernel with the same orders and the same AT pass -- the A/B of the kernel alone)
-            static const bool lit_env = [] { const char *e = getenv("FSMI355_HDR64_LITERAL"); return e && e[0] == '1'; }();
             // (k_lav2_hdr64 addresses its records with 32-bit byte offsets: an orbit or a table of 4 GB and more stays with the literal kernel)
             const bool small = (uint64_t)A.orbit_count * sizeof(FsZ64) < 0xFFFFFF00ull &&
                                (uint64_t)r->n_las * sizeof(fs_la_hdr64_u32) < 0xFFFFFF00ull;
-            if (lit_env || !small || (r->variant & FS_VARIANT_BASE_MASK) == FS_VARIANT_LITERAL)
+            if (!small || (r->variant & FS_VARIANT_BASE_MASK) == FS_VARIANT_LITERAL)
                 fsk_lav2_hdr64(A, kmode, r->stats_on, r->compute);
             else
                 fsk_lav2_hdr64_fast(A, kmode, r->stats_on, r->compute);
         }
-        if (second && !inframe_done)
-            pix_order_after(r, A.frame, pk, false, cost_key, cost_key ? 16 : 32);
+        // (sorted by COUNT, not by a recorded cost as the 2x32 frames are: this kernel's steps are cheap enough for the loads of
+        // a wave whose lanes are scattered over the frame to cost more than the idle lanes they save -- 81 ms with the cost as
+        // the key, 68 with its binades, 53 with the counts, which keep the pixels inside the set side by side: DESIGN.md 7)
+        if (second)
+            pix_order_after(r, A.frame, pk, false);
         const uint32_t n_buf = A.frame.rounded_width * ((A.frame.local_rows + 7u) & ~7u);
         if (at_split && at_record && r->pix_valid && r->pix_work && r->pix_temp && r->pix_cap >= n_buf) {
             // the AT pass's own order, from the costs it has just recorded (the sort's work memory is the pixel order's)

@@ -133,8 +133,8 @@ __device__ __forceinline__ bool scaled_startable(const float4 e)
 // The form above tests every SECOND state and therefore needs a test relative to the state's size (part ratio 2^-40 and a
 // 60-binade window: six vector instructions per two states instead of three).  Exact zero parts fail the floor (pixels on
 // the axes go to the exponent-tracking loop, as before).
-// Two forms, selected at build time (FS_FL_EVERY).  1 (the default) = every state against the floor 2^-56, as derived above:
-// each state of a run is certified.  0 = every SECOND state (a trip's second step) against the higher floor 2^-44 -- one
+// Two forms (FS_FL_EVERY).  1 (the product) = every state against the floor 2^-56, as derived above: each state of a run is
+// certified.  0 (only the FS_VERIFY_FLOOR build) = every SECOND state (a trip's second step) against the higher floor 2^-44 -- one
 // v_min and one compare per two states instead of two and one: 49.0 instead of 51.5 ms on C3, the same frames on every
 // test -- but its argument has a gap and it is NOT the default: the untested first state `a` of a trip can differ from the
 // reference's in a part that is itself below 2^-60 (by less than 2^-86), and although that difference is 2^25 ulps below
@@ -142,30 +142,16 @@ __device__ __forceinline__ bool scaled_startable(const float4 e)
 // b's intermediate sums happens to land within that distance of a rounding boundary (probability of the order of 2^-15
 // per such trip).  tools/floor_check.py (FS_VERIFY_FLOOR build) counts the trips whose first state has a part below 2^-56
 // while the second passes: about 1 in 10^4 wave-trips on C3's view -- rare, not absent.
-#ifndef FS_FL_EVERY
 #if defined(FS_VERIFY_FLOOR)
 #define FS_FL_EVERY 0
 #else
 #define FS_FL_EVERY 1
 #endif
-#endif
-#if defined(FS_VERIFY_FLOOR) && FS_FL_EVERY
-#error "FS_VERIFY_FLOOR measures the every-second-state form"
-#endif
-#ifndef FS_FL_SHIFT
-#define FS_FL_SHIFT 24 /* measured on C3 (every-state form): 20 / 24 / 28 -> 51.5 / 51.7 / 51.5 ms; second-state form 10 .. 28 in DESIGN.md */
-#endif
-constexpr int kScaleShift = FS_FL_SHIFT;
-#ifndef FS_FL_FLOOR_EXP
-#if FS_FL_EVERY
-#define FS_FL_FLOOR_EXP 56
-#else
-#define FS_FL_FLOOR_EXP 44
-#endif
-#endif
-static_assert(FS_FL_EVERY ? FS_FL_FLOOR_EXP <= 56 : FS_FL_FLOOR_EXP <= 48, "the floor's margins (see above)");
-#define FS_FL_FLOOR __builtin_amdgcn_ldexpf(1.0f, -FS_FL_FLOOR_EXP)
-constexpr int kFloorBits = (127 - FS_FL_FLOOR_EXP) << 23;
+// scale of a run: measured on C3 (every-state form): 20 / 24 / 28 -> 51.5 / 51.7 / 51.5 ms; second-state form 10 .. 28 in DESIGN.md
+constexpr int kScaleShift = 24;
+constexpr int kFloorExp = FS_FL_EVERY ? 56 : 44; // the floor 2^-kFloorExp (its margins: see above)
+#define FS_FL_FLOOR __builtin_amdgcn_ldexpf(1.0f, -kFloorExp)
+constexpr int kFloorBits = (127 - kFloorExp) << 23;
 #define FS_FL_HIGH 0x1p14f   /* max|w| where a 4-step block starts */
 #define FS_FL_HIGH_TRIP 0x1p24f /* the per-lane paths test H once per two-step trip: 25.2 * 2^24 + 2^7 < 2^29 */
 #if defined(FS_VERIFY_FLOOR)
@@ -174,12 +160,9 @@ constexpr int kFloorBits = (127 - FS_FL_FLOOR_EXP) << 23;
 // sticky lane mask %[xa]; the caller counts the loop invocations that leave it non-zero.
 #define FS_FL_N1(A, B) "v_min_f32_e64 v61, |" A "|, |" B "|\n\tv_cmp_gt_f32_e32 vcc, %[flr56], v61\n\ts_or_b64 %[xa], %[xa], vcc\n\t"
 #define FS_FL_N2(A, B) "v_min_f32_e64 v61, |" A "|, |" B "|\n\t"
-#elif FS_FL_EVERY
+#else
 #define FS_FL_N1(A, B) "v_min_f32_e64 v61, |" A "|, |" B "|\n\t"
 #define FS_FL_N2(A, B) "v_min3_f32 v61, |" A "|, |" B "|, v61\n\t"
-#else
-#define FS_FL_N1(A, B) ""
-#define FS_FL_N2(A, B) "v_min_f32_e64 v61, |" A "|, |" B "|\n\t"
 #endif
 #define FS_FL_C "v_cmp_gt_f32_e32 vcc, %[flr], v61\n\t"   /* floor > the smallest part tested */
 #define FS_FL_H "v_cmp_lt_f32_e32 vcc, 0x46800000, v60\n\t"   /* 2^14 < max|w| at a block's first state */
@@ -189,10 +172,8 @@ constexpr int kFloorBits = (127 - FS_FL_FLOOR_EXP) << 23;
 #define FS_STEP_FLOOR_FIRST(NW_, V)                                                                                 \
     if (kStats && __builtin_amdgcn_ballot_w64(!(fs_min_abs(NW_.x, NW_.y) >= 0x1p-56f)) != 0ull) \
         c_blk_violation++;
-#elif FS_FL_EVERY
-#define FS_STEP_FLOOR_FIRST(NW_, V) FS_STEP_FLOOR(NW_, V)
 #else
-#define FS_STEP_FLOOR_FIRST(NW_, V)
+#define FS_STEP_FLOOR_FIRST(NW_, V) FS_STEP_FLOOR(NW_, V)
 #endif
 // The untested body, floor form (round 3's form of this statement tested every second state against a ratio and a window:
 // six vector instructions per two states).  Registers, rotation of the four state pairs and exits as described above; a
@@ -282,66 +263,13 @@ constexpr int kFloorBits = (127 - FS_FL_FLOOR_EXP) << 23;
 // every-state rigour at the price of the every-second-state form.  H and the block bounds are tested where a block starts,
 // as in FS_FAST_LOOP_FL (they guard the steps that follow, so they cannot be deferred).
 #define FS_FL_ACC(A, B) "v_min3_f32 v61, |" A "|, |" B "|, v61\n\t"
-// The block test's pieces are macro parameters (BMAX / BADD / HCMP / HOR): a second and third copy of the loop without the dc half
-// (max|dc| 2^E within the smallest block bound of the whole orbit) and without H (E >= -26 in every lane) were written and would
-// save about 1 ms on C3, but more than one copy of this statement per kernel makes the backend fail ("illegal VGPR to SGPR copy":
-// the statement's scalar in/out operands meet in phis it treats as divergent) -- one copy, the general one, is instantiated.
 #define FS_BT_DC_MAX "v_max_i32_e32 v62, v60, %[imdc]\n\t"
 #define FS_BT_DC_ADD "v_add_u32_e32 v62, v62, %[esh]\n\t"
-#define FS_BT_NODC_MAX ""
-#define FS_BT_NODC_ADD "v_add_u32_e32 v62, v60, %[esh]\n\t"
-#define FS_BT_H_CMP FS_FL_H
-#define FS_BT_H_OR "s_or_b64 %[m], %[m], vcc\n\t"
-#define FS_BT_NOH_CMP ""
-#define FS_BT_NOH_OR "s_cmp_lg_u64 %[m], 0\n\t"
-#define FS_FAST_LOOP_FD(PF, BMAX, BADD, HCMP, HOR)                                                                                          \
-    asm volatile(                                                                                                   \
-        "v_mov_b32_e32 v61, 0x7f800000\n"                                                                           \
-        ".Lfd_loop_%=:\n\t" /* eight steps left?  the first block's tests: max(max|w|, max|dc|) against .w (s67), H */ \
-        BMAX "s_cmp_gt_u32 %[off], %[lim8]\n\t" BADD                                                                \
-        "s_cbranch_scc1 .Lfd_out_%=\n\t"                                                                            \
-        "v_cmp_lt_i32_e64 %[m], s67, v62\n\t" HCMP HOR                                                              \
-        "s_cbranch_scc1 .Lfd_out_%=\n\t" /* steps 1 .. 4 */                                                         \
-        FS_PK_F(FS_R0, "s[64:65]")                                                                                  \
-        "s_load_dwordx16 s[36:51], s[68:69], %[off]\n\t"                                                            \
-        "s_load_dwordx16 s[52:67], s[68:69], %[off] offset:0x40\n\t"                                                \
-        FS_PK_MA(FS_R0) FS_PK_MB(FS_R0) FS_PK_P FS_PK_A(FS_R1)                                                      \
-        "s_waitcnt lgkmcnt(0)\n\t" PF                                                                               \
-        FS_PK_F(FS_R1, "s[36:37]") FS_FL_ACC("v50", "v51") FS_PK_MA(FS_R1) FS_PK_MB(FS_R1) FS_PK_P FS_PK_A(FS_R2)   \
-        FS_PK_F(FS_R2, "s[40:41]") FS_FL_ACC("v52", "v53") FS_PK_MA(FS_R2) FS_PK_MB(FS_R2) FS_PK_P FS_PK_A(FS_R3)   \
-        FS_PK_F(FS_R3, "s[44:45]") FS_FL_ACC("v54", "v55") FS_PK_MA(FS_R3) FS_PK_MB(FS_R3) FS_PK_P FS_PK_A(FS_R0)   \
-        /* step 5 + w4's floor part and max; the second block's tests in step 6, before anything of block 2 is counted */ \
-        FS_PK_F(FS_R0, "s[48:49]") FS_FL_ACC("v48", "v49") FS_PK_MA(FS_R0) FS_T_X("v48", "v49") FS_PK_MB(FS_R0)     \
-        FS_PK_P BMAX FS_PK_A(FS_R1) BADD                                                                            \
-        FS_PK_F(FS_R1, "s[52:53]") "v_cmp_lt_i32_e64 %[m], s51, v62\n\t" HCMP FS_PK_MA(FS_R1)                       \
-        HOR FS_PK_MB(FS_R1) FS_PK_P "s_cbranch_scc1 .Lfd_blk_%=\n\t" FS_PK_A(FS_R2)                                 \
-        FS_PK_F(FS_R2, "s[56:57]") FS_FL_ACC("v50", "v51") FS_PK_MA(FS_R2) FS_FL_ACC("v52", "v53") FS_PK_MB(FS_R2)  \
-        FS_PK_P FS_PK_A(FS_R3)                                                                                      \
-        FS_PK_F(FS_R3, "s[60:61]") FS_FL_ACC("v54", "v55") FS_PK_MA(FS_R3) FS_PK_MB(FS_R3) FS_PK_P FS_PK_A(FS_R0)   \
-        "s_add_u32 %[off], %[off], 0x80\n\t"                                                                        \
-        FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") "s_branch .Lfd_loop_%=\n"                                      \
-        ".Lfd_blk_%=:\n\t" /* the second block needs its bound tests (or H): the state is w4 in v[48:49] */         \
-        "s_mov_b64 s[64:65], s[48:49]\n\t"                                                                          \
-        "s_mov_b32 s67, s51\n\t"                                                                                    \
-        "s_add_u32 %[off], %[off], 0x40\n"                                                                          \
-        ".Lfd_out_%=:\n\t" /* the verdict over every state of this invocation */                                    \
-        "s_mov_b32 %[st], 0\n\t" FS_FL_C                                                                            \
-        "s_cbranch_vccz .Lfd_end_%=\n\t"                                                                            \
-        "s_mov_b32 %[st], 3\n"                                                                                      \
-        ".Lfd_end_%=:\n\t"                                                                                          \
-        "s_waitcnt lgkmcnt(0)"                                                                                      \
-        : "+{v[48:49]}"(wv), "={v[50:51]}"(r1), "={v[52:53]}"(r2), "={v[54:55]}"(r3), "={v[56:57]}"(ts_),           \
-          "={v[58:59]}"(ta_), "+{v60}"(mxS), "={v61}"(tn_), "={v62}"(tl_), [m] "=&s"(msk_), [st] "=&s"(st),         \
-          "+{s67}"(pwi), "+{s[64:65]}"(zS), [off] "+s"(off), [pf] "=&s"(pf_), [pg] "=&s"(pg_), [ph] "=&s"(ph_)      \
-        : [se] "v"(sE2), [dc] "v"(dcs), [esh] "v"(Esh), [imdc] "v"(imdc), [lim8] "s"(lim8), "{s[68:69]}"(zpb),      \
-          [flr] "s"(kFloorBits)                                                                                     \
-        : "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50",  \
-          "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s66", "vcc",  \
-          "scc")
 
-// The same loop with the block test on WAVE-UNIFORM thresholds (round 5): the kernel issues one vector instruction per SIMD
-// every four cycles and nothing else, and the block test was five of them per four steps (max|w|, max with max|dc|, + the lane's
-// scale, the compare, H's compare).  Both sides of it that are not the state are made scalar, each in the safe direction:
+// The untested body with the deferred verdict and the block test on WAVE-UNIFORM thresholds (round 5): the kernel issues one
+// vector instruction per SIMD every four cycles and nothing else, and round 4's per-lane block test was five of them per four
+// steps (max|w|, max with max|dc|, + the lane's scale, the compare, H's compare).  Both sides of it that are not the state are
+// made scalar, each in the safe direction:
 //   max|dc| 2^E is the pixel's true max|dc|, a constant: its largest value over the wave (`sdc`, made once per tile) is compared
 //     with the block bound on the scalar unit;
 //   bits(max|w|) + Esh <= bound holds in every lane when bits(max|w|) <= bound - (the LARGEST Esh of the running lanes: `eshm`,
@@ -413,80 +341,13 @@ constexpr int kFloorBits = (127 - FS_FL_FLOOR_EXP) << 23;
 // Registers: entries E0 .. E15 in s[36:67] (E15 = s[66:67] is the entry the state is at when the body ends: the next
 // body's first step reads it BEFORE the loads overwrite it), the four block bounds in s[72:75] (s75 = the bound of the
 // state's entry at the loop's top), bases s[68:69] (zs2) and s[70:71] (zqb), `off` = 16 bytes per step as everywhere.
-// State pairs, temporaries, the floor accumulator and the statuses as in FS_FAST_LOOP_FD: 0 = stopped in front of a block
+// State pairs, temporaries, the floor accumulator and the statuses as in FS_FAST_LOOP_FDU: 0 = stopped in front of a block
 // that needs its tests / fewer than 16 steps left, 3 = a state below the floor (the caller repeats the run attempt with
 // FS_FAST_LOOP_FL).  Blocks 2 .. 4 are tested in the second step of the block, before anything of the block is counted.
-#define FS_FD16_PAIR(EA, EB_, BW, LBL)                                                                              \
-    FS_PK_F(FS_R0, EA) FS_FL_ACC("v48", "v49") FS_PK_MA(FS_R0) FS_T_X("v48", "v49") FS_PK_MB(FS_R0)                 \
-    FS_PK_P FS_BT_DC_MAX FS_PK_A(FS_R1) FS_BT_DC_ADD                                                                \
-    FS_PK_F(FS_R1, EB_) "v_cmp_lt_i32_e64 %[m], " BW ", v62\n\t" FS_BT_H_CMP FS_PK_MA(FS_R1)                         \
-    FS_BT_H_OR FS_PK_MB(FS_R1) FS_PK_P "s_cbranch_scc1 " LBL "\n\t" FS_PK_A(FS_R2)
 #define FS_FD16_TAIL(EC, ED)                                                                                        \
     FS_PK_F(FS_R2, EC) FS_FL_ACC("v50", "v51") FS_PK_MA(FS_R2) FS_FL_ACC("v52", "v53") FS_PK_MB(FS_R2)              \
     FS_PK_P FS_PK_A(FS_R3)                                                                                          \
     FS_PK_F(FS_R3, ED) FS_FL_ACC("v54", "v55") FS_PK_MA(FS_R3) FS_PK_MB(FS_R3) FS_PK_P FS_PK_A(FS_R0)
-#define FS_PF16_NONE ""
-#define FS_PF16_NEXT_BODY                                                                                           \
-    "s_load_dword %[pf], s[68:69], %[oc] offset:0x80\n\t"                                                           \
-    "s_load_dword %[pg], s[68:69], %[oc] offset:0xc0\n\t"                                                           \
-    "s_load_dword %[ph], s[68:69], %[oc] offset:0xfc\n\t"                                                           \
-    "s_load_dword %[pi], s[70:71], %[off] offset:0x100\n\t"                                                         \
-    "s_load_dword %[pj], s[70:71], %[off] offset:0x10c\n\t"
-#define FS_FAST_LOOP_FD16(PF)                                                                                       \
-    asm volatile(                                                                                                   \
-        "v_mov_b32_e32 v61, 0x7f800000\n"                                                                           \
-        ".Lfe_loop_%=:\n\t" /* sixteen steps left?  the first block's tests: max(max|w|, max|dc|) against s75, H */  \
-        FS_BT_DC_MAX "s_cmp_gt_u32 %[off], %[lim16]\n\t" FS_BT_DC_ADD                                               \
-        "s_cbranch_scc1 .Lfe_out_%=\n\t"                                                                            \
-        "v_cmp_lt_i32_e64 %[m], s75, v62\n\t" FS_BT_H_CMP FS_BT_H_OR                                                \
-        "s_cbranch_scc1 .Lfe_out_%=\n\t" /* steps 1 .. 4 */                                                         \
-        FS_PK_F(FS_R0, "s[66:67]")                                                                                  \
-        "s_lshr_b32 %[oc], %[off], 1\n\t"                                                                           \
-        "s_load_dwordx16 s[36:51], s[68:69], %[oc]\n\t"                                                             \
-        "s_load_dwordx16 s[52:67], s[68:69], %[oc] offset:0x40\n\t"                                                 \
-        "s_load_dwordx4 s[72:75], s[70:71], %[off]\n\t"                                                             \
-        FS_PK_MA(FS_R0) FS_PK_MB(FS_R0) FS_PK_P FS_PK_A(FS_R1)                                                      \
-        "s_waitcnt lgkmcnt(0)\n\t" PF                                                                               \
-        FS_PK_F(FS_R1, "s[36:37]") FS_FL_ACC("v50", "v51") FS_PK_MA(FS_R1) FS_PK_MB(FS_R1) FS_PK_P FS_PK_A(FS_R2)   \
-        FS_PK_F(FS_R2, "s[38:39]") FS_FL_ACC("v52", "v53") FS_PK_MA(FS_R2) FS_PK_MB(FS_R2) FS_PK_P FS_PK_A(FS_R3)   \
-        FS_PK_F(FS_R3, "s[40:41]") FS_FL_ACC("v54", "v55") FS_PK_MA(FS_R3) FS_PK_MB(FS_R3) FS_PK_P FS_PK_A(FS_R0)   \
-        /* steps 5 .. 8: w4's floor part and max in step 5, the second block's tests in step 6 */                   \
-        FS_FD16_PAIR("s[42:43]", "s[44:45]", "s72", ".Lfe_b1_%=") FS_FD16_TAIL("s[46:47]", "s[48:49]")              \
-        /* steps 9 .. 12 */                                                                                         \
-        FS_FD16_PAIR("s[50:51]", "s[52:53]", "s73", ".Lfe_b2_%=") FS_FD16_TAIL("s[54:55]", "s[56:57]")              \
-        /* steps 13 .. 16 */                                                                                        \
-        FS_FD16_PAIR("s[58:59]", "s[60:61]", "s74", ".Lfe_b3_%=") FS_FD16_TAIL("s[62:63]", "s[64:65]")              \
-        "s_add_u32 %[off], %[off], 0x100\n\t"                                                                       \
-        FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") "s_branch .Lfe_loop_%=\n"                                      \
-        ".Lfe_b1_%=:\n\t" /* block 2 needs its bound tests (or H): the state is w4 in v[48:49], at entry 3 */       \
-        "s_mov_b64 s[66:67], s[42:43]\n\t"                                                                          \
-        "s_mov_b32 s75, s72\n\t"                                                                                    \
-        "s_add_u32 %[off], %[off], 0x40\n\t"                                                                        \
-        "s_branch .Lfe_out_%=\n"                                                                                    \
-        ".Lfe_b2_%=:\n\t" /* block 3: w8, entry 7 */                                                                \
-        "s_mov_b64 s[66:67], s[50:51]\n\t"                                                                          \
-        "s_mov_b32 s75, s73\n\t"                                                                                    \
-        "s_add_u32 %[off], %[off], 0x80\n\t"                                                                        \
-        "s_branch .Lfe_out_%=\n"                                                                                    \
-        ".Lfe_b3_%=:\n\t" /* block 4: w12, entry 11 */                                                              \
-        "s_mov_b64 s[66:67], s[58:59]\n\t"                                                                          \
-        "s_mov_b32 s75, s74\n\t"                                                                                    \
-        "s_add_u32 %[off], %[off], 0xc0\n"                                                                          \
-        ".Lfe_out_%=:\n\t" /* the verdict over every state of this invocation */                                    \
-        "s_mov_b32 %[st], 0\n\t" FS_FL_C                                                                            \
-        "s_cbranch_vccz .Lfe_end_%=\n\t"                                                                            \
-        "s_mov_b32 %[st], 3\n"                                                                                      \
-        ".Lfe_end_%=:\n\t"                                                                                          \
-        "s_waitcnt lgkmcnt(0)"                                                                                      \
-        : "+{v[48:49]}"(wv), "={v[50:51]}"(r1), "={v[52:53]}"(r2), "={v[54:55]}"(r3), "={v[56:57]}"(ts_),           \
-          "={v[58:59]}"(ta_), "+{v60}"(mxS), "={v61}"(tn_), "={v62}"(tl_), [m] "=&s"(msk_), [st] "=&s"(st),         \
-          "+{s75}"(pwi), "+{s[66:67]}"(zS), [off] "+s"(off), [oc] "=&s"(oc_), [pf] "=&s"(pf_), [pg] "=&s"(pg_),     \
-          [ph] "=&s"(ph_), [pi] "=&s"(pi_), [pj] "=&s"(pj_)                                                         \
-        : [se] "v"(sE2), [dc] "v"(dcs), [esh] "v"(Esh), [imdc] "v"(imdc), [lim16] "s"(lim16), "{s[68:69]}"(zpb2),   \
-          "{s[70:71]}"(zqbp), [flr] "s"(kFloorBits)                                                                 \
-        : "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50",  \
-          "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65",  \
-          "s72", "s73", "s74", "vcc", "scc")
 
 // The sixteen-step body as a TWO-STAGE PIPELINE (round 5).  Scalar loads return out of order behind one counter, so a wait is a
 // wait for everything in flight -- but nothing says the wait has to follow the request: the body's entries live in two halves
@@ -495,8 +356,8 @@ constexpr int kFloorBits = (127 - FS_FL_FLOOR_EXP) << 23;
 // instruction that reads E15 of the body before), the next body's lower half at step 10 (right after the instructions that read
 // E7 and the bound of entry 7) -- and waited for eight steps later, just before its first use, when it has long landed: the
 // only thing in flight at either wait is the half requested eight steps ago.  A wave that is alone on its SIMD no longer
-// stands still for an L2 round trip per body (C2's interior pixels: 4.7 M dependent steps; FS_FAST_LOOP_FD16 with its warming
-// loads measured ~30 ns per step against the ~19 ns of the step's dependent arithmetic).  Same registers as FS_FAST_LOOP_FD16,
+// stands still for an L2 round trip per body (C2's interior pixels: 4.7 M dependent steps; round 4's sixteen-step body with its
+// warming loads measured ~30 ns per step against the ~19 ns of the step's dependent arithmetic).  Same registers as that body,
 // statuses 0 and 3 as there (4: below).  The half requested past the end of a run is never used (the companion arrays carry 32
 // entries of slack).
 // The deferred floor verdict is taken PER BODY: the state a body starts from is kept (v[46:47], its step count in `cko`) once
@@ -663,10 +524,7 @@ __device__ __forceinline__ long long norm_key_nz(float m, int e)
 // Steps per scaled run (a multiple of the 8-step body): a run's scale is fixed, and its lanes must have this many
 // steps left before the orbit ends and before their iteration limit.  Measured on View 5 (C3 / C2, ms): 64: 69.9 / 385,
 // 128: 68.6 / 390, 256: 68.0 / 372, 512: 68.2 / 380, 1024: 68.0 / 380, 4096: 78.9 / 561 (too few lanes qualify).
-#ifndef FS_SCALED_CHUNK
-#define FS_SCALED_CHUNK 256
-#endif
-constexpr uint32_t kScaledChunk = FS_SCALED_CHUNK;
+constexpr uint32_t kScaledChunk = 256;
 static_assert(kScaledChunk % 8 == 0 && kScaledChunk >= 64, "a run is a whole number of 8-step bodies");
 
 // Steps of the next scaled run: kScaledChunk when every (active) lane has that many left, else 64, else 16, else none --
@@ -679,18 +537,10 @@ static_assert(kScaledChunk % 8 == 0 && kScaledChunk >= 64, "a run is a whole num
 // (no back-off) 60.3 / 10.27, 1: 57.7 / 9.81, 3: 56.5 / 9.41, 7: 55.8 / 9.36, 15: 55.5 / 9.13, 31: 56.1 / 9.28, 63: 55.4 / 9.17;
 // doubling instead of counting up: no better; neither is waiting for a careful step that leaves every lane's dz 1 .. 4 binades
 // below the orbit value it arrived at (57.3 .. 58.7).  Which steps run scaled changes no result.
-#ifndef FS_BACKOFF_CAP
-#define FS_BACKOFF_CAP 15
-#endif
-constexpr uint32_t kScaledBackoffCap = FS_BACKOFF_CAP;
-// Steps of a hot run (k_lav2_hdr32_fast, see there) before the scale is re-centred.
-#ifndef FS_HOT_RUN_STEPS
-#define FS_HOT_RUN_STEPS 64 /* measured on C3 (kernel ms): 8: 50.2, 16: 49.75, 32: 49.7, 64: 49.5, 128 .. 1024: 49.5 - 49.6 */
-#endif
-constexpr uint32_t kHotRunSteps = FS_HOT_RUN_STEPS;
-#ifndef FS_HOT_AFTER_FAIL
-#define FS_HOT_AFTER_FAIL 0 /* A/B, measured neutral on C3 (43.80 against 43.85 ms): 1 = the step a run failed on goes to a hot run before the careful step */
-#endif
+constexpr uint32_t kScaledBackoffCap = 15;
+// Steps of a hot run (k_lav2_hdr32_fast, see there) before the scale is re-centred.  Measured on C3 (kernel ms): 8: 50.2,
+// 16: 49.75, 32: 49.7, 64: 49.5, 128 .. 1024: 49.5 - 49.6.
+constexpr uint32_t kHotRunSteps = 64;
 
 __device__ __forceinline__ uint32_t scaled_run_length(uint32_t left)
 {
@@ -705,10 +555,7 @@ __device__ __forceinline__ uint32_t scaled_run_length(uint32_t left)
 // for every instruction of a run's entry and exit (and waits out their vector loads): at 256 steps per run they were 40 % of the
 // time of C2's never-escaping pixels (tools/microbench/lone_pace.hip: the loop's own pace is 11.5 ns per step, the kernel's
 // 21 - 31).  A run still ends where it has to: H, a floor or bound failure, a block that needs its tests at the very end.
-#ifndef FS_PO_CHUNK
-#define FS_PO_CHUNK 2048
-#endif
-constexpr uint32_t kPoChunk = FS_PO_CHUNK;
+constexpr uint32_t kPoChunk = 2048;
 static_assert(kPoChunk % 16 == 0 && kPoChunk >= kScaledChunk && kPoChunk <= (1u << 20), "whole 16-step bodies; offsets stay 32-bit");
 // Between the tiers: when every lane has as many steps left as the first one (the lanes of a never-escaping tile walk the orbit
 // together), the run takes exactly those -- a pass over View 5's 16 046-entry orbit is then 8 runs instead of 17 (seven of 2048

@@ -61,9 +61,8 @@ def test_hdr64_frames_in_count_order_are_the_first_frame(renderer, native_libs, 
     fourth, ordered3 = _frame(r, co, n, T_HDR64, parity)
     # (round 6) the view's FIRST frame runs its tiles in the order of a sampled PerformAT count when the table has an AT; the later ones do not
     assert _frame.sampled[1:] == [False, False, False] and _frame.sampled[0] == bool(la.use_at)
-    # (round 6: a frame whose table has an AT makes its own order from the AT pass -- ordered from the first frame on)
-    inframe = False  # (FSMI355_C4_INFRAME_ORDER=1, an A/B that is off: DESIGN.md 7)
-    assert (ordered0, ordered1, ordered2, ordered3) == ((True, True, True, True) if inframe else (False, False, True, True))
+    # (the first frame of a view leaves its key behind, the second records and sorts, the third and later run ordered)
+    assert (ordered0, ordered1, ordered2, ordered3) == (False, False, True, True)
     assert np.array_equal(second, first) and np.array_equal(third, first) and np.array_equal(fourth, first)
     _oracle.set_row_step(255)
     try:
@@ -78,7 +77,7 @@ def test_hdr64_frames_in_count_order_are_the_first_frame(renderer, native_libs, 
     a, oa = _frame(r, co2, n, T_HDR64, parity)
     b, ob_ = _frame(r, co2, n, T_HDR64, parity)
     b2, ob2 = _frame(r, co2, n, T_HDR64, parity)
-    assert (oa, ob_, ob2) == ((True, True, True) if inframe else (False, False, True)) and np.array_equal(a, b) and np.array_equal(a, b2)
+    assert (oa, ob_, ob2) == (False, False, True) and np.array_equal(a, b) and np.array_equal(a, b2)
     # the A/B switch and fs_forget_tile_costs
     assert r.set_kernel_variant(0, natural_tile_order=True) == 0
     del _frame.sampled[:]
@@ -88,7 +87,7 @@ def test_hdr64_frames_in_count_order_are_the_first_frame(renderer, native_libs, 
     assert oc is False and np.array_equal(c, a)
     assert r.forget_tile_costs() == 0
     d, od = _frame(r, co2, n, T_HDR64, parity)
-    assert od is inframe and np.array_equal(d, a)
+    assert od is False and np.array_equal(d, a)
 
 
 def test_hdr64_count_order_with_row_bands(renderer, native_libs):
