@@ -111,6 +111,7 @@ def render_lib():
     _decl(lib, "fs_upload_la", u32, [vp, u64, C.c_int, u32, vp, u32, vp, u32, C.c_int, C.c_int, vp])
     _decl(lib, "fs_upload_bla", u32, [vp, C.c_int, vp, vp, i32, i32])
     _decl(lib, "fs_render_lav2", u32, [vp, C.c_int, C.c_int, C.c_int, vp, u64])
+    _decl(lib, "fs_feature_eval", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
     _decl(lib, "fs_render_bla", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_render_direct", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_upload_orbit_scaled", u32, [vp, C.c_int, u32, vp, vp, u64, u64])
@@ -187,7 +188,8 @@ def render_lib():
 RENDER_SYMBOLS = [
     "fs_create", "fs_destroy", "fs_test_device_is_working", "fs_device_count", "fs_error_string", "fs_init_memory", "fs_set_row_bands",
     "fs_local_rows", "fs_set_external_iter_buffer", "fs_device_iter_buffer", "fs_rounded_width", "fs_upload_orbit", "fs_upload_orbit_compressed",
-    "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
+    "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_feature_eval",
+    "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
     "fs_render_direct_lp", "fs_clear",
     "fs_render_current", "fs_sync_compute", "fs_compute_stream", "fs_sync_display", "fs_query_compute", "fs_enqueue_done_callback",
@@ -235,6 +237,15 @@ def inputs_lib():
     _decl(lib, "fsh_orbit_load_im", vp, [C.c_char_p, C.POINTER(u64)])
     _decl(lib, "fsh_orbit_is64", C.c_int, [vp])
     _decl(lib, "fsh_orbit_destroy", None, [vp])
+    _decl(lib, "fsh_feature_begin", vp, [vp, vp, u32, u32, u32, u64])
+    _decl(lib, "fsh_feature_destroy", None, [vp])
+    _decl(lib, "fsh_feature_is64", C.c_int, [vp])
+    _decl(lib, "fsh_feature_candidates", u64, [vp])
+    _decl(lib, "fsh_feature_next_batch", u64, [vp, vp, u64, C.POINTER(C.c_int), vp, C.POINTER(u64)])
+    _decl(lib, "fsh_feature_consume", None, [vp, vp, u64])
+    _decl(lib, "fsh_feature_found", u64, [vp])
+    _decl(lib, "fsh_feature_result", C.c_int, [vp, u64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(u64),
+                                                vp, C.POINTER(u32)])
     _decl(lib, "fsh_orbit_count", u64, [vp])
     _decl(lib, "fsh_orbit_scale_entries", u64, [vp, vp, vp, u64])
     _decl(lib, "fsh_orbit_period", u64, [vp])

@@ -61,6 +61,24 @@ template <> struct FsDev<double> {
     using BLA = fs_bla_hdr64;
 };
 
+// Feature Finder evaluator (kernels_feature.hip, fs_feature_eval): the ABI records by type, and one candidate's state between
+// the bounded launches (phase 0 = Evaluate_PT, 1 = the Direct fixed-period fallback, 2 = finished and written out).
+template <class F> struct FsFeatRec;
+template <> struct FsFeatRec<float> {
+    using In = fs_feature_in_hdr32;
+    using Out = fs_feature_out_hdr32;
+};
+template <> struct FsFeatRec<double> {
+    using In = fs_feature_in_hdr64;
+    using Out = fs_feature_out_hdr64;
+};
+template <class F> struct FsFeatLane {
+    fs::hcplx<F> z, dz, dzdc, zcoeff, dc, c;
+    fs::hreal<F> sqr_r, sqr_scale; // PeriodicityPP: SqrNearLinearRadius, SqrNearLinearRadiusScale
+    uint64_t step, cap, period;
+    uint32_t ref, phase;
+};
+
 template <class F> struct FsCoordsT {
     fs::hreal<F> dx, dy, centerX, centerY;
 };
@@ -341,6 +359,14 @@ void fsk_decompress_orbit_hdr32(const fs_orbit_hdr32_rc *wp, uint64_t n_wp, uint
 void fsk_decompress_orbit_hdr64(const fs_orbit_hdr64_rc *wp, uint64_t n_wp, uint64_t n_uncompressed, fs_real_hdr64 cxLow,
                                 fs_real_hdr64 cyLow, FsZ64 *out, hipStream_t s);
 void fsk_prepare_orbit_hdr64(const fs_orbit_hdr64 *in, FsZ64 *out, uint64_t n, hipStream_t s);
+// Feature Finder evaluator (kernels_feature.hip): set up n candidates from their fs_feature_in_* records, then advance every
+// unfinished one by at most `slice` steps per call; *unfinished (zeroed by the caller) counts those still running afterwards.
+template <class F>
+void fsk_feature_init(const void *in, FsFeatLane<F> *st, void *out, uint64_t n, int find, fs::hreal<F> R, uint64_t max_iters,
+                      uint64_t count, hipStream_t s);
+template <class F>
+void fsk_feature_step(const typename FsDev<F>::Z *zref, uint32_t count, FsFeatLane<F> *st, void *out, uint64_t n, int find,
+                      int iter_u64, uint32_t slice, uint32_t *unfinished, hipStream_t s);
 void fsk_make_quiet_orbit(const float4 *zref, float4 *zq, float2 *zs2, float4 *zqb, uint64_t n, hipStream_t s);
 // Launch order for "long tiles first": order[0 .. n_slots) = the tiles whose probe count (their own centre's or a
 // neighbour's) reached `threshold`, in tile order, then the others, then 0xFFFFFFFF; order[n_slots] = the number of long

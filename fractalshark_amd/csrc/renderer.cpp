@@ -874,6 +874,66 @@ template <class R64, class R32> static bool narrow_la(const void *in, uint32_t n
 }
 
 
+// Steps per candidate per launch of the Feature Finder evaluator (kernels_feature.hip): bounds one launch to a fraction of a
+// second at the measured pace, whatever the iteration cap.
+static constexpr uint32_t kFeatureSlice = 1u << 18;
+
+template <class F>
+static uint32_t feature_eval(fs_renderer *r, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
+                             const void *in, void *out, uint64_t n)
+{
+    using In = typename FsFeatRec<F>::In;
+    using Out = typename FsFeatRec<F>::Out;
+    using Real = typename FsDev<F>::Real;
+    const auto *zref = (const typename FsDev<F>::Z *)(sizeof(F) == 4 ? (const void *)r->zref : (const void *)r->zref64);
+    if (iter_bytes == 4 && mode == FS_FEATURE_FIXED)
+        for (uint64_t k = 0; k < n; k++)
+            if (((const In *)in)[k].period > 0xFFFFFFFFull)
+                return hipErrorInvalidValue; // a period IterType cannot hold
+    const Real rad = *(const Real *)radius;
+    const fs::hreal<F> R{rad.m, rad.e};
+    hipStream_t s = r->compute;
+    void *d_in = nullptr, *d_out = nullptr, *d_st = nullptr, *d_cnt = nullptr;
+    hipError_t e = r_alloc(r, &d_in, n * sizeof(In), kFrame);
+    if (e == hipSuccess)
+        e = r_alloc(r, &d_out, n * sizeof(Out), kFrame);
+    if (e == hipSuccess)
+        e = r_alloc(r, &d_st, n * sizeof(FsFeatLane<F>), kFrame);
+    if (e == hipSuccess)
+        e = r_alloc(r, &d_cnt, sizeof(uint32_t), kFrame);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_in, in, n * sizeof(In), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        fsk_feature_init<F>(d_in, (FsFeatLane<F> *)d_st, d_out, n, mode == FS_FEATURE_FIND, R, max_iters, r->orbit_uncompressed,
+                            s);
+        e = hipGetLastError();
+    }
+    // slices until no candidate is left running; each ends in a synchronisation (a launch lasts a fraction of a second)
+    while (e == hipSuccess) {
+        uint32_t left = 0;
+        e = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), s);
+        if (e != hipSuccess)
+            break;
+        fsk_feature_step<F>(zref, (uint32_t)r->orbit_uncompressed, (FsFeatLane<F> *)d_st, d_out, n, mode == FS_FEATURE_FIND,
+                            iter_bytes == 8, kFeatureSlice, (uint32_t *)d_cnt, s);
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(&left, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (left == 0)
+            break;
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out, d_out, n * sizeof(Out), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    for (void *p : {d_in, d_out, d_st, d_cnt})
+        if (p)
+            (void)r_free(r, p);
+    return (uint32_t)e;
+}
+
 extern "C" {
 
 fs_renderer *fs_create(int device)
@@ -2374,6 +2434,28 @@ static const uint32_t *cold_tile_order(fs_renderer *r, FsTileSampleArgs &S)
     fsk_tile_order_finish(r->cold_order, S.n_slots, S.tiles_x * S.tiles_y, r->compute);
     r->last_cold_ordered = true;
     return r->cold_order;
+}
+
+uint32_t fs_feature_eval(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
+                         const void *in, void *out, uint64_t n)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if ((type_tag != FS_T_HDR32 && type_tag != FS_T_HDR64) || (iter_bytes != 4 && iter_bytes != 8) ||
+        (mode != FS_FEATURE_FIND && mode != FS_FEATURE_FIXED))
+        return FS_ERR_UNSUPPORTED;
+    if (!r->compute || !r->orbit_ok || r->orbit_type != type_tag)
+        return FS_ERR_6;
+    if (r->orbit_seq)
+        return FS_ERR_UNSUPPORTED; // only the waypoints are resident: the evaluator reads the expanded orbit
+    if ((type_tag == FS_T_HDR32 ? (const void *)r->zref : (const void *)r->zref64) == nullptr)
+        return FS_ERR_6;
+    if (n == 0)
+        return 0;
+    if (!radius || !in || !out)
+        return hipErrorInvalidValue;
+    return type_tag == FS_T_HDR32 ? feature_eval<float>(r, iter_bytes, mode, radius, max_iters, in, out, n)
+                                  : feature_eval<double>(r, iter_bytes, mode, radius, max_iters, in, out, n);
 }
 
 uint32_t fs_render_lav2(fs_renderer *r, int type_tag, int mode, int parity, const void *coords, uint64_t n_iterations)

@@ -140,6 +140,24 @@ class GPURenderer:
                                          C.addressof(la.at))
         return err
 
+    def FeatureEval(self, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
+        """fs_feature_eval: the Feature Finder's perturbation evaluator on the resident orbit (include/fsmi355.h).
+        T = T_HDR32 / T_HDR64; mode = features.FIND / features.FIXED; radius = R as the raw bytes of an fs_real_hdr32 /
+        fs_real_hdr64 (numpy record); records_in / records_out = numpy arrays of features.FEATURE_IN_* / FEATURE_OUT_* records
+        (the same length).  Synchronous."""
+        from . import features
+        din, dout, dreal = features.records(T == T_HDR64)
+        n = len(records_in)
+        if T in (T_HDR32, T_HDR64) and (records_in.dtype != din or records_out.dtype != dout or
+                                        np.asarray(radius).dtype != dreal):
+            raise ValueError("records and radius must be the features.FEATURE_*_%s / REAL_%s dtypes of T"
+                             % (("HDR64",) * 2 if T == T_HDR64 else ("HDR32",) * 2))
+        if len(records_out) < n or not (records_in.flags.c_contiguous and records_out.flags.c_contiguous):
+            raise ValueError("records_out must be contiguous and hold at least as many records as records_in")
+        radius = np.ascontiguousarray(radius)
+        return self._lib.fs_feature_eval(self._h, int(T), int(iter_bytes), int(mode), radius.ctypes.data, int(max_iters),
+                                         records_in.ctypes.data if n else None, records_out.ctypes.data if n else None, n)
+
     def InitializePerturbPlain(self, GenerationNumber1, plain, with_la=True):
         """InitializePerturb<IterType, T, T, Disable, T> for a non-HDR T: plain = inputs.PlainInputs (kind f32 -> float,
         f64 -> double, 2x32 -> CudaDblflt<MattDblflt>), i.e. the inputs of Gpu1x32 / Gpu1x64 / Gpu2x32 PerturbedLAv2*."""

@@ -211,6 +211,27 @@ void fsh_convert_la_f64_to_p2x32(const fs_la_f64_u32 *in, uint64_t n, fs_la_p2x3
 void fsh_convert_at_f64_to_p2x32(const fs_at_f64_u32 *in, fs_at_p2x32_u32 *out);
 void fsh_convert_coords_f64_to_p2x32(const double in[4], fs_real_p2x32 out[4]);
 
+/* Feature Finder scan (FeatureFinderOrchestrator PT / PTScan, FeatureFinderOrchestrator.cpp:485-559, and
+ * FeatureFinder::FindPeriodicPoint_Common up to SetFound, FeatureFinder.cpp:2443-2697) as a batched state machine: an nx x ny grid
+ * of screen points of the view (the reference: 12 x 12), search radius = half the view's height / 12, T = the orbit's type.
+ * Rounds: fsh_feature_next_batch writes the fs_feature_in_* records of the candidates still running (at most cap; all of one
+ * mode: period searches first), the call's mode (FS_FEATURE_FIND / FS_FEATURE_FIXED), R and cap of iterations -- the arguments of
+ * one fs_feature_eval call -- and returns their number (0: the scan is over); fsh_feature_consume takes the n fs_feature_out_* records of that batch back and applies the
+ * Newton updates and stop tests in mpf.  Found points in grid order: fsh_feature_result (k < fsh_feature_found) gives cx, cy and
+ * the intrinsic radius (ComputeIntrinsicRadius_HP) as "%.Fe" strings, the period, residual2 as HDRFloat<double> and the grid
+ * index (row-major). */
+typedef struct fsh_feature fsh_feature;
+fsh_feature *fsh_feature_begin(const fsh_view *v, const fsh_orbit *o, uint32_t nx, uint32_t ny, uint32_t iter_bytes,
+                               uint64_t max_iters);
+void fsh_feature_destroy(fsh_feature *f);
+int fsh_feature_is64(const fsh_feature *f);
+uint64_t fsh_feature_candidates(const fsh_feature *f);
+uint64_t fsh_feature_next_batch(fsh_feature *f, void *in, uint64_t cap, int *mode, void *radius, uint64_t *max_iters);
+void fsh_feature_consume(fsh_feature *f, const void *out, uint64_t n);
+uint64_t fsh_feature_found(const fsh_feature *f);
+int fsh_feature_result(fsh_feature *f, uint64_t k, char *cx, char *cy, char *radius, size_t buflen, uint64_t *period,
+                       fs_real_hdr64 *residual2, uint32_t *grid_index);
+
 #ifdef __cplusplus
 }
 #endif

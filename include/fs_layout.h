@@ -440,8 +440,50 @@ typedef struct fs_reduction {
     uint64_t Sum;
 } fs_reduction;
 
+/* fs_feature_eval (fsmi355.h): one Feature Finder candidate in, one evaluation out.  T = HDRFloat<float> (hdr32) or
+ * HDRFloat<double> (hdr64).  dc = T{cX_hp - HiX} + i T{cY_hp - HiY} (Evaluate_PT's dc), c = T{cX_hp} + i T{cY_hp} (the Direct
+ * fallback's parameter), both reduced; period: the period of a fixed-period evaluation (ignored when finding one). */
+typedef struct fs_feature_in_hdr32 {
+    fs_cplx_hdr32 dc;
+    fs_cplx_hdr32 c;
+    uint64_t period;
+} fs_feature_in_hdr32;
+
+typedef struct fs_feature_in_hdr64 {
+    fs_cplx_hdr64 dc;
+    fs_cplx_hdr64 c;
+    uint64_t period;
+} fs_feature_in_hdr64;
+
+/* status: FS_FEATURE_REJECTED / FS_FEATURE_OK / FS_FEATURE_OK_DIRECT (fsmi355.h); the other fields are the evaluator's outputs
+ * (FeatureFinder::Evaluate_PT: ioPeriod, outDiff, outDzdc, outZcoeff, outResidual2), all zero bits for a rejected candidate.
+ * period is counted at IterType width. */
+typedef struct fs_feature_out_hdr32 {
+    uint32_t status;
+    uint32_t pad0_;
+    uint64_t period;
+    fs_cplx_hdr32 diff;
+    fs_cplx_hdr32 dzdc;
+    fs_cplx_hdr32 zcoeff;
+    fs_real_hdr32 residual2;
+    uint32_t pad1_;
+} fs_feature_out_hdr32;
+
+typedef struct fs_feature_out_hdr64 {
+    uint32_t status;
+    uint32_t pad0_;
+    uint64_t period;
+    fs_cplx_hdr64 diff;
+    fs_cplx_hdr64 dzdc;
+    fs_cplx_hdr64 zcoeff;
+    fs_real_hdr64 residual2;
+} fs_feature_out_hdr64;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(fs_feature_in_hdr32) == 32 && sizeof(fs_feature_in_hdr64) == 56 && sizeof(fs_feature_out_hdr32) == 64 &&
+                  sizeof(fs_feature_out_hdr64) == 104,
+              "Feature Finder records");
 static_assert(sizeof(fs_orbit_hdr32) == 16, "orbit entry");
 static_assert(sizeof(fs_orbit_hdr32_rc) == 24 && sizeof(fs_orbit_hdr64_rc) == 40, "compressed orbit entry");
 static_assert(sizeof(fs_orbit_f32_rc) == 16 && sizeof(fs_orbit_f64_rc) == 24 && sizeof(fs_orbit_p2x32_rc) == 24 &&

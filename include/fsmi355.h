@@ -172,6 +172,21 @@ uint32_t fs_upload_la(fs_renderer *r, uint64_t generation, int type_tag, uint32_
                       uint32_t n_las, const void *stages, uint32_t n_stages, int is_valid, int use_at,
                       const void *at_info);
 
+/* The Feature Finder's perturbation evaluator (FeatureFinder::PTEvaluator::Eval, FeatureFinder.cpp:2313-2354, with
+ * Evaluate_PT :1757-1958, PeriodicityPP :1471-1534 and the Direct fixed-period fallback Evaluate_PeriodResidualAndDzdc_Direct
+ * :1661-1711) for n candidates at once, against the expanded orbit of fs_upload_orbit / fs_upload_orbit_compressed (the same
+ * HBM copy the render kernels read).  mode FS_FEATURE_FIND: Eval<true> with cap max_iters; FS_FEATURE_FIXED: Eval<false> at
+ * each candidate's period (PT, then Direct when PT escapes).  radius = R = HdrSqrt(SqrRadius) (fs_real_hdr32 / _hdr64);
+ * in / out = fs_feature_in_* / fs_feature_out_* (fs_layout.h) by type_tag FS_T_HDR32 / FS_T_HDR64; iter_bytes = sizeof(IterType)
+ * (4 or 8: the width periods are counted at).  Synchronous on the compute stream; n = 0 does nothing.  Frame state (iteration
+ * buffer, recorded tile costs and orders, orbit / LA caches, kernel-time history) is left as it was.
+ * FS_ERR_6: no orbit of this type resident.  FS_ERR_UNSUPPORTED: another type tag, iter_bytes or mode (FS_FEATURE_LA: the LA
+ * evaluator is not built), or a waypoint-resident orbit (fs_set_compressed_orbit_mode(r, 1)). */
+enum { FS_FEATURE_FIND = 0, FS_FEATURE_FIXED = 1, FS_FEATURE_LA = 2 };
+enum { FS_FEATURE_REJECTED = 0, FS_FEATURE_OK = 1, FS_FEATURE_OK_DIRECT = 2 };
+uint32_t fs_feature_eval(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
+                         const void *in, void *out, uint64_t n);
+
 /* BLA table upload (GPU_BLAS ctor, BLA.cuh:123-160); the reference does this inside RenderPerturbBLA. */
 uint32_t fs_upload_bla(fs_renderer *r, int type_tag, const void *const *levels, const uint64_t *level_sizes,
                        int32_t n_levels, int32_t lm2);
