@@ -112,6 +112,8 @@ def render_lib():
     _decl(lib, "fs_upload_bla", u32, [vp, C.c_int, vp, vp, i32, i32])
     _decl(lib, "fs_render_lav2", u32, [vp, C.c_int, C.c_int, C.c_int, vp, u64])
     _decl(lib, "fs_feature_eval", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
+    _decl(lib, "fs_feature_eval_direct", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
+    _decl(lib, "fs_set_feature_slice", u32, [vp, u32])
     _decl(lib, "fs_render_bla", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_render_direct", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_upload_orbit_scaled", u32, [vp, C.c_int, u32, vp, vp, u64, u64])
@@ -188,7 +190,7 @@ def render_lib():
 RENDER_SYMBOLS = [
     "fs_create", "fs_destroy", "fs_test_device_is_working", "fs_device_count", "fs_error_string", "fs_init_memory", "fs_set_row_bands",
     "fs_local_rows", "fs_set_external_iter_buffer", "fs_device_iter_buffer", "fs_rounded_width", "fs_upload_orbit", "fs_upload_orbit_compressed",
-    "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_feature_eval",
+    "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_feature_eval", "fs_feature_eval_direct", "fs_set_feature_slice",
     "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
     "fs_render_direct_lp", "fs_clear",
@@ -238,6 +240,9 @@ def inputs_lib():
     _decl(lib, "fsh_orbit_is64", C.c_int, [vp])
     _decl(lib, "fsh_orbit_destroy", None, [vp])
     _decl(lib, "fsh_feature_begin", vp, [vp, vp, u32, u32, u32, u64])
+    _decl(lib, "fsh_feature_begin_direct", vp, [vp, C.c_int, u32, u32, u32, u64])
+    _decl(lib, "fsh_feature_begin_direct_at", vp, [vp, C.c_int, u32, u32, u32, u64])
+    _decl(lib, "fsh_feature_direct_grid", C.c_int, [vp, C.c_int, u32, u32, vp, vp])
     _decl(lib, "fsh_feature_destroy", None, [vp])
     _decl(lib, "fsh_feature_is64", C.c_int, [vp])
     _decl(lib, "fsh_feature_candidates", u64, [vp])

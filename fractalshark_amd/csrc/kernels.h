@@ -78,6 +78,13 @@ template <class F> struct FsFeatLane {
     uint64_t step, cap, period;
     uint32_t ref, phase;
 };
+// The Direct evaluator's candidate (kernels_feature_direct.hip, fs_feature_eval_direct): no orbit position, no dz, no
+// PeriodicityPP radius (phase 3 = Evaluate_FindPeriod_Direct, 1 = the fixed-period loop, 2 = finished and written out).
+template <class F> struct FsFeatDirectLane {
+    fs::hcplx<F> z, dzdc, zcoeff, c;
+    uint64_t step, cap, period;
+    uint32_t phase, pad_;
+};
 
 template <class F> struct FsCoordsT {
     fs::hreal<F> dx, dy, centerX, centerY;
@@ -367,6 +374,13 @@ void fsk_feature_init(const void *in, FsFeatLane<F> *st, void *out, uint64_t n, 
 template <class F>
 void fsk_feature_step(const typename FsDev<F>::Z *zref, uint32_t count, FsFeatLane<F> *st, void *out, uint64_t n, int find,
                       int iter_u64, uint32_t slice, uint32_t *unfinished, hipStream_t s);
+// The Direct evaluator (kernels_feature_direct.hip), same calling pattern; needs no orbit.
+template <class F>
+void fsk_feature_direct_init(const void *in, FsFeatDirectLane<F> *st, void *out, uint64_t n, int find, fs::hreal<F> R,
+                             uint64_t max_iters, hipStream_t s);
+template <class F>
+void fsk_feature_direct_step(FsFeatDirectLane<F> *st, void *out, uint64_t n, int find, int iter_u64, fs::hreal<F> R,
+                             uint32_t slice, uint32_t *unfinished, hipStream_t s);
 void fsk_make_quiet_orbit(const float4 *zref, float4 *zq, float2 *zs2, float4 *zqb, uint64_t n, hipStream_t s);
 // Launch order for "long tiles first": order[0 .. n_slots) = the tiles whose probe count (their own centre's or a
 // neighbour's) reached `threshold`, in tile order, then the others, then 0xFFFFFFFF; order[n_slots] = the number of long

@@ -3,7 +3,7 @@
 // Restates, operation for operation, in the arithmetic of hdr_math.hpp (HDRFloat<float | double>):
 //   FeatureFinder::Evaluate_PT<true | false>                 FeatureFinder.cpp:1757-1958
 //   PeriodicityPP::Init / CheckPeriodicity                   FeatureFinder.cpp:1471-1534
-//   FeatureFinder::Evaluate_PeriodResidualAndDzdc_Direct     FeatureFinder.cpp:1661-1711
+//   FeatureFinder::Evaluate_PeriodResidualAndDzdc_Direct     FeatureFinder.cpp:1661-1711   (feature_steps.hpp)
 //   PTEvaluator::Eval (PT, then Direct when a fixed-period PT evaluation escapes)  FeatureFinder.cpp:2313-2354
 // Points the reference fixes and this file keeps: escape radius^2 4096; the rebase test (refIteration >= count - 1 or
 // |z|^2 < |dz|^2) comes before the escape test; zcoeff and dzdc are advanced with the previous step's z; every product with the
@@ -15,14 +15,12 @@
 // All lanes start at orbit position 0 and stay in lockstep until their first rebase; while the wave's active lanes agree on the
 // position (a ballot vote), the two orbit entries of the step are read once for the wave through the scalar cache, else each
 // lane loads its own.
-#include "kernels.h"
-#include "../../include/fsmi355.h"
+#include "feature_steps.hpp"
 
 using namespace fs;
+using namespace fsfeat;
 
 namespace {
-
-enum : uint32_t { kPhasePT = 0, kPhaseDirect = 1, kPhaseDone = 2 };
 
 // Orbit entry i as a complex.  P = a global pointer (each lane its own entry: vector loads) or a constant-address-space one with a
 // wave-uniform index (one scalar load for the wave); fields read one by one (an address-space-qualified record cannot be copied
@@ -37,25 +35,6 @@ template <> struct OrbitRead<float4> { // {re, im, bitcast(exp), -}
 template <> struct OrbitRead<FsZ64> {
     template <class P> static __device__ __forceinline__ hcplx64 at(P z, uint32_t i) { return hcplx64{z[i].re, z[i].im, z[i].e}; }
 };
-
-__device__ __forceinline__ fs_cplx_hdr32 rec(hcplx32 a) { return fs_cplx_hdr32{a.re, a.im, a.e}; }
-__device__ __forceinline__ fs_cplx_hdr64 rec(hcplx64 a) { return fs_cplx_hdr64{a.re, a.im, a.e, 0}; }
-__device__ __forceinline__ fs_real_hdr32 rec(hreal32 a) { return fs_real_hdr32{a.m, a.e}; }
-__device__ __forceinline__ fs_real_hdr64 rec(hreal64 a) { return fs_real_hdr64{a.m, a.e, 0}; }
-
-template <class F>
-__device__ __forceinline__ void store_out(typename FsFeatRec<F>::Out &o, uint32_t status, uint64_t period, hcplx<F> diff,
-                                          hcplx<F> dzdc, hcplx<F> zcoeff, hreal<F> residual2)
-{
-    typename FsFeatRec<F>::Out r{};
-    r.status = status;
-    r.period = period;
-    r.diff = rec(diff);
-    r.dzdc = rec(dzdc);
-    r.zcoeff = rec(zcoeff);
-    r.residual2 = rec(residual2);
-    o = r;
-}
 
 // Evaluate_PT's set-up (:1774-1827) and PeriodicityPP::Init (:1478-1496); a candidate that fails it is finished here
 // (rejected in find mode, handed to the Direct loop in fixed mode, as PTEvaluator::Eval does).
@@ -219,27 +198,7 @@ __global__ void __launch_bounds__(64) k_feature_step(const typename FsDev<F>::Z 
                 s.phase = kPhaseDone;
             }
         } else if (s.phase == kPhaseDirect) {
-            // Evaluate_PeriodResidualAndDzdc_Direct, :1677-1710 (period steps counted at IterType width)
-            if ((IterT)s.step >= (IterT)s.cap) {
-                store_out<F>(out[i], FS_FEATURE_OK_DIRECT, (uint64_t)(IterT)s.period, s.z, s.dzdc, s.zcoeff,
-                             hr_reduced(hc_norm2(s.z)));
-                s.phase = kPhaseDone;
-                continue;
-            }
-            if (s.step == 0)
-                s.zcoeff = hc_from_hr(one, zero);
-            else
-                s.zcoeff = hc_mul(s.zcoeff, hc_mul_real(s.z, two));
-            hc_reduce(s.zcoeff);
-            s.dzdc = hc_add(hc_mul(s.dzdc, hc_mul_real(s.z, two)), oneC);
-            hc_reduce(s.dzdc);
-            s.z = hc_add(hc_mul(s.z, s.z), s.c);
-            hc_reduce(s.z);
-            s.step++;
-            if (hr_cmp_pos(hr_reduced(hc_norm2(s.z)), escape2) > 0) {
-                s.phase = kPhaseDone;
-                out[i] = typename FsFeatRec<F>::Out{};
-            }
+            direct_fixed_trip<F, IterT>(s, out[i], one, two, escape2, oneC);
         }
     }
 

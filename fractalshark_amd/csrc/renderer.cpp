@@ -193,6 +193,7 @@ struct fs_renderer {
     std::vector<Block> live_blocks, kept_blocks;
     std::mutex kept_mu; // kept_blocks only: another renderer of the same device may drain them when IT runs out of memory
     size_t host_alloc_bytes = 0;
+    uint32_t feature_slice = 0;      // fs_set_feature_slice (tests): steps per launch of the Feature Finder evaluators, 0 = default
     bool inject_input_oom = false;   // fault injection: FSMI355_FAIL_INPUT_ALLOC=1 at fs_create time
     void *arena = nullptr;           // work memory of fs_build_la (kept between calls, grown on demand)
     uint32_t *la_mail = nullptr;     // 32 words of coherent page-locked memory the build's kernels report through (k_la_mail)
@@ -915,7 +916,7 @@ static uint32_t feature_eval(fs_renderer *r, uint32_t iter_bytes, int mode, cons
         if (e != hipSuccess)
             break;
         fsk_feature_step<F>(zref, (uint32_t)r->orbit_uncompressed, (FsFeatLane<F> *)d_st, d_out, n, mode == FS_FEATURE_FIND,
-                            iter_bytes == 8, kFeatureSlice, (uint32_t *)d_cnt, s);
+                            iter_bytes == 8, r->feature_slice ? r->feature_slice : kFeatureSlice, (uint32_t *)d_cnt, s);
         e = hipGetLastError();
         if (e == hipSuccess)
             e = hipMemcpyAsync(&left, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
@@ -932,6 +933,86 @@ static uint32_t feature_eval(fs_renderer *r, uint32_t iter_bytes, int mode, cons
         if (p)
             (void)r_free(r, p);
     return (uint32_t)e;
+}
+
+// fs_feature_eval_direct: the same shape without an orbit (kernels_feature_direct.hip).
+template <class F>
+static uint32_t feature_eval_direct(fs_renderer *r, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
+                                    const void *in, void *out, uint64_t n)
+{
+    using In = typename FsFeatRec<F>::In;
+    using Out = typename FsFeatRec<F>::Out;
+    using Real = typename FsDev<F>::Real;
+    const bool find = mode == FS_FEATURE_FIND;
+    if (iter_bytes == 4 && !find)
+        for (uint64_t k = 0; k < n; k++)
+            if (((const In *)in)[k].period > 0xFFFFFFFFull)
+                return hipErrorInvalidValue; // a period IterType cannot hold
+    const Real rad = *(const Real *)radius;
+    const fs::hreal<F> R{rad.m, rad.e};
+    const uint32_t slice = r->feature_slice ? r->feature_slice : kFeatureSlice;
+    hipStream_t s = r->compute;
+    void *d_in = nullptr, *d_out = nullptr, *d_st = nullptr, *d_cnt = nullptr;
+    hipError_t e = r_alloc(r, &d_in, n * sizeof(In), kFrame);
+    if (e == hipSuccess)
+        e = r_alloc(r, &d_out, n * sizeof(Out), kFrame);
+    if (e == hipSuccess)
+        e = r_alloc(r, &d_st, n * sizeof(FsFeatDirectLane<F>), kFrame);
+    if (e == hipSuccess)
+        e = r_alloc(r, &d_cnt, sizeof(uint32_t), kFrame);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_in, in, n * sizeof(In), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        fsk_feature_direct_init<F>(d_in, (FsFeatDirectLane<F> *)d_st, d_out, n, find, R, max_iters, s);
+        e = hipGetLastError();
+    }
+    while (e == hipSuccess) {
+        uint32_t left = 0;
+        e = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), s);
+        if (e != hipSuccess)
+            break;
+        fsk_feature_direct_step<F>((FsFeatDirectLane<F> *)d_st, d_out, n, find, iter_bytes == 8, R, slice, (uint32_t *)d_cnt, s);
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(&left, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (left == 0)
+            break;
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out, d_out, n * sizeof(Out), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    for (void *p : {d_in, d_out, d_st, d_cnt})
+        if (p)
+            (void)r_free(r, p);
+    return (uint32_t)e;
+}
+
+// The renderer's two streams and its timing events, made once: by fs_init_memory, or by fs_feature_eval_direct on a renderer that
+// has no frame yet.
+static uint32_t ensure_streams(fs_renderer *r)
+{
+    if (r->compute)
+        return 0;
+    int lo = 0, hi = 0;
+    FS_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    FS_TRY(hipStreamCreateWithPriority(&r->compute, hipStreamNonBlocking, lo));
+    FS_TRY(hipStreamCreateWithPriority(&r->display, hipStreamNonBlocking, hi));
+    for (uint32_t i = 0; i < fs_renderer::kTimingRing; i++) {
+        FS_TRY(hipEventCreate(&r->ev_start[i]));
+        FS_TRY(hipEventCreate(&r->ev_stop[i]));
+    }
+    // the stream-ordered allocator keeps freed memory for the next allocation instead of returning it to the driver at
+    // every synchronisation (uploads synchronise: their host buffers are borrowed for the call only)
+    hipMemPool_t pool = nullptr;
+    if (hipDeviceGetDefaultMemPool(&pool, r->device) == hipSuccess && pool) {
+        uint64_t keep = ~0ull;
+        (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
+    }
+    (void)hipGetLastError();
+    return 0;
 }
 
 extern "C" {
@@ -1037,24 +1118,8 @@ uint32_t fs_init_memory(fs_renderer *r, uint32_t w, uint32_t h, uint32_t antiali
         return e;
     if (iter_bytes != 4 && iter_bytes != 8)
         return FS_ERR_UNSUPPORTED;
-    if (!r->compute) {
-        int lo = 0, hi = 0;
-        FS_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        FS_TRY(hipStreamCreateWithPriority(&r->compute, hipStreamNonBlocking, lo));
-        FS_TRY(hipStreamCreateWithPriority(&r->display, hipStreamNonBlocking, hi));
-        for (uint32_t i = 0; i < fs_renderer::kTimingRing; i++) {
-            FS_TRY(hipEventCreate(&r->ev_start[i]));
-            FS_TRY(hipEventCreate(&r->ev_stop[i]));
-        }
-        // the stream-ordered allocator keeps freed memory for the next allocation instead of returning it to the driver at
-        // every synchronisation (uploads synchronise: their host buffers are borrowed for the call only)
-        hipMemPool_t pool = nullptr;
-        if (hipDeviceGetDefaultMemPool(&pool, r->device) == hipSuccess && pool) {
-            uint64_t keep = ~0ull;
-            (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
-        }
-        (void)hipGetLastError();
-    }
+    if (uint32_t e = ensure_streams(r))
+        return e;
     // palette: re-upload when the host pointer or the generation changes (GPU_Render.cu:270-304)
     r->pal_aux_depth = palette_aux_depth;
     if (pal_interleaved && (r->pal_cached_host != pal_interleaved || r->pal_cached_gen != palette_generation ||
@@ -2456,6 +2521,32 @@ uint32_t fs_feature_eval(fs_renderer *r, int type_tag, uint32_t iter_bytes, int 
         return hipErrorInvalidValue;
     return type_tag == FS_T_HDR32 ? feature_eval<float>(r, iter_bytes, mode, radius, max_iters, in, out, n)
                                   : feature_eval<double>(r, iter_bytes, mode, radius, max_iters, in, out, n);
+}
+
+uint32_t fs_feature_eval_direct(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
+                                const void *in, void *out, uint64_t n)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if ((type_tag != FS_T_HDR32 && type_tag != FS_T_HDR64) || (iter_bytes != 4 && iter_bytes != 8) ||
+        (mode != FS_FEATURE_FIND && mode != FS_FEATURE_FIXED))
+        return FS_ERR_UNSUPPORTED;
+    if (n == 0)
+        return 0;
+    if (!radius || !in || !out)
+        return hipErrorInvalidValue;
+    if (uint32_t e = ensure_streams(r)) // no fs_init_memory needed
+        return e;
+    return type_tag == FS_T_HDR32 ? feature_eval_direct<float>(r, iter_bytes, mode, radius, max_iters, in, out, n)
+                                  : feature_eval_direct<double>(r, iter_bytes, mode, radius, max_iters, in, out, n);
+}
+
+uint32_t fs_set_feature_slice(fs_renderer *r, uint32_t steps)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    r->feature_slice = steps;
+    return 0;
 }
 
 uint32_t fs_render_lav2(fs_renderer *r, int type_tag, int mode, int parity, const void *coords, uint64_t n_iterations)

@@ -5,6 +5,9 @@ rounds and two final passes, every one a perturbation evaluation against the ref
 (FeatureFinderOrchestrator.cpp:535-559, FeatureFinder.cpp:2443-2697).  Here the host keeps the high-precision state of every
 candidate (libfsinputs: fsh_feature_*) and each round evaluates all candidates still running in one fs_feature_eval call, one
 GPU lane per candidate.
+
+The Direct / DirectScan modes (scan_direct, find_periodic_points_direct) are the same scan without a reference orbit, through
+fs_feature_eval_direct; period_map is their period search alone over a dense grid of the view.
 """
 import ctypes as C
 
@@ -43,6 +46,11 @@ def scan(view, orbit, evaluate, nx=12, ny=12, iter_bytes=4, max_iters=None):
     h = lib.fsh_feature_begin(view._h, orbit._h, int(nx), int(ny), int(iter_bytes), n_iter)
     if not h:
         raise ValueError("fsh_feature_begin: bad arguments")
+    return _run(lib, h, evaluate)
+
+
+def _run(lib, h, evaluate):
+    """The rounds of one fsh_feature scan, to its found points; destroys h."""
     try:
         is64 = bool(lib.fsh_feature_is64(h))
         din, dout, dreal = records(is64)
@@ -85,3 +93,58 @@ def find_periodic_points(renderer, view, orbit, nx=12, ny=12, T=T_HDR32, iter_by
             raise RuntimeError("fs_feature_eval failed: %d (%s)" % (err, renderer.ConvertErrorToString(err)))
 
     return scan(view, orbit, evaluate, nx, ny, iter_bytes, max_iters)
+
+
+def scan_direct(view, is64, evaluate, nx=12, ny=12, iter_bytes=4, max_iters=None, at=None):
+    """The Direct / DirectScan modes with any evaluator (fs_feature_eval_direct's contract): no orbit; T = HDRFloat<double> when
+    is64, else HDRFloat<float>.  at = (px, py): the non-scan mode, one candidate (grid 0) at that screen point, nx and ny unused.
+    Direct tells grid points apart only as far as T's mantissa does: far below its resolution every candidate is the same c."""
+    lib = _capi.inputs_lib()
+    n_iter = view.num_iterations if max_iters is None else int(max_iters)
+    if at is None:
+        h = lib.fsh_feature_begin_direct(view._h, 1 if is64 else 0, int(nx), int(ny), int(iter_bytes), n_iter)
+    else:
+        h = lib.fsh_feature_begin_direct_at(view._h, 1 if is64 else 0, int(at[0]), int(at[1]), int(iter_bytes), n_iter)
+    if not h:
+        raise ValueError("fsh_feature_begin_direct: bad arguments")
+    return _run(lib, h, evaluate)
+
+
+def _direct_evaluator(renderer, T, iter_bytes):
+    if T not in (T_HDR32, T_HDR64):
+        raise ValueError("T must be T_HDR32 or T_HDR64")
+
+    def evaluate(mode, radius, cap, rin, rout):
+        err = renderer.FeatureEvalDirect(T, iter_bytes, mode, radius, cap, rin, rout)
+        if err:
+            raise RuntimeError("fs_feature_eval_direct failed: %d (%s)" % (err, renderer.ConvertErrorToString(err)))
+
+    return evaluate
+
+
+def find_periodic_points_direct(renderer, view, nx=12, ny=12, T=T_HDR32, iter_bytes=4, max_iters=None):
+    """The reference's DirectScan with every evaluation on the GPU: as find_periodic_points, without an orbit -- `renderer` needs
+    none, nor InitializeMemory.  Returns the same dicts."""
+    return scan_direct(view, T == T_HDR64, _direct_evaluator(renderer, T, iter_bytes), nx, ny, iter_bytes, max_iters)
+
+
+def direct_grid(view, is64, nx, ny):
+    """(records_in, radius) of a DirectScan's period-search round over the view's nx x ny grid points, row-major: the first batch
+    of scan_direct, built without its state machine (libfsinputs does the high-precision arithmetic once per column and row)."""
+    din, _, dreal = records(is64)
+    rin, rad = np.zeros(int(nx) * int(ny), din), np.zeros(1, dreal)
+    if _capi.inputs_lib().fsh_feature_direct_grid(view._h, 1 if is64 else 0, int(nx), int(ny), rin.ctypes.data,
+                                                  rad.ctypes.data) != 0:
+        raise ValueError("fsh_feature_direct_grid: bad arguments")
+    return rin, rad
+
+
+def period_map(renderer, view, nx, ny, T=T_HDR64, iter_bytes=4, max_iters=None):
+    """The period the Direct search finds at each of the view's nx x ny grid points (the DirectScan's points and radius; nx = width,
+    ny = height: every pixel), 0 where it finds none: a uint64 array (ny, nx).  The search round only -- one
+    fs_feature_eval_direct call, no Newton."""
+    evaluate = _direct_evaluator(renderer, T, iter_bytes)
+    rin, rad = direct_grid(view, T == T_HDR64, nx, ny)
+    rout = np.zeros(len(rin), records(T == T_HDR64)[1])
+    evaluate(FIND, rad, view.num_iterations if max_iters is None else int(max_iters), rin, rout)
+    return np.where(rout["status"] == OK_DIRECT, rout["period"], 0).astype(np.uint64).reshape(int(ny), int(nx))

@@ -3113,7 +3113,8 @@ extern "C" void fsh_convert_coords_f64_to_p2x32(const double in[4], fs_real_p2x3
 // up to SetFound (FeatureFinder.cpp:2443-2697), restated as a batched state machine: every candidate's evaluations are asked for
 // together (fsh_feature_next_batch), made elsewhere (fs_feature_eval or the CPU checker), and handed back (fsh_feature_consume);
 // the Newton updates stay here, in mpf, as the reference keeps them.  FeatureFinder::Params defaults (FeatureFinder.h:58-63):
-// MaxNewtonIters 32, RelStepTol 2^-40, Eps2Accept = T{} (off).
+// MaxNewtonIters 32, RelStepTol 2^-40, Eps2Accept = T{} (off).  The Direct / DirectScan modes (fsh_feature_begin_direct*) are the same
+// machine without an orbit: FindPeriodicPoint_Common takes nothing from it, only PTEvaluator does (dc), so their records carry dc = 0.
 namespace {
 
 enum FeatStage { kFind = 0, kNewton = 1, kFinal1 = 2, kFinal2 = 3, kFound = 4, kRejected = 5 };
@@ -3177,6 +3178,7 @@ struct fsh_feature {
     uint32_t iter_bytes = 4;
     uint64_t max_iters = 0;
     uint64_t prec_bits = 0;
+    bool direct = false; // Direct / DirectScan: no orbit, records carry an all-zero dc
     Mp hiX, hiY;     // the reference orbit's point (results.GetHiX / GetHiY)
     Mp radius_hp;    // FeatureSummary radius: half the view's height / 12
     std::vector<FeatCand<float>> c32;
@@ -3190,7 +3192,49 @@ template <class F> std::vector<FeatCand<F>> &cands(fsh_feature &f);
 template <> std::vector<FeatCand<float>> &cands<float>(fsh_feature &f) { return f.c32; }
 template <> std::vector<FeatCand<double>> &cands<double>(fsh_feature &f) { return f.c64; }
 
-template <class F> void feature_begin(fsh_feature &f, const fsh_view &v, uint32_t nx, uint32_t ny)
+// PointZoomBBConverter::X/YFromScreenToCalc (PointZoomBBConverter.cpp:339-354), antialiasing 1
+struct FeatScreen {
+    uint64_t prec;
+    Mp wX, wY, OriginX, OriginY, hwaa, hhaa;
+    explicit FeatScreen(const fsh_view &v)
+        : prec(v.prec_bits), wX(v.maxX - v.minX), wY(v.maxY - v.minY), OriginX(v.prec_bits, 0), OriginY(v.prec_bits, 0),
+          hwaa(v.prec_bits, 0), hhaa(v.prec_bits, 0)
+    {
+        const Mp aa = Mp::from_ui(1), highWidth = Mp::from_ui(v.width), highHeight = Mp::from_ui(v.height);
+        Mp negMinX(v.minX.prec(), 0);
+        mpf_neg(negMinX.v, v.minX.v);
+        mpf_mul(hwaa.v, highWidth.v, aa.v);
+        mpf_div(OriginX.v, hwaa.v, wX.v);
+        mpf_mul(OriginX.v, OriginX.v, negMinX.v);
+        mpf_mul(hhaa.v, highHeight.v, aa.v);
+        mpf_div(OriginY.v, hhaa.v, wY.v);
+        mpf_mul(OriginY.v, OriginY.v, v.maxY.v);
+    }
+    Mp X(uint64_t x) const
+    {
+        Mp px = Mp::from_ui(x), cx(prec, 0);
+        mpf_sub(cx.v, px.v, OriginX.v);
+        mpf_mul(cx.v, cx.v, wX.v);
+        mpf_div(cx.v, cx.v, hwaa.v);
+        return cx;
+    }
+    Mp Y(uint64_t y) const
+    {
+        Mp py = Mp::from_ui(y), cy(prec, 0);
+        mpf_sub(cy.v, py.v, OriginY.v);
+        mpf_neg(cy.v, cy.v);
+        mpf_mul(cy.v, cy.v, wY.v);
+        mpf_div(cy.v, cy.v, hhaa.v);
+        return cy;
+    }
+};
+
+// The scan's screen points (FeatureFinderOrchestrator.cpp:541-548)
+inline uint64_t feat_grid_px(uint64_t extent, uint32_t g, uint32_t n) { return (extent * (2 * (uint64_t)g + 1)) / (2 * (uint64_t)n); }
+
+// `at`: the one screen point of the non-scan mode instead of the nx x ny grid
+template <class F>
+void feature_begin(fsh_feature &f, const fsh_view &v, uint32_t nx, uint32_t ny, const uint64_t *at = nullptr)
 {
     mpf_set_default_prec(v.prec_bits);
     // radiusY = T{MaxY - MinY} / T{2.0f}; HighPrecision radius{radiusY}; radius /= HighPrecision{12}
@@ -3200,37 +3244,22 @@ template <class F> void feature_begin(fsh_feature &f, const fsh_view &v, uint32_
         Mp twelve = Mp::from_ui(12);
         mpf_div(f.radius_hp.v, f.radius_hp.v, twelve.v);
     }
-    // PointZoomBBConverter::X/YFromScreenToCalc (PointZoomBBConverter.cpp:339-354), antialiasing 1
-    const Mp aa = Mp::from_ui(1), highWidth = Mp::from_ui(v.width), highHeight = Mp::from_ui(v.height);
-    Mp wX = v.maxX - v.minX, wY = v.maxY - v.minY;
-    Mp negMinX(v.minX.prec(), 0), OriginX(v.prec_bits, 0), OriginY(v.prec_bits, 0), hwaa(v.prec_bits, 0), hhaa(v.prec_bits, 0);
-    mpf_neg(negMinX.v, v.minX.v);
-    mpf_mul(hwaa.v, highWidth.v, aa.v);
-    mpf_div(OriginX.v, hwaa.v, wX.v);
-    mpf_mul(OriginX.v, OriginX.v, negMinX.v);
-    mpf_mul(hhaa.v, highHeight.v, aa.v);
-    mpf_div(OriginY.v, hhaa.v, wY.v);
-    mpf_mul(OriginY.v, OriginY.v, v.maxY.v);
+    const FeatScreen scr(v);
     auto &cs = cands<F>(f);
-    for (uint32_t gy = 0; gy < ny; ++gy) {
-        const uint64_t y = ((uint64_t)v.height * (2 * gy + 1)) / (2 * (uint64_t)ny);
-        for (uint32_t gx = 0; gx < nx; ++gx) {
-            const uint64_t x = ((uint64_t)v.width * (2 * gx + 1)) / (2 * (uint64_t)nx);
-            FeatCand<F> c;
-            Mp px = Mp::from_ui(x), py = Mp::from_ui(y);
-            c.cx = Mp(v.prec_bits, 0);
-            mpf_sub(c.cx.v, px.v, OriginX.v);
-            mpf_mul(c.cx.v, c.cx.v, wX.v);
-            mpf_div(c.cx.v, c.cx.v, hwaa.v);
-            c.cy = Mp(v.prec_bits, 0);
-            mpf_sub(c.cy.v, py.v, OriginY.v);
-            mpf_neg(c.cy.v, c.cy.v);
-            mpf_mul(c.cy.v, c.cy.v, wY.v);
-            mpf_div(c.cy.v, c.cy.v, hhaa.v);
-            c.grid = gy * nx + gx;
-            cs.push_back(c);
-        }
+    auto add = [&](uint64_t x, uint64_t y, uint32_t grid) {
+        FeatCand<F> c;
+        c.cx = scr.X(x);
+        c.cy = scr.Y(y);
+        c.grid = grid;
+        cs.push_back(c);
+    };
+    if (at) {
+        add(at[0], at[1], 0);
+        return;
     }
+    for (uint32_t gy = 0; gy < ny; ++gy)
+        for (uint32_t gx = 0; gx < nx; ++gx)
+            add(feat_grid_px(v.width, gx, nx), feat_grid_px(v.height, gy, ny), gy * nx + gx);
 }
 
 // FindPeriodicPoint_Common's search radius: R = HdrAbs(T{radius}), SqrRadius = R * R reduced; what PTEvaluator::Eval passes on
@@ -3253,10 +3282,12 @@ template <class F, class In> uint64_t feature_next(fsh_feature &f, In *in, uint6
     for (uint32_t k = 0; k < cs.size(); ++k)
         if (cs[k].stage < kFound && (cs[k].stage == kFind) == any_find && f.batch.size() < cap) {
             FeatCand<F> &c = cs[k];
-            const hcplx<F> dc = ct_from_mp<F>(c.cx - f.hiX, c.cy - f.hiY);
             const hcplx<F> cc = ct_from_mp<F>(c.cx, c.cy);
             In r{};
-            r.dc.re = dc.re, r.dc.im = dc.im, r.dc.e = dc.e;
+            if (!f.direct) {
+                const hcplx<F> dc = ct_from_mp<F>(c.cx - f.hiX, c.cy - f.hiY);
+                r.dc.re = dc.re, r.dc.im = dc.im, r.dc.e = dc.e;
+            }
             r.c.re = cc.re, r.c.im = cc.im, r.c.e = cc.e;
             r.period = c.stage == kFind ? 0 : c.period;
             in[f.batch.size()] = r;
@@ -3373,6 +3404,78 @@ extern "C" fsh_feature *fsh_feature_begin(const fsh_view *v, const fsh_orbit *o,
     else
         feature_begin<float>(*f, *v, nx, ny);
     return f.release();
+}
+
+static fsh_feature *feature_begin_direct(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, const uint64_t *at,
+                                         uint32_t iter_bytes, uint64_t max_iters)
+{
+    if (!v || nx == 0 || ny == 0 || (iter_bytes != 4 && iter_bytes != 8))
+        return nullptr;
+    auto f = std::make_unique<fsh_feature>();
+    f->is64 = is64 != 0;
+    f->iter_bytes = iter_bytes;
+    f->max_iters = max_iters;
+    f->prec_bits = v->prec_bits;
+    f->direct = true;
+    if (f->is64)
+        feature_begin<double>(*f, *v, nx, ny, at);
+    else
+        feature_begin<float>(*f, *v, nx, ny, at);
+    return f.release();
+}
+
+extern "C" fsh_feature *fsh_feature_begin_direct(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, uint32_t iter_bytes,
+                                                 uint64_t max_iters)
+{
+    return feature_begin_direct(v, is64, nx, ny, nullptr, iter_bytes, max_iters);
+}
+
+extern "C" fsh_feature *fsh_feature_begin_direct_at(const fsh_view *v, int is64, uint32_t px, uint32_t py, uint32_t iter_bytes,
+                                                    uint64_t max_iters)
+{
+    const uint64_t at[2] = {px, py};
+    return feature_begin_direct(v, is64, 1, 1, at, iter_bytes, max_iters);
+}
+
+namespace {
+
+template <class F, class In, class Real> void feature_direct_grid(const fsh_view &v, uint32_t nx, uint32_t ny, In *in, Real *radius)
+{
+    mpf_set_default_prec(v.prec_bits);
+    fsh_feature f; // for its search radius only
+    f.prec_bits = v.prec_bits;
+    feature_begin<F>(f, v, 1, 1);
+    const hreal<F> R = feature_eval_radius<F>(f);
+    Real rad{};
+    rad.m = R.m, rad.e = R.e;
+    *radius = rad;
+    // T{cX_hp} per column and T{cY_hp} per row; MakeCTFromHP = C(re, im), reduced, per point
+    const FeatScreen scr(v);
+    std::vector<hreal<F>> re(nx), im(ny);
+    for (uint32_t gx = 0; gx < nx; ++gx)
+        re[gx] = hr_from_mpf<F>(scr.X(feat_grid_px(v.width, gx, nx)).v);
+    for (uint32_t gy = 0; gy < ny; ++gy)
+        im[gy] = hr_from_mpf<F>(scr.Y(feat_grid_px(v.height, gy, ny)).v);
+    for (uint32_t gy = 0; gy < ny; ++gy)
+        for (uint32_t gx = 0; gx < nx; ++gx) {
+            const hcplx<F> cc = hc_reduced(hc_from_hr(re[gx], im[gy]));
+            In r{};
+            r.c.re = cc.re, r.c.im = cc.im, r.c.e = cc.e;
+            in[(size_t)gy * nx + gx] = r;
+        }
+}
+
+} // namespace
+
+extern "C" int fsh_feature_direct_grid(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, void *in, void *radius)
+{
+    if (!v || nx == 0 || ny == 0 || !in || !radius)
+        return -1;
+    if (is64)
+        feature_direct_grid<double>(*v, nx, ny, (fs_feature_in_hdr64 *)in, (fs_real_hdr64 *)radius);
+    else
+        feature_direct_grid<float>(*v, nx, ny, (fs_feature_in_hdr32 *)in, (fs_real_hdr32 *)radius);
+    return 0;
 }
 
 extern "C" void fsh_feature_destroy(fsh_feature *f) { delete f; }

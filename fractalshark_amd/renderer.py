@@ -145,6 +145,15 @@ class GPURenderer:
         T = T_HDR32 / T_HDR64; mode = features.FIND / features.FIXED; radius = R as the raw bytes of an fs_real_hdr32 /
         fs_real_hdr64 (numpy record); records_in / records_out = numpy arrays of features.FEATURE_IN_* / FEATURE_OUT_* records
         (the same length).  Synchronous."""
+        return self._feature_eval(self._lib.fs_feature_eval, T, iter_bytes, mode, radius, max_iters, records_in, records_out)
+
+    def FeatureEvalDirect(self, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
+        """fs_feature_eval_direct: the Feature Finder's Direct evaluator (include/fsmi355.h); the arguments of FeatureEval.  Needs
+        no orbit and no InitializeMemory; reads `c` (and `period` when fixed) of records_in.  Synchronous."""
+        return self._feature_eval(self._lib.fs_feature_eval_direct, T, iter_bytes, mode, radius, max_iters, records_in,
+                                  records_out)
+
+    def _feature_eval(self, entry, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
         from . import features
         din, dout, dreal = features.records(T == T_HDR64)
         n = len(records_in)
@@ -155,8 +164,8 @@ class GPURenderer:
         if len(records_out) < n or not (records_in.flags.c_contiguous and records_out.flags.c_contiguous):
             raise ValueError("records_out must be contiguous and hold at least as many records as records_in")
         radius = np.ascontiguousarray(radius)
-        return self._lib.fs_feature_eval(self._h, int(T), int(iter_bytes), int(mode), radius.ctypes.data, int(max_iters),
-                                         records_in.ctypes.data if n else None, records_out.ctypes.data if n else None, n)
+        return entry(self._h, int(T), int(iter_bytes), int(mode), radius.ctypes.data, int(max_iters),
+                     records_in.ctypes.data if n else None, records_out.ctypes.data if n else None, n)
 
     def InitializePerturbPlain(self, GenerationNumber1, plain, with_la=True):
         """InitializePerturb<IterType, T, T, Disable, T> for a non-HDR T: plain = inputs.PlainInputs (kind f32 -> float,

@@ -231,6 +231,21 @@ void fsh_feature_consume(fsh_feature *f, const void *out, uint64_t n);
 uint64_t fsh_feature_found(const fsh_feature *f);
 int fsh_feature_result(fsh_feature *f, uint64_t k, char *cx, char *cy, char *radius, size_t buflen, uint64_t *period,
                        fs_real_hdr64 *residual2, uint32_t *grid_index);
+/* The Direct / DirectScan modes (FeatureFinderOrchestrator.cpp:485-499, 535-551; FindPeriodicPoint(maxIters, feature) =
+ * FindPeriodicPoint_Common with DirectEvaluator, FeatureFinder.cpp:2356-2362): the same state machine without an orbit.  T =
+ * HDRFloat<double> when is64, else HDRFloat<float>; records carry c = T{cX_hp} + i T{cY_hp} and an all-zero dc; the batches are
+ * the arguments of fs_feature_eval_direct calls.  After begin, next_batch / consume / found / result / destroy as above.
+ * fsh_feature_begin_direct_at: the non-scan Direct mode, one candidate (grid index 0) at screen point (px, py).
+ * Direct sees only what T{cX_hp} separates: in a view narrower than T's mantissa every grid point is the same c. */
+fsh_feature *fsh_feature_begin_direct(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, uint32_t iter_bytes,
+                                      uint64_t max_iters);
+fsh_feature *fsh_feature_begin_direct_at(const fsh_view *v, int is64, uint32_t px, uint32_t py, uint32_t iter_bytes,
+                                         uint64_t max_iters);
+/* The find-round arguments of a DirectScan over an nx x ny grid, without the state machine: in[gy * nx + gx] = the record
+ * fsh_feature_begin_direct's first batch holds for that grid point (high-precision arithmetic once per column and once per row,
+ * not per point), *radius = its R.  in = nx * ny fs_feature_in_hdr32 / _hdr64, radius = fs_real_hdr32 / _hdr64 by is64.
+ * 0, or -1 for bad arguments. */
+int fsh_feature_direct_grid(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, void *in, void *radius);
 
 #ifdef __cplusplus
 }

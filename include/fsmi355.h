@@ -186,6 +186,16 @@ enum { FS_FEATURE_FIND = 0, FS_FEATURE_FIXED = 1, FS_FEATURE_LA = 2 };
 enum { FS_FEATURE_REJECTED = 0, FS_FEATURE_OK = 1, FS_FEATURE_OK_DIRECT = 2 };
 uint32_t fs_feature_eval(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
                          const void *in, void *out, uint64_t n);
+/* FeatureFinder::DirectEvaluator::Eval (FeatureFinder.cpp:2188-2211) for n candidates: FS_FEATURE_FIND = Evaluate_FindPeriod_Direct
+ * (:1576-1660: the trigger |z|^2 < R^2 |dzdc|^2 with the fixed R of the call, cap max_iters), FS_FEATURE_FIXED =
+ * Evaluate_PeriodResidualAndDzdc_Direct at each candidate's period; no fallback.  The records of fs_feature_eval: reads `c` and,
+ * when fixed, `period`; ignores `dc`.  status FS_FEATURE_OK_DIRECT, or FS_FEATURE_REJECTED with an all-zero record.
+ * Needs no resident orbit, no LA table and no fs_init_memory (a renderer fresh from fs_create will do); with a frame and an orbit
+ * present it leaves them, and all frame state named above, as they were.  Synchronous on the compute stream; n = 0 returns 0 and
+ * launches nothing.  FS_ERR_UNSUPPORTED: type tags other than FS_T_HDR32 / FS_T_HDR64, iter_bytes not 4 or 8, a mode other than
+ * FS_FEATURE_FIND / FS_FEATURE_FIXED.  hipErrorInvalidValue: a fixed period that a 4-byte IterType cannot hold. */
+uint32_t fs_feature_eval_direct(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius,
+                                uint64_t max_iters, const void *in, void *out, uint64_t n);
 
 /* BLA table upload (GPU_BLAS ctor, BLA.cuh:123-160); the reference does this inside RenderPerturbBLA. */
 uint32_t fs_upload_bla(fs_renderer *r, int type_tag, const void *const *levels, const uint64_t *level_sizes,

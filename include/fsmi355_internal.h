@@ -91,6 +91,10 @@ uint32_t fs_seq_cursor_probe(fs_renderer *r, int wide_positions, uint64_t start,
 /* The launch order of the most recent frame when it was an ordered one (its first n_tiles words: a permutation of the tile
  * numbers, highest cost class first); 10006 otherwise.  For tests. */
 uint32_t fs_read_tile_order(fs_renderer *r, uint32_t *out, uint64_t max_words);
+/* Test hook: steps per candidate per launch of the Feature Finder evaluators (fs_feature_eval, fs_feature_eval_direct); 0 = the
+ * default, 2^18.  A Direct period search never runs that long, so only a small slice exercises the lane state that is carried
+ * from launch to launch.  Changes no result. */
+uint32_t fs_set_feature_slice(fs_renderer *r, uint32_t steps);
 uint32_t fs_enable_step_count(fs_renderer *r, int enable);
 uint32_t fs_read_step_count(fs_renderer *r, uint64_t counts[8]);
 /* The whole statistics buffer (measurement builds append per-wave trace records behind the 8 counters: library built
