@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -26,6 +27,14 @@
         if (e_ != hipSuccess)                                                                                         \
             return (uint32_t)e_;                                                                                      \
     } while (0)
+
+// A device buffer that only grows: the pointer and the bytes behind it in one place, so that neither outlives the other
+// (buf_reserve / buf_release below, on top of r_alloc / r_free).
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0; // bytes
+    template <class T> T *as() const { return (T *)p; }
+};
 
 struct fs_renderer {
     int device = 0;
@@ -50,8 +59,7 @@ struct fs_renderer {
     uint32_t local_rows = 0, local_rows_padded = 0;
 
     // buffers
-    void *iters_internal = nullptr;
-    size_t iters_internal_bytes = 0;
+    DevBuf iters_internal;
     void *iters_external = nullptr;
     size_t iters_external_bytes = 0;
     fs_reduction reduce_seed{}; // source of the stream-ordered seed copy in fs_render_current (must outlive the call)
@@ -61,13 +69,11 @@ struct fs_renderer {
     size_t stats_words = 40;
 
     uint32_t *queue = nullptr; // pixel counter of the persistent launches (kernels_perturb.hip, k_perturb_scalar)
-    uint32_t *tile_probe = nullptr, *tile_order = nullptr; // "long tiles first" (fs_render_bla): probe counts, launch order
-    size_t tile_probe_cap = 0, tile_order_cap = 0;           // in elements
+    DevBuf tile_probe, tile_order; // "long tiles first" (fs_render_bla): probe counts, launch order (uint32_t each)
     // "longest tiles first" of the tuned LAv2 kernel (fs_render_lav2): the costs the last frame recorded per 8 x 8 tile, the
     // launch order made from them, work memory of the sort; and what the costs belong to (a frame of another geometry, band
     // layout or orbit generation starts cold: natural order, costs recorded)
-    uint32_t *lav2_cost = nullptr, *lav2_order = nullptr, *lav2_sort_tmp = nullptr;
-    size_t lav2_cost_cap = 0, lav2_order_cap = 0; // in elements
+    DevBuf lav2_cost, lav2_order, lav2_sort_tmp; // (uint32_t each)
     bool lav2_cost_valid = false;
     struct CostKey {
         uint32_t width, local_rows, band_first, band_rows, band_stride;
@@ -89,15 +95,10 @@ struct fs_renderer {
     // the order, the sort's work memory, and what the order was made from
     // HDRFloat<double> LAv2: PerformAT in a pass of its own (fsk_at_pass64) with its own pixel order -- its results, the AT
     // iterations every pixel needs by itself (recorded by the first frame of a view), and the order made from them
-    FsAtRes *at_res = nullptr;
-    uint32_t *at_cost = nullptr, *at_order = nullptr;
-    size_t at_cap = 0;
+    DevBuf at_res, at_cost, at_order; // FsAtRes[], uint32_t[], uint32_t[]
     bool at_order_valid = false; // ... for at_key (set where at_order is built: the order is a permutation of THAT key's buffer)
-    uint32_t *pix_cost = nullptr; // per-pixel cost the unordered frame of a view records; what the order is sorted by
-    size_t pix_cost_cap = 0;
-    uint32_t *pix_order = nullptr, *pix_work = nullptr;
-    void *pix_temp = nullptr;
-    size_t pix_cap = 0, pix_temp_bytes = 0;
+    DevBuf pix_cost; // per-pixel cost the unordered frame of a view records; what the order is sorted by
+    DevBuf pix_order, pix_work, pix_temp;
     bool pix_valid = false;
     bool pix_seen = false; // the last unordered frame's key (pix_seen_key): an order is only made for a view that comes twice
     struct PixKey {
@@ -108,10 +109,7 @@ struct fs_renderer {
         bool operator==(const PixKey &o) const { return memcmp(this, &o, sizeof(*this)) == 0; }
     } pix_key{}, pix_seen_key{}, at_key{};
     // (round 6) an order for a view's FIRST frame: tiles by a sampled PerformAT count (kernels_tile_sample.hip)
-    uint32_t *cold_cost = nullptr, *cold_order = nullptr, *cold_work = nullptr;
-    void *cold_temp = nullptr;
-    size_t cold_temp_bytes = 0;
-    uint32_t cold_cap = 0;
+    DevBuf cold_cost, cold_order, cold_work, cold_temp;
     bool last_cold_ordered = false; // (fs_last_frame_sampled_tile_order)
     bool lav2_last_ordered = false; // the last launch was an HDRFloat<float> frame in its recorded TILE order (fs_read_tile_order)
     bool last_launch_wide = false;   // the last render launched a 64-bit counting kernel: those carry no step counters
@@ -161,8 +159,8 @@ struct fs_renderer {
     uint64_t la_gen = 0;
     bool la_ok = false;
     int la_type = -1;
-    void *las = nullptr; // fs_la_hdr32_u32[] or fs_la_hdr64_u32[]
-    fs_la_stage_u32 *stages = nullptr;
+    DevBuf las;    // fs_la_hdr32_u32[] or fs_la_hdr64_u32[]; reused by the next table when it fits
+    DevBuf stages; // fs_la_stage_u32[]
     uint32_t n_las = 0, n_stages = 0;
     int la_valid = 0, use_at = 0;
     bool la_u64 = false;     // `las` holds the reference's uint64_t records (only the waypoint-resident wide kernel reads them)
@@ -179,8 +177,7 @@ struct fs_renderer {
     int32_t bla_n_levels = 0, bla_lm2 = 0;
 
     // direct kernels
-    void *cx_row = nullptr; // double[] / hreal<float>[] / hreal<double>[] (16 B per column is enough for all)
-    uint32_t cx_row_cap = 0;
+    DevBuf cx_row; // double[] / hreal<float>[] / hreal<double>[] (16 B per column is enough for all)
 
     // memory management (r_alloc / r_free below)
     std::vector<void *> host_allocs; // input tables that live in page-locked HOST memory (device out of memory)
@@ -195,28 +192,23 @@ struct fs_renderer {
     size_t host_alloc_bytes = 0;
     uint32_t feature_slice = 0;      // fs_set_feature_slice (tests): steps per launch of the Feature Finder evaluators, 0 = default
     bool inject_input_oom = false;   // fault injection: FSMI355_FAIL_INPUT_ALLOC=1 at fs_create time
-    void *arena = nullptr;           // work memory of fs_build_la (kept between calls, grown on demand)
+    DevBuf arena;                    // work memory of fs_build_la (kept between calls, grown on demand)
     uint32_t *la_mail = nullptr;     // 32 words of coherent page-locked memory the build's kernels report through (k_la_mail)
     uint32_t la_mail_seq = 0;
-    size_t arena_cap = 0;
-    void *bla_block = nullptr;       // ONE allocation for the BLA table: the level pointer table, then the levels
-    size_t bla_block_cap = 0;
-    size_t las_cap = 0, stages_cap = 0; // bytes behind `las` / `stages` (reused by the next table when they fit)
+    DevBuf bla_block;                // ONE allocation for the BLA table: the level pointer table, then the levels
     // device-native form of an HDRFloat<float> BLA table (FsBlaRec + ladder, kernels.h): [flag word | records | ladder]
-    void *bla_native = nullptr;
-    size_t bla_native_cap = 0;
+    DevBuf bla_native;
     bool bla_native_ok = false;
     bool bla_native_stale = false; // table or orbit changed since the native form was made: remade by the next BLA render
     uint32_t bla_native_total = 0;
     // the heap-numbered copy the hand-written kernel reads (kernels_bla_fast.hip), made with the native form
-    void *bla_heap = nullptr;
-    size_t bla_heap_cap = 0;
+    DevBuf bla_heap;
     bool bla_heap_ok = false;
     uint64_t bla_heap_positions = 0;
     uint32_t bla_heap_nq = 0;
     uint32_t bla_level_off[kBlaMaxLevels] = {0};
 
-    void *iters() const { return iters_external ? iters_external : iters_internal; }
+    void *iters() const { return iters_external ? iters_external : iters_internal.p; }
     bool memory_initialized() const { return iters() != nullptr && width != 0; }
 };
 
@@ -379,43 +371,70 @@ hipError_t r_free(fs_renderer *r, const void *cp)
     return hipFree(p); // (not one of ours: allocated before the compute stream existed, or by the stream-ordered path)
 }
 
+// Frees a block and forgets it in the same breath.
+template <class T> hipError_t r_release(fs_renderer *r, T *&p)
+{
+    const hipError_t e = r_free(r, p);
+    p = nullptr;
+    return e;
+}
+
+void buf_release(fs_renderer *r, DevBuf &b)
+{
+    (void)r_free(r, b.p);
+    b = DevBuf{};
+}
+
+// At least `bytes` behind every buffer of a group that lives and dies together (the sort's order / work / temp, ...).  When
+// one of them is too small ALL are freed, then allocated again in the order given; a failed allocation leaves the whole
+// group released and is returned -- whether that is an error or "run without it" is the caller's decision (the sticky
+// error is still the caller's to clear).  *valid, when given, describes contents that index the group (a recorded order):
+// it is cleared whenever the buffers are replaced.
+struct BufWant {
+    DevBuf *buf;
+    size_t bytes;
+};
+hipError_t buf_reserve(fs_renderer *r, std::initializer_list<BufWant> group, AllocKind kind, bool *valid = nullptr)
+{
+    bool fits = true;
+    for (const BufWant &w : group)
+        fits = fits && w.buf->p && w.buf->cap >= w.bytes;
+    if (fits)
+        return hipSuccess;
+    if (valid)
+        *valid = false;
+    for (const BufWant &w : group)
+        buf_release(r, *w.buf);
+    for (const BufWant &w : group) {
+        const hipError_t e = r_alloc(r, &w.buf->p, w.bytes, kind);
+        if (e != hipSuccess) {
+            w.buf->p = nullptr;
+            for (const BufWant &u : group)
+                buf_release(r, *u.buf);
+            return e;
+        }
+        w.buf->cap = w.bytes ? w.bytes : 16; // (what r_alloc hands out for a request of zero)
+    }
+    return hipSuccess;
+}
+hipError_t buf_reserve(fs_renderer *r, DevBuf &b, size_t bytes, AllocKind kind, bool *valid = nullptr)
+{
+    return buf_reserve(r, {BufWant{&b, bytes}}, kind, valid);
+}
+
 // The installed LA table (records + stages): the buffers of the previous table are kept when the new one fits.
 hipError_t la_reserve(fs_renderer *r, size_t las_bytes, size_t stages_bytes)
 {
-    if (!r->las || r->las_cap < las_bytes) {
-        (void)r_free(r, r->las);
-        r->las = nullptr;
-        r->las_cap = 0;
-        hipError_t e = r_alloc(r, &r->las, las_bytes, kInput);
-        if (e != hipSuccess)
-            return e;
-        r->las_cap = las_bytes ? las_bytes : 16;
-    }
-    if (!r->stages || r->stages_cap < stages_bytes) {
-        (void)r_free(r, r->stages);
-        r->stages = nullptr;
-        r->stages_cap = 0;
-        hipError_t e = r_alloc(r, (void **)&r->stages, stages_bytes, kInput);
-        if (e != hipSuccess)
-            return e;
-        r->stages_cap = stages_bytes ? stages_bytes : 16;
-    }
-    return hipSuccess;
+    const hipError_t e = buf_reserve(r, r->las, las_bytes, kInput);
+    return e != hipSuccess ? e : buf_reserve(r, r->stages, stages_bytes, kInput);
 }
 
 // Work memory that outlives a call: grown, never shrunk, handed out from the start on every use.
 hipError_t arena_reserve(fs_renderer *r, size_t bytes)
 {
-    if (r->arena_cap >= bytes)
+    if (r->arena.cap >= bytes)
         return hipSuccess;
-    (void)r_free(r, r->arena);
-    r->arena = nullptr;
-    r->arena_cap = 0;
-    const size_t want = bytes + bytes / 4; // some slack: the next orbit of a zoom sequence is usually a little longer
-    hipError_t e = r_alloc(r, &r->arena, want, kInput);
-    if (e == hipSuccess)
-        r->arena_cap = want;
-    return e;
+    return buf_reserve(r, r->arena, bytes + bytes / 4, kInput); // some slack: the next orbit of a zoom sequence is usually a little longer
 }
 
 void compute_local_rows(fs_renderer *r)
@@ -470,10 +489,7 @@ constexpr uint64_t quiet_orbit_units(uint64_t n)
 // zq: the tuned LAv2 loop's view of the prepared orbit (same length incl. the two spare entries)
 hipError_t make_quiet_orbit(fs_renderer *r, uint64_t n)
 {
-    if (r->zq) {
-        (void)r_free(r, r->zq);
-        r->zq = nullptr;
-    }
+    (void)r_release(r, r->zq);
     // two companions back to back; the scaled runs request their entries one 8-entry body ahead, so the second one may be
     // read up to 16 entries past its end (never used)
     // ... followed by the compact form the 16-step body of the untested loop reads: 2Z alone (8 B per entry) and, per entry, the
@@ -500,17 +516,11 @@ uint32_t ensure_iter_buffer(fs_renderer *r)
     const size_t need = (size_t)r->w_block * 16u * r->local_rows_padded * r->iter_bytes;
     if (r->iters_external)
         return r->iters_external_bytes >= need ? 0 : (uint32_t)hipErrorInvalidValue; // never write past a caller's buffer
-    if (r->iters_internal && r->iters_internal_bytes >= need)
+    if (r->iters_internal.p && r->iters_internal.cap >= need)
         return 0;
-    if (r->iters_internal) {
-        if (r->display)
-            FS_TRY(hipStreamSynchronize(r->display)); // a progressive RenderCurrent may still be reading it
-        FS_TRY(r_free(r, r->iters_internal));
-        r->iters_internal = nullptr;
-        r->iters_internal_bytes = 0;
-    }
-    FS_TRY(r_alloc(r, &r->iters_internal, need, kFrame));
-    r->iters_internal_bytes = need;
+    if (r->iters_internal.p && r->display)
+        FS_TRY(hipStreamSynchronize(r->display)); // a progressive RenderCurrent may still be reading it
+    FS_TRY(buf_reserve(r, r->iters_internal, need, kFrame));
     if (r->compute)
         FS_TRY(hipStreamSynchronize(r->compute)); // usable from any stream from here on
     return 0;
@@ -523,17 +533,10 @@ constexpr size_t kBlaPtrTableBytes = 64 * sizeof(void *);
 
 void bla_release(fs_renderer *r)
 {
-    (void)r_free(r, r->bla_native);
-    r->bla_native = nullptr;
-    r->bla_native_cap = 0;
-    r->bla_native_ok = false;
-    (void)r_free(r, r->bla_heap);
-    r->bla_heap = nullptr;
-    r->bla_heap_cap = 0;
-    r->bla_heap_ok = false;
-    (void)r_free(r, r->bla_block);
-    r->bla_block = nullptr;
-    r->bla_block_cap = 0;
+    buf_release(r, r->bla_native);
+    buf_release(r, r->bla_heap);
+    buf_release(r, r->bla_block);
+    r->bla_native_ok = r->bla_heap_ok = false;
     r->bla_level_mem.clear();
     r->bla_level_sizes.clear();
     r->bla_levels_dev = nullptr;
@@ -550,12 +553,11 @@ hipError_t bla_layout(fs_renderer *r, const uint64_t *sizes, int32_t n_levels, s
     for (int32_t l = 0; l < n_levels; l++)
         total += (sizes[l] * rec_bytes + 255u) & ~(size_t)255u;
     r->bla_n_levels = 0;
-    if (!r->bla_block || r->bla_block_cap < total) {
-        bla_release(r);
-        hipError_t e = r_alloc(r, &r->bla_block, total, kInput);
+    if (!r->bla_block.p || r->bla_block.cap < total) {
+        bla_release(r); // (the native forms were made from the table that goes)
+        const hipError_t e = buf_reserve(r, r->bla_block, total, kInput);
         if (e != hipSuccess)
             return e;
-        r->bla_block_cap = total;
     }
     r->bla_level_mem.assign((size_t)n_levels, nullptr);
     r->bla_level_sizes.assign((size_t)n_levels, 0);
@@ -563,12 +565,12 @@ hipError_t bla_layout(fs_renderer *r, const uint64_t *sizes, int32_t n_levels, s
     for (int32_t l = 0; l < n_levels; l++) {
         if (sizes[l] == 0)
             continue;
-        r->bla_level_mem[(size_t)l] = (char *)r->bla_block + at;
+        r->bla_level_mem[(size_t)l] = r->bla_block.as<char>() + at;
         r->bla_level_sizes[(size_t)l] = sizes[l];
         at += (sizes[l] * rec_bytes + 255u) & ~(size_t)255u;
     }
-    r->bla_levels_dev = (const void **)r->bla_block;
-    return hipMemcpyAsync(r->bla_block, r->bla_level_mem.data(), sizeof(void *) * (size_t)n_levels, hipMemcpyHostToDevice,
+    r->bla_levels_dev = (const void **)r->bla_block.p;
+    return hipMemcpyAsync(r->bla_block.p, r->bla_level_mem.data(), sizeof(void *) * (size_t)n_levels, hipMemcpyHostToDevice,
                           r->compute);
 }
 
@@ -593,18 +595,12 @@ uint32_t bla_make_native(fs_renderer *r, int32_t n_levels)
     // (+ the lookup's pre-test keys, one per orbit index 4 q + 1)
     const uint32_t n_kmax = (uint32_t)(r->orbit_uncompressed / 4u) + 2u;
     const size_t need = 256 + (size_t)total * (sizeof(FsBlaRec) + 2 * sizeof(int4)) + (size_t)n_kmax * sizeof(long long);
-    if (!r->bla_native || r->bla_native_cap < need) {
-        (void)r_free(r, r->bla_native);
-        r->bla_native = nullptr;
-        r->bla_native_cap = 0;
-        if (r_alloc(r, &r->bla_native, need, kInput) != hipSuccess) {
-            (void)hipGetLastError();
-            return 0; // not an error: the reference-layout table serves
-        }
-        r->bla_native_cap = need;
+    if (buf_reserve(r, r->bla_native, need, kInput) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0; // not an error: the reference-layout table serves
     }
-    uint32_t *bad = (uint32_t *)r->bla_native;
-    FsBlaRec *rec = (FsBlaRec *)((char *)r->bla_native + 256);
+    uint32_t *bad = r->bla_native.as<uint32_t>();
+    FsBlaRec *rec = (FsBlaRec *)(r->bla_native.as<char>() + 256);
     int4 *lad = (int4 *)((char *)rec + (size_t)total * sizeof(FsBlaRec));
     FS_TRY(hipMemsetAsync(bad, 0, 256, r->compute));
     fsk_bla_make_native((const fs_bla_hdr32 *const *)r->bla_levels_dev, r->bla_level_off, r->bla_level_sizes.data(), n_levels,
@@ -623,18 +619,12 @@ uint32_t bla_make_native(fs_renderer *r, int32_t n_levels)
     if (r->bla_native_ok && hn != 0 && r->orbit_uncompressed < 0x00FFFFF0ull) {
         const size_t nz = (size_t)r->orbit_uncompressed + 2u;
         const size_t hneed = (size_t)hn * (sizeof(FsBlaRec) + 2 * sizeof(int4)) + (size_t)n_kmax * 3 * sizeof(int4) + nz * sizeof(float4);
-        if (!r->bla_heap || r->bla_heap_cap < hneed) {
-            (void)r_free(r, r->bla_heap);
-            r->bla_heap = nullptr;
-            r->bla_heap_cap = 0;
-            if (r_alloc(r, &r->bla_heap, hneed, kInput) != hipSuccess) {
-                (void)hipGetLastError();
-                return 0;
-            }
-            r->bla_heap_cap = hneed;
+        if (buf_reserve(r, r->bla_heap, hneed, kInput) != hipSuccess) {
+            (void)hipGetLastError();
+            return 0;
         }
-        FS_TRY(hipMemsetAsync(r->bla_heap, 0, hneed, r->compute));
-        FsBlaRec *hrec = (FsBlaRec *)r->bla_heap;
+        FS_TRY(hipMemsetAsync(r->bla_heap.p, 0, hneed, r->compute));
+        FsBlaRec *hrec = r->bla_heap.as<FsBlaRec>();
         int4 *hlad = (int4 *)(hrec + hn);
         int4 *hq = hlad + 2 * (size_t)hn;
         float4 *zb = (float4 *)(hq + 3 * (size_t)n_kmax);
@@ -660,49 +650,26 @@ void orbit_changed(fs_renderer *r)
 // The compressed-resident form of the orbit (runtime decompression) goes whenever another orbit is about to come in.
 void drop_seq(fs_renderer *r)
 {
-    (void)r_free(r, r->wp_raw);
-    r->wp_raw = nullptr;
+    (void)r_release(r, r->wp_raw);
     r->orbit_seq = false;
 }
 
 void free_perturb(fs_renderer *r)
 {
-    if (r->zref)
-        r_free(r, r->zref);
-    if (r->zq)
-        r_free(r, r->zq);
-    r->zq = nullptr;
-    if (r->zref64)
-        r_free(r, r->zref64);
+    (void)r_release(r, r->zref);
+    (void)r_release(r, r->zq);
+    (void)r_release(r, r->zref64);
     drop_seq(r);
-    if (r->orbit_f64)
-        r_free(r, r->orbit_f64);
-    if (r->orbit_plain)
-        r_free(r, r->orbit_plain);
-    r->orbit_plain = nullptr;
-    if (r->orbit_2x32)
-        r_free(r, r->orbit_2x32);
-    r->orbit_2x32 = nullptr;
-    if (r->scaled_t)
-        r_free(r, r->scaled_t);
-    if (r->scaled_f)
-        r_free(r, r->scaled_f);
-    r->scaled_t = nullptr;
-    r->scaled_f = nullptr;
+    (void)r_release(r, r->orbit_f64);
+    (void)r_release(r, r->orbit_plain);
+    (void)r_release(r, r->orbit_2x32);
+    (void)r_release(r, r->scaled_t);
+    (void)r_release(r, r->scaled_f);
     r->scaled_count = 0;
-    r->zref = nullptr;
-    r->zref64 = nullptr;
-    r->orbit_f64 = nullptr;
     r->orbit_ok = false;
-    drop_seq(r);
     r->orbit_gen = 0;
-    if (r->las)
-        r_free(r, r->las);
-    if (r->stages)
-        r_free(r, r->stages);
-    r->las = nullptr;
-    r->stages = nullptr;
-    r->las_cap = r->stages_cap = 0;
+    buf_release(r, r->las);
+    buf_release(r, r->stages);
     r->la_ok = false;
     r->la_gen = 0;
     bla_release(r);
@@ -711,71 +678,28 @@ void free_perturb(fs_renderer *r)
 void free_all(fs_renderer *r)
 {
     free_perturb(r);
-    if (r->iters_internal)
-        r_free(r, r->iters_internal);
-    if (r->colors)
-        r_free(r, r->colors);
-    if (r->reduction)
-        r_free(r, r->reduction);
-    if (r->stats)
-        r_free(r, r->stats);
-    if (r->queue)
-        r_free(r, r->queue);
-    r->queue = nullptr;
-    if (r->tile_probe)
-        r_free(r, r->tile_probe);
-    if (r->tile_order)
-        r_free(r, r->tile_order);
-    r->tile_probe = r->tile_order = nullptr;
-    r->tile_probe_cap = r->tile_order_cap = 0;
-    (void)r_free(r, r->lav2_cost);
-    (void)r_free(r, r->lav2_order);
-    (void)r_free(r, r->lav2_sort_tmp);
-    (void)r_free(r, r->pix_cost);
-    r->pix_cost = nullptr;
-    r->pix_cost_cap = 0;
-    (void)r_free(r, r->at_res);
-    (void)r_free(r, r->at_cost);
-    (void)r_free(r, r->at_order);
-    r->at_res = nullptr;
-    r->at_cost = r->at_order = nullptr;
-    r->at_cap = 0;
-    r->at_order_valid = false;
-    (void)r_free(r, r->pix_order);
-    (void)r_free(r, r->pix_work);
-    (void)r_free(r, r->pix_temp);
-    r->pix_order = r->pix_work = nullptr;
-    r->pix_temp = nullptr;
-    r->pix_cap = 0;
-    r->pix_valid = false;
-    (void)r_free(r, r->cold_cost);
-    (void)r_free(r, r->cold_order);
-    (void)r_free(r, r->cold_work);
-    (void)r_free(r, r->cold_temp);
-    r->cold_cost = r->cold_order = r->cold_work = nullptr;
-    r->cold_temp = nullptr;
-    r->cold_cap = 0;
-    r->lav2_cost = r->lav2_order = r->lav2_sort_tmp = nullptr;
-    r->lav2_cost_cap = r->lav2_order_cap = 0;
-    r->lav2_cost_valid = false;
-    r->po_order_valid = false;
-
-    if (r->pal)
-        r_free(r, r->pal);
-    if (r->cx_row)
-        r_free(r, r->cx_row);
-    (void)r_free(r, r->arena);
-    r->arena = nullptr;
+    buf_release(r, r->iters_internal);
+    (void)r_release(r, r->colors);
+    (void)r_release(r, r->reduction);
+    (void)r_release(r, r->stats);
+    (void)r_release(r, r->queue);
+    for (DevBuf *b : {&r->tile_probe, &r->tile_order, &r->lav2_cost, &r->lav2_order, &r->lav2_sort_tmp, &r->pix_cost, &r->at_res,
+                      &r->at_cost, &r->at_order, &r->pix_order, &r->pix_work, &r->pix_temp, &r->cold_cost, &r->cold_order,
+                      &r->cold_work, &r->cold_temp})
+        buf_release(r, *b);
+    // (a recorded order must not survive the buffer it indexes)
+    r->at_order_valid = r->pix_valid = r->lav2_cost_valid = r->po_order_valid = false;
+    // ... nor the palette's cache key the palette: the next fs_init_memory uploads again, whatever pointer and generation it
+    // is given
+    (void)r_release(r, r->pal);
+    r->pal_cached_host = nullptr;
+    r->pal_cached_gen = 0;
+    r->pal_iters = 0;
+    buf_release(r, r->cx_row);
+    buf_release(r, r->arena);
     if (r->la_mail)
         (void)hipHostFree(r->la_mail);
     r->la_mail = nullptr;
-    r->arena_cap = 0;
-    r->iters_internal = nullptr;
-    r->colors = nullptr;
-    r->reduction = nullptr;
-    r->stats = nullptr;
-    r->pal = nullptr;
-    r->cx_row = nullptr;
     r->width = r->height = 0;
     release_kept_blocks(r);
 }
@@ -832,22 +756,29 @@ static void fill_coords(FsCoordsT<double> &c, const void *coords)
     c.centerY = fs::hreal64{p[3].m, p[3].e};
 }
 
-template <class F> static void fill_lav2(fs_renderer *r, FsLav2ArgsT<F> &A, const void *coords, uint64_t n_iterations, int parity)
+// What every launch-argument block of kernels.h starts with: the iteration buffer, the statistics words, the frame, and the
+// iteration cap in two halves -- a cap of 2^32 and more selects the 64-bit counting instantiation of the kernel.
+template <class Args> static void init_args(fs_renderer *r, Args &A, uint64_t n_iterations)
 {
     memset(&A, 0, sizeof(A));
     A.out = (uint32_t *)r->iters();
-    A.las = (const typename FsDev<F>::LA *)r->las;
-    A.stages = r->stages;
     A.stats = r->stats;
     A.frame = make_frame(r);
+    A.n_iterations = (uint32_t)n_iterations;
+    A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
+    A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
+    r->last_launch_wide = A.frame.wide != 0u;
+}
+
+template <class F> static void fill_lav2(fs_renderer *r, FsLav2ArgsT<F> &A, const void *coords, uint64_t n_iterations, int parity)
+{
+    init_args(r, A, n_iterations);
+    A.las = r->las.as<const typename FsDev<F>::LA>();
+    A.stages = r->stages.as<fs_la_stage_u32>();
     fill_coords(A.coords, coords);
     A.orbit_count = (uint32_t)r->orbit_uncompressed;
     A.period = (uint32_t)r->orbit_period;
     A.stage_count = r->n_stages;
-    A.n_iterations = (uint32_t)n_iterations;
-    A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
     A.la_valid = r->la_ok ? r->la_valid : 0;
     A.use_at = r->use_at;
     A.parity = (parity == FS_PARITY_CPU_GPUSTAGE) ? FS_PARITY_GPUSTAGE : FS_PARITY_LITERAL;
@@ -856,7 +787,6 @@ template <class F> static void fill_lav2(fs_renderer *r, FsLav2ArgsT<F> &A, cons
     A.at_step_hi = r->at_step_hi;
     A.la_u64 = r->la_u64 ? 1u : 0u;
 }
-
 
 // uint64_t IterType tables (fs_la_*_u64 / fs_la_stage_u64 / fs_at_*_u64) are narrowed to the uint32_t device records.
 template <class R64, class R32> static bool narrow_la(const void *in, uint32_t n, std::vector<uint8_t> &out)
@@ -1129,8 +1059,7 @@ uint32_t fs_init_memory(fs_renderer *r, uint32_t w, uint32_t h, uint32_t antiali
             // block where the r_alloc below finds it again: the display stream must have drained before the block is reused
             // (hipFree used to synchronise the whole device here)
             FS_TRY(hipStreamSynchronize(r->display));
-            FS_TRY(r_free(r, r->pal));
-            r->pal = nullptr;
+            FS_TRY(r_release(r, r->pal));
         }
         FS_TRY(r_alloc(r, (void **)&r->pal, sizeof(fs_color16) * (size_t)pal_iters, kFrame));
         FS_TRY(hipMemcpyAsync(r->pal, pal_interleaved, sizeof(fs_color16) * (size_t)pal_iters, hipMemcpyDefault,
@@ -1172,13 +1101,11 @@ uint32_t fs_init_memory(fs_renderer *r, uint32_t w, uint32_t h, uint32_t antiali
     FS_TRY(hipStreamSynchronize(r->display));
     free_perturb(r);
     if (uint32_t e = ensure_iter_buffer(r)) {
+        (void)hipGetLastError(); // reported by this return value, not by the launch check of a later frame
         free_all(r);
         return e;
     }
-    if (r->colors) {
-        r_free(r, r->colors);
-        r->colors = nullptr;
-    }
+    (void)r_release(r, r->colors);
     if (!r->reduction)
         FS_TRY(r_alloc(r, (void **)&r->reduction, sizeof(fs_reduction), kFrame));
     if (!r->stats) {
@@ -1316,13 +1243,58 @@ static uint64_t orbit_fingerprint(const void *entries, uint64_t bytes, uint64_t 
     return h != 0ull ? h : 1ull;
 }
 
-// called where an upload has replaced the resident orbit
-static void bump_orbit_epoch(fs_renderer *r)
+// The slot of an orbit that the kernels read in the layout of the upload (plain float / CudaDblflt, double,
+// HDRFloat<CudaDblflt>) and the size of its records.
+static void **as_uploaded_slot(fs_renderer *r, int type_tag, size_t *rec_bytes)
 {
+    switch (type_tag) {
+    case FS_T_F32: // GPUReferenceIter<float,Disable> (8 B)
+        *rec_bytes = sizeof(fs_orbit_f32);
+        return &r->orbit_plain;
+    case FS_T_2X32: // GPUReferenceIter<CudaDblflt,Disable> (16 B)
+        *rec_bytes = sizeof(fs_orbit_p2x32);
+        return &r->orbit_plain;
+    case FS_T_F64:
+        *rec_bytes = sizeof(fs_orbit_f64);
+        return (void **)&r->orbit_f64;
+    default:
+        *rec_bytes = sizeof(fs_orbit_2x32);
+        return (void **)&r->orbit_2x32;
+    }
+}
+
+// Another orbit of this type is about to come in: the slot of ITS type is freed (an orbit of another type stays allocated
+// until free_perturb), and nothing is resident until install_orbit.
+static uint32_t retire_orbit(fs_renderer *r, int type_tag)
+{
+    if (type_tag == FS_T_HDR32 || type_tag == FS_T_HDR64) {
+        FS_TRY(r_release(r, r->zref));
+        FS_TRY(r_release(r, r->zref64));
+    } else {
+        size_t rec_bytes;
+        FS_TRY(r_release(r, *as_uploaded_slot(r, type_tag, &rec_bytes)));
+    }
+    r->orbit_ok = false;
+    drop_seq(r);
+    return 0;
+}
+
+// An upload has replaced the resident orbit.  `seq`: only its waypoints are resident (wp_raw).
+static void install_orbit(fs_renderer *r, uint64_t generation, int type_tag, uint64_t size, uint64_t uncompressed_size,
+                          uint64_t period_maybe_zero, bool seq = false)
+{
+    r->orbit_seq = seq;
+    r->orbit_size = size;
+    r->orbit_uncompressed = uncompressed_size;
+    r->orbit_period = period_maybe_zero;
+    r->orbit_gen = generation;
     if (r->pending_fp == 0ull || r->pending_fp != r->orbit_fp)
         r->orbit_epoch++;
     r->orbit_fp = r->pending_fp;
     r->pending_fp = 0ull;
+    r->orbit_type = type_tag;
+    r->orbit_ok = true;
+    orbit_changed(r);
 }
 
 uint32_t fs_upload_orbit(fs_renderer *r, uint64_t generation, int type_tag, uint32_t iter_bytes, const void *entries,
@@ -1339,75 +1311,19 @@ uint32_t fs_upload_orbit(fs_renderer *r, uint64_t generation, int type_tag, uint
         return FS_ERR_6;
     if (r->orbit_ok && r->orbit_gen == generation && generation != 0 && r->orbit_type == type_tag)
         return 0; // cached by generation number (GPU_Render.cu:440-487)
-    if (type_tag == FS_T_F32 || type_tag == FS_T_2X32) {
-        // GPUReferenceIter<float,Disable> (8 B) / GPUReferenceIter<CudaDblflt,Disable> (16 B), used as uploaded
-        const size_t eb = type_tag == FS_T_F32 ? sizeof(fs_orbit_f32) : sizeof(fs_orbit_p2x32);
-        if (r->orbit_plain) {
-            FS_TRY(r_free(r, r->orbit_plain));
-            r->orbit_plain = nullptr;
-        }
-        r->orbit_ok = false;
-        drop_seq(r);
-        FS_TRY(r_alloc(r, &r->orbit_plain, (orbit_size + 1) * eb, kInput));
-        FS_TRY(hipMemcpyAsync(r->orbit_plain, entries, orbit_size * eb, hipMemcpyDefault, r->compute));
+    if (uint32_t e = retire_orbit(r, type_tag))
+        return e;
+    if (type_tag != FS_T_HDR32 && type_tag != FS_T_HDR64) {
+        // used as uploaded; the plain types get one spare record
+        size_t eb;
+        void **slot = as_uploaded_slot(r, type_tag, &eb);
+        const uint64_t spare = (type_tag == FS_T_F32 || type_tag == FS_T_2X32) ? 1u : 0u;
+        FS_TRY(r_alloc(r, slot, (orbit_size + spare) * eb, kInput));
+        FS_TRY(hipMemcpyAsync(*slot, entries, orbit_size * eb, hipMemcpyDefault, r->compute));
         FS_TRY(hipStreamSynchronize(r->compute));
-        r->orbit_size = orbit_size;
-        r->orbit_uncompressed = uncompressed_size;
-        r->orbit_period = period_maybe_zero;
-        r->orbit_gen = generation, bump_orbit_epoch(r);
-        r->orbit_type = type_tag;
-        r->orbit_ok = true;
-        orbit_changed(r);
+        install_orbit(r, generation, type_tag, orbit_size, uncompressed_size, period_maybe_zero);
         return 0;
     }
-    if (type_tag == FS_T_HDR2X32) {
-        if (r->orbit_2x32) {
-            FS_TRY(r_free(r, r->orbit_2x32));
-            r->orbit_2x32 = nullptr;
-        }
-        r->orbit_ok = false;
-        drop_seq(r);
-        FS_TRY(r_alloc(r, (void **)&r->orbit_2x32, orbit_size * sizeof(fs_orbit_2x32), kInput));
-        FS_TRY(hipMemcpyAsync(r->orbit_2x32, entries, orbit_size * sizeof(fs_orbit_2x32), hipMemcpyDefault, r->compute));
-        FS_TRY(hipStreamSynchronize(r->compute));
-        r->orbit_size = orbit_size;
-        r->orbit_uncompressed = uncompressed_size;
-        r->orbit_period = period_maybe_zero;
-        r->orbit_gen = generation, bump_orbit_epoch(r);
-        r->orbit_type = type_tag;
-        r->orbit_ok = true;
-        orbit_changed(r);
-        return 0;
-    }
-    if (type_tag == FS_T_F64) {
-        if (r->orbit_f64) {
-            FS_TRY(r_free(r, r->orbit_f64));
-            r->orbit_f64 = nullptr;
-        }
-        r->orbit_ok = false;
-        drop_seq(r);
-        FS_TRY(r_alloc(r, (void **)&r->orbit_f64, orbit_size * sizeof(fs_orbit_f64), kInput));
-        FS_TRY(hipMemcpyAsync(r->orbit_f64, entries, orbit_size * sizeof(fs_orbit_f64), hipMemcpyDefault, r->compute));
-        FS_TRY(hipStreamSynchronize(r->compute));
-        r->orbit_size = orbit_size;
-        r->orbit_uncompressed = uncompressed_size;
-        r->orbit_period = period_maybe_zero;
-        r->orbit_gen = generation, bump_orbit_epoch(r);
-        r->orbit_type = type_tag;
-        r->orbit_ok = true;
-        orbit_changed(r);
-        return 0;
-    }
-    if (r->zref) {
-        FS_TRY(r_free(r, r->zref));
-        r->zref = nullptr;
-    }
-    if (r->zref64) {
-        FS_TRY(r_free(r, r->zref64));
-        r->zref64 = nullptr;
-    }
-    r->orbit_ok = false;
-    drop_seq(r);
     const size_t in_bytes = type_tag == FS_T_HDR32 ? sizeof(fs_orbit_hdr32) : sizeof(fs_orbit_hdr64);
     r->pending_fp = orbit_fingerprint(entries, orbit_size * in_bytes, orbit_size, period_maybe_zero, type_tag);
     void *raw = nullptr;
@@ -1435,13 +1351,7 @@ uint32_t fs_upload_orbit(fs_renderer *r, uint64_t generation, int type_tag, uint
     (void)r_free(r, raw);
     if (err != hipSuccess)
         return (uint32_t)err;
-    r->orbit_size = orbit_size;
-    r->orbit_uncompressed = uncompressed_size;
-    r->orbit_period = period_maybe_zero;
-    r->orbit_gen = generation, bump_orbit_epoch(r);
-    r->orbit_type = type_tag;
-    r->orbit_ok = true;
-    orbit_changed(r);
+    install_orbit(r, generation, type_tag, orbit_size, uncompressed_size, period_maybe_zero);
     return 0;
 }
 
@@ -1464,31 +1374,17 @@ uint32_t fs_upload_orbit_compressed(fs_renderer *r, uint64_t generation, int typ
         return FS_ERR_UNSUPPORTED; // (fs_set_compressed_orbit_mode(1) serves such an orbit)
     if (r->orbit_ok && r->orbit_gen == generation && generation != 0 && r->orbit_type == type_tag && r->orbit_seq == want_seq)
         return 0;
+    if (uint32_t e = retire_orbit(r, type_tag))
+        return e;
     if (type_tag != FS_T_HDR32 && type_tag != FS_T_HDR64) {
         // float / double / CudaDblflt / HDRFloat<CudaDblflt>: expanded into the record array the uncompressed upload
         // of that type fills (kernels_decompress.hip)
-        size_t in_b, out_b;
-        void **slot;
-        switch (type_tag) {
-        case FS_T_F32:
-            in_b = sizeof(fs_orbit_f32_rc), out_b = sizeof(fs_orbit_f32), slot = &r->orbit_plain;
-            break;
-        case FS_T_2X32:
-            in_b = sizeof(fs_orbit_p2x32_rc), out_b = sizeof(fs_orbit_p2x32), slot = &r->orbit_plain;
-            break;
-        case FS_T_F64:
-            in_b = sizeof(fs_orbit_f64_rc), out_b = sizeof(fs_orbit_f64), slot = (void **)&r->orbit_f64;
-            break;
-        default:
-            in_b = sizeof(fs_orbit_2x32_rc), out_b = sizeof(fs_orbit_2x32), slot = (void **)&r->orbit_2x32;
-            break;
-        }
-        if (*slot) {
-            FS_TRY(r_free(r, *slot));
-            *slot = nullptr;
-        }
-        r->orbit_ok = false;
-        drop_seq(r);
+        size_t out_b;
+        void **slot = as_uploaded_slot(r, type_tag, &out_b);
+        const size_t in_b = type_tag == FS_T_F32    ? sizeof(fs_orbit_f32_rc)
+                            : type_tag == FS_T_2X32 ? sizeof(fs_orbit_p2x32_rc)
+                            : type_tag == FS_T_F64  ? sizeof(fs_orbit_f64_rc)
+                                                    : sizeof(fs_orbit_2x32_rc);
         if (want_seq) {
             // keep the waypoints, nothing else: k_lav2_plain / k_lav2_2x32 walk them with a cursor per pixel (same values as
             // the expansion below, entry for entry)
@@ -1501,14 +1397,7 @@ uint32_t fs_upload_orbit_compressed(fs_renderer *r, uint64_t generation, int typ
             memset(r->c_low_plain, 0, sizeof(r->c_low_plain));
             memcpy(r->c_low_plain[0], orbit_x_low, low_b);
             memcpy(r->c_low_plain[1], orbit_y_low, low_b);
-            r->orbit_seq = true;
-            r->orbit_size = compressed_size;
-            r->orbit_uncompressed = uncompressed_size;
-            r->orbit_period = period_maybe_zero;
-            r->orbit_gen = generation, bump_orbit_epoch(r);
-            r->orbit_type = type_tag;
-            r->orbit_ok = true;
-            orbit_changed(r);
+            install_orbit(r, generation, type_tag, compressed_size, uncompressed_size, period_maybe_zero, true);
             return 0;
         }
         void *raw = nullptr;
@@ -1528,27 +1417,11 @@ uint32_t fs_upload_orbit_compressed(fs_renderer *r, uint64_t generation, int typ
         (void)r_free(r, raw);
         if (err != hipSuccess)
             return (uint32_t)err;
-        r->orbit_size = compressed_size;
-        r->orbit_uncompressed = uncompressed_size;
-        r->orbit_period = period_maybe_zero;
-        r->orbit_gen = generation, bump_orbit_epoch(r);
-        r->orbit_type = type_tag;
-        r->orbit_ok = true;
-        orbit_changed(r);
+        install_orbit(r, generation, type_tag, compressed_size, uncompressed_size, period_maybe_zero);
         return 0;
     }
-    if (r->zref) {
-        FS_TRY(r_free(r, r->zref));
-        r->zref = nullptr;
-    }
-    if (r->zref64) {
-        FS_TRY(r_free(r, r->zref64));
-        r->zref64 = nullptr;
-    }
-    r->orbit_ok = false;
-    drop_seq(r);
     const size_t in_bytes = type_tag == FS_T_HDR32 ? sizeof(fs_orbit_hdr32_rc) : sizeof(fs_orbit_hdr64_rc);
-    if (r->compressed_mode == 1) {
+    if (want_seq) {
         // keep the waypoints, nothing else: the kernel decompresses as it goes (GPUPerturbSingleResults for
         // PerturbExtras::SimpleCompression uploads exactly this array, Perturb.cuh:51-80)
         if (compressed_size == 0 || compressed_size > 0xFFFFFFFFull)
@@ -1563,14 +1436,7 @@ uint32_t fs_upload_orbit_compressed(fs_renderer *r, uint64_t generation, int typ
             r->c_low64[0] = *(const fs_real_hdr64 *)orbit_x_low;
             r->c_low64[1] = *(const fs_real_hdr64 *)orbit_y_low;
         }
-        r->orbit_seq = true;
-        r->orbit_size = compressed_size;
-        r->orbit_uncompressed = uncompressed_size;
-        r->orbit_period = period_maybe_zero;
-        r->orbit_gen = generation, bump_orbit_epoch(r);
-        r->orbit_type = type_tag;
-        r->orbit_ok = true;
-        orbit_changed(r);
+        install_orbit(r, generation, type_tag, compressed_size, uncompressed_size, period_maybe_zero, true);
         return 0;
     }
     void *raw = nullptr;
@@ -1601,13 +1467,7 @@ uint32_t fs_upload_orbit_compressed(fs_renderer *r, uint64_t generation, int typ
     (void)r_free(r, raw);
     if (err != hipSuccess)
         return (uint32_t)err;
-    r->orbit_size = compressed_size;
-    r->orbit_uncompressed = uncompressed_size;
-    r->orbit_period = period_maybe_zero;
-    r->orbit_gen = generation, bump_orbit_epoch(r);
-    r->orbit_type = type_tag;
-    r->orbit_ok = true;
-    orbit_changed(r);
+    install_orbit(r, generation, type_tag, compressed_size, uncompressed_size, period_maybe_zero);
     return 0;
 }
 
@@ -1693,11 +1553,11 @@ uint32_t fs_upload_la(fs_renderer *r, uint64_t generation, int type_tag, uint32_
     r->la_ok = false;
     FS_TRY(la_reserve(r, (size_t)n_las * la_bytes_up, (size_t)n_stages * sizeof(fs_la_stage_u32)));
     if (n_las)
-        FS_TRY(hipMemcpyAsync(r->las, las, (size_t)n_las * la_bytes_up, hipMemcpyDefault, r->compute));
+        FS_TRY(hipMemcpyAsync(r->las.p, las, (size_t)n_las * la_bytes_up, hipMemcpyDefault, r->compute));
     r->la_u64 = keep_u64;
     r->at_step_hi = at_step_hi;
     if (n_stages)
-        FS_TRY(hipMemcpyAsync(r->stages, stages, (size_t)n_stages * sizeof(fs_la_stage_u32), hipMemcpyDefault,
+        FS_TRY(hipMemcpyAsync(r->stages.p, stages, (size_t)n_stages * sizeof(fs_la_stage_u32), hipMemcpyDefault,
                               r->compute));
     FS_TRY(hipStreamSynchronize(r->compute));
     r->n_las = n_las;
@@ -1884,7 +1744,7 @@ template <class F> uint32_t build_la(fs_renderer *r, const void *max_radius, int
     for (size_t b : sizes)
         total += ArenaCarver::padded(b);
     FS_TRY(arena_reserve(r, total));
-    ArenaCarver carve(r->arena);
+    ArenaCarver carve(r->arena.p);
     ArenaSlice chebv{carve.take<char>(sizes[0])}, mm{carve.take<char>(sizes[1])}, steps{carve.take<char>(sizes[2])},
         pos{carve.take<char>(sizes[3])}, nextA{carve.take<char>(sizes[4])}, nextB{carve.take<char>(sizes[5])},
         nextC{carve.take<char>(sizes[6])}, reach{carve.take<char>(sizes[7])}, rank{carve.take<char>(sizes[8])},
@@ -2228,8 +2088,8 @@ template <class F> uint32_t build_la(fs_renderer *r, const void *max_radius, int
     r->la_ok = false;
     const size_t rec_bytes = sizeof(F) == 4 ? sizeof(fs_la_hdr32_u32) : sizeof(fs_la_hdr64_u32);
     FS_TRY(la_reserve(r, rec_bytes * la_size, sizeof(fs_la_stage_u32) * stage_count));
-    fsk_la_pack(sizeof(F) == 8, d_table, r->las, la_size, s);
-    FS_TRY(hipMemcpyAsync(r->stages, stages.data(), sizeof(fs_la_stage_u32) * stage_count, hipMemcpyHostToDevice, s));
+    fsk_la_pack(sizeof(F) == 8, d_table, r->las.p, la_size, s);
+    FS_TRY(hipMemcpyAsync(r->stages.p, stages.data(), sizeof(fs_la_stage_u32) * stage_count, hipMemcpyHostToDevice, s));
     FS_TRY(hipMemcpyAsync(&at, atbuf.p, sizeof(at), hipMemcpyDeviceToHost, s));
     FS_TRY(hipMemcpyAsync(h, d_small, 4, hipMemcpyDeviceToHost, s));
     FS_TRY(hipStreamSynchronize(s)); // (one round trip for the AT record, its flag, and the host temporaries above)
@@ -2298,9 +2158,9 @@ uint32_t fs_read_la(fs_renderer *r, void *las_out, uint32_t max_las, void *stage
     const size_t rec_bytes = r->la_type == FS_T_HDR32 ? sizeof(fs_la_hdr32_u32) : sizeof(fs_la_hdr64_u32);
     const uint32_t nl = r->n_las < max_las ? r->n_las : max_las, ns = r->n_stages < max_stages ? r->n_stages : max_stages;
     if (las_out && nl)
-        FS_TRY(hipMemcpyAsync(las_out, r->las, rec_bytes * nl, hipMemcpyDeviceToHost, r->compute));
+        FS_TRY(hipMemcpyAsync(las_out, r->las.p, rec_bytes * nl, hipMemcpyDeviceToHost, r->compute));
     if (stages_out && ns)
-        FS_TRY(hipMemcpyAsync(stages_out, r->stages, sizeof(fs_la_stage_u32) * ns, hipMemcpyDeviceToHost, r->compute));
+        FS_TRY(hipMemcpyAsync(stages_out, r->stages.p, sizeof(fs_la_stage_u32) * ns, hipMemcpyDeviceToHost, r->compute));
     FS_TRY(hipStreamSynchronize(r->compute));
     if (at_out) {
         if (r->la_type == FS_T_HDR32)
@@ -2351,9 +2211,12 @@ static fs_renderer::PixKey pix_key_of(fs_renderer *r, const FsFrame &f, int type
     return k;
 }
 
+// elements of the iteration buffer of a frame, padding included
+static uint64_t buffer_elems(const FsFrame &f) { return (uint64_t)f.rounded_width * ((f.local_rows + 7u) & ~7u); }
+
 static bool pix_order_wanted(fs_renderer *r, const FsFrame &f)
 {
-    const uint64_t n = (uint64_t)f.rounded_width * ((f.local_rows + 7u) & ~7u);
+    const uint64_t n = buffer_elems(f);
     // (FSMI355_STATS_KEEP_ORDER=1: a counting launch keeps the recorded order -- tools/c4_arm_probe.py counts what the ORDERED waves do)
     static const bool stats_keep = [] { const char *e = getenv("FSMI355_STATS_KEEP_ORDER"); return e && e[0] == '1'; }();
     return r->iter_bytes == 4 && f.wide == 0u && (!r->stats_on || stats_keep) && n >= kPixOrderMinPixels && n < 0x7FFFFFFFull &&
@@ -2366,7 +2229,7 @@ static const uint32_t *pix_order_for(fs_renderer *r, const FsFrame &f, const fs_
     if (!pix_order_wanted(r, f) || !r->pix_valid || !(r->pix_key == key))
         return nullptr;
     r->last_frame_ordered = true;
-    return r->pix_order;
+    return r->pix_order.as<uint32_t>();
 }
 
 // An order costs a sort (two for HDRFloat<double>) and is worth it only for a view that is rendered again: a viewer that zooms
@@ -2388,51 +2251,13 @@ static uint32_t *pix_cost_for(fs_renderer *r, const FsFrame &f, bool frame_is_or
 {
     if (frame_is_ordered || !pix_order_wanted(r, f))
         return nullptr;
-    const size_t n = (size_t)f.rounded_width * ((f.local_rows + 7u) & ~7u);
-    if (r->pix_cost_cap < n) {
-        (void)r_free(r, r->pix_cost);
-        r->pix_cost = nullptr;
-        r->pix_cost_cap = 0;
-        if (r_alloc(r, (void **)&r->pix_cost, n * sizeof(uint32_t), kFrame) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        r->pix_cost_cap = n;
-    }
-    if (hipMemsetAsync(r->pix_cost, 0, n * sizeof(uint32_t), r->compute) != hipSuccess) {
+    const size_t bytes = (size_t)buffer_elems(f) * sizeof(uint32_t);
+    if (buf_reserve(r, r->pix_cost, bytes, kFrame) != hipSuccess ||
+        hipMemsetAsync(r->pix_cost.p, 0, bytes, r->compute) != hipSuccess) {
         (void)hipGetLastError();
         return nullptr;
     }
-    return r->pix_cost;
-}
-
-// order / work / temp buffers of the pixel sort for n elements; false = no memory (frames keep the tile mapping)
-static bool pix_buffers(fs_renderer *r, uint32_t n)
-{
-    if (r->pix_cap >= n)
-        return true;
-    (void)r_free(r, r->pix_order);
-    (void)r_free(r, r->pix_work);
-    (void)r_free(r, r->pix_temp);
-    r->pix_order = r->pix_work = nullptr;
-    r->pix_temp = nullptr;
-    r->pix_cap = 0;
-    r->pix_valid = false;
-    const size_t tb = fsk_pixel_order_temp_bytes(n);
-    if (r_alloc(r, (void **)&r->pix_order, (size_t)n * sizeof(uint32_t), kFrame) != hipSuccess ||
-        r_alloc(r, (void **)&r->pix_work, (size_t)n * 2 * sizeof(uint32_t), kFrame) != hipSuccess ||
-        r_alloc(r, &r->pix_temp, tb ? tb : 16, kFrame) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)r_free(r, r->pix_order);
-        (void)r_free(r, r->pix_work);
-        (void)r_free(r, r->pix_temp);
-        r->pix_order = r->pix_work = nullptr;
-        r->pix_temp = nullptr;
-        return false;
-    }
-    r->pix_cap = n;
-    r->pix_temp_bytes = tb;
-    return true;
+    return r->pix_cost.as<uint32_t>();
 }
 
 static void pix_order_after(fs_renderer *r, const FsFrame &f, const fs_renderer::PixKey &key, bool frame_was_ordered,
@@ -2440,13 +2265,14 @@ static void pix_order_after(fs_renderer *r, const FsFrame &f, const fs_renderer:
 {
     if (frame_was_ordered || !pix_order_wanted(r, f))
         return; // (an ordered frame's buffer equals the one the order was made from: nothing new to learn)
-    const uint32_t n = f.rounded_width * ((f.local_rows + 7u) & ~7u);
+    const uint32_t n = (uint32_t)buffer_elems(f);
     r->pix_valid = false;
-    if (!pix_buffers(r, n))
-        return;
-    // sorted by the cost the frame recorded (round 5) -- or, without a record, by the counts as before
-    if (fsk_pixel_order_build(cost ? cost : (const uint32_t *)r->iters(), n, r->pix_work, r->pix_order, r->pix_temp, r->pix_temp_bytes,
-                              r->compute) != hipSuccess) {
+    // the order, the sort's work memory and its temporary storage; sorted by the cost the frame recorded (round 5) -- or,
+    // without a record, by the counts as before.  No memory: frames keep the tile mapping.
+    if (buf_reserve(r, {{&r->pix_order, (size_t)n * sizeof(uint32_t)}, {&r->pix_work, (size_t)n * 2 * sizeof(uint32_t)},
+                        {&r->pix_temp, fsk_pixel_order_temp_bytes(n)}}, kFrame, &r->pix_valid) != hipSuccess ||
+        fsk_pixel_order_build(cost ? cost : (const uint32_t *)r->iters(), n, r->pix_work.as<uint32_t>(), r->pix_order.as<uint32_t>(),
+                              r->pix_temp.p, r->pix_temp.cap, r->compute) != hipSuccess) {
         (void)hipGetLastError();
         return;
     }
@@ -2464,41 +2290,22 @@ static const uint32_t *cold_tile_order(fs_renderer *r, FsTileSampleArgs &S)
         return nullptr;
     S.tiles_x = (S.frame.width + 7u) / 8u, S.tiles_y = (S.frame.local_rows + 7u) / 8u;
     S.n_slots = ((S.frame.width + 31u) / 32u) * S.tiles_y * 4u; // waves of the frame's launch (tile_grid: 4 tiles per workgroup)
-    if (r->cold_cap < S.n_slots) {
-        (void)r_free(r, r->cold_cost);
-        (void)r_free(r, r->cold_order);
-        (void)r_free(r, r->cold_work);
-        (void)r_free(r, r->cold_temp);
-        r->cold_cost = r->cold_order = r->cold_work = nullptr;
-        r->cold_temp = nullptr;
-        r->cold_cap = 0;
-        const size_t tb = fsk_pixel_order_temp_bytes(S.n_slots);
-        if (r_alloc(r, (void **)&r->cold_cost, (size_t)S.n_slots * sizeof(uint32_t), kFrame) != hipSuccess ||
-            r_alloc(r, (void **)&r->cold_order, (size_t)S.n_slots * sizeof(uint32_t), kFrame) != hipSuccess ||
-            r_alloc(r, (void **)&r->cold_work, (size_t)S.n_slots * 2 * sizeof(uint32_t), kFrame) != hipSuccess ||
-            r_alloc(r, &r->cold_temp, tb ? tb : 16, kFrame) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)r_free(r, r->cold_cost);
-            (void)r_free(r, r->cold_order);
-            (void)r_free(r, r->cold_work);
-            (void)r_free(r, r->cold_temp);
-            r->cold_cost = r->cold_order = r->cold_work = nullptr;
-            r->cold_temp = nullptr;
-            return nullptr;
-        }
-        r->cold_cap = S.n_slots;
-        r->cold_temp_bytes = tb;
-    }
-    S.cost = r->cold_cost;
-    fsk_at_tile_sample64(S, r->compute);
-    if (fsk_pixel_order_build(r->cold_cost, S.n_slots, r->cold_work, r->cold_order, r->cold_temp, r->cold_temp_bytes, r->compute) !=
-        hipSuccess) {
+    const size_t words = (size_t)S.n_slots * sizeof(uint32_t);
+    if (buf_reserve(r, {{&r->cold_cost, words}, {&r->cold_order, words}, {&r->cold_work, 2 * words},
+                        {&r->cold_temp, fsk_pixel_order_temp_bytes(S.n_slots)}}, kFrame) != hipSuccess) {
         (void)hipGetLastError();
         return nullptr;
     }
-    fsk_tile_order_finish(r->cold_order, S.n_slots, S.tiles_x * S.tiles_y, r->compute);
+    S.cost = r->cold_cost.as<uint32_t>();
+    fsk_at_tile_sample64(S, r->compute);
+    if (fsk_pixel_order_build(S.cost, S.n_slots, r->cold_work.as<uint32_t>(), r->cold_order.as<uint32_t>(), r->cold_temp.p,
+                              r->cold_temp.cap, r->compute) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    fsk_tile_order_finish(r->cold_order.as<uint32_t>(), S.n_slots, S.tiles_x * S.tiles_y, r->compute);
     r->last_cold_ordered = true;
-    return r->cold_order;
+    return r->cold_order.as<uint32_t>();
 }
 
 uint32_t fs_feature_eval(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
@@ -2549,372 +2356,349 @@ uint32_t fs_set_feature_slice(fs_renderer *r, uint32_t steps)
     return 0;
 }
 
+// How every fs_render_* begins.  kNoFrame: return *rc now -- the HIP error of a device that cannot be selected, else 0: there is
+// nothing to render into (no fs_init_memory yet, as GPU_Render.cu:626-628, 1007-1009, 1317-1319; or a renderer that owns no
+// row of the frame, a rank beyond the last band).  kRefused: *rc says what is wrong with the call.
+enum class Begin { kGo, kNoFrame, kRefused };
+
+static Begin render_begin(fs_renderer *r, bool type_ok, uint64_t n_iterations, uint32_t *rc)
+{
+    *rc = use_device(r);
+    if (*rc != 0u || !r->memory_initialized() || r->local_rows == 0)
+        return Begin::kNoFrame;
+    if (!type_ok)
+        *rc = FS_ERR_UNSUPPORTED;
+    else if (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8)
+        *rc = (uint32_t)hipErrorInvalidValue; // a 4-byte IterType cannot hold such a count
+    return *rc != 0u ? Begin::kRefused : Begin::kGo;
+}
+
+static int kernel_mode(int lav2_mode)
+{
+    return lav2_mode == FS_LAV2_FULL ? FS_MODE_FULL : (lav2_mode == FS_LAV2_PO ? FS_MODE_PO : FS_MODE_LAO);
+}
+
+// ---- The launch paths of fs_render_lav2, which validates the call and picks one.
+
+// The orbit is resident as waypoints only (fs_set_compressed_orbit_mode 1): the literal kernel with a sequential
+// decompression cursor per pixel.
+static uint32_t lav2_seq(fs_renderer *r, int type_tag, int mode, int parity, const void *coords, uint64_t n_iterations, bool wide)
+{
+    // 64-bit POSITIONS (and counters) whenever something does not fit 32 bits: the orbit's uncompressed length or period,
+    // a table kept in the uint64_t layout -- besides the iteration cap and the test switch
+    const bool wide_pos = wide || r->la_u64 || r->orbit_uncompressed > 0xFFFFFFFFull || r->orbit_period > 0xFFFFFFFFull;
+    TimedLaunch t(r);
+    if (type_tag == FS_T_HDR32) {
+        FsLav2ArgsT<float> A;
+        fill_lav2<float>(r, A, coords, n_iterations, parity);
+        A.frame.wide |= wide_pos ? 1u : 0u;
+        r->last_launch_wide = A.frame.wide != 0u;
+        A.at = r->at;
+        A.wp = r->wp_raw, A.n_wp = (uint32_t)r->orbit_size;
+        A.cxLow = r->c_low32[0], A.cyLow = r->c_low32[1];
+        fsk_lav2_seq(&A, nullptr, kernel_mode(mode), r->stats_on, r->compute);
+    } else {
+        FsLav2ArgsT<double> A;
+        fill_lav2<double>(r, A, coords, n_iterations, parity);
+        A.frame.wide |= wide_pos ? 1u : 0u;
+        r->last_launch_wide = A.frame.wide != 0u;
+        A.at = r->at64;
+        A.wp = r->wp_raw, A.n_wp = (uint32_t)r->orbit_size;
+        A.cxLow = r->c_low64[0], A.cyLow = r->c_low64[1];
+        fsk_lav2_seq(nullptr, &A, kernel_mode(mode), r->stats_on, r->compute);
+    }
+    return (uint32_t)hipGetLastError();
+}
+
+// the prepared HDRFloat<float> orbit, the companions of the tuned loops and the AT record
+static void set_orbit_hdr32(const fs_renderer *r, FsLav2ArgsT<float> &A)
+{
+    A.zref = r->zref;
+    A.zq = r->zq;
+    A.zs = r->zq + r->zq_n;
+    A.zs2 = r->zs2;
+    A.zqb = r->zqb;
+    A.at = r->at;
+}
+
+// GPURenderer::RenderPerturbLAv2<uint64_t, ...> with a cap the 32-bit counters cannot hold: the literal kernel
+// instantiated with 64-bit counters (all three modes; the reference's arithmetic, operation by operation)
+static uint32_t lav2_wide(fs_renderer *r, int type_tag, int mode, int parity, const void *coords, uint64_t n_iterations)
+{
+    TimedLaunch t(r);
+    if (type_tag == FS_T_HDR32) {
+        FsLav2ArgsT<float> A;
+        fill_lav2<float>(r, A, coords, n_iterations, parity);
+        set_orbit_hdr32(r, A);
+        fsk_lav2_wide(&A, nullptr, kernel_mode(mode), r->stats_on, r->compute);
+    } else {
+        FsLav2ArgsT<double> A;
+        fill_lav2<double>(r, A, coords, n_iterations, parity);
+        A.zref = r->zref64;
+        A.at = r->at64;
+        fsk_lav2_wide(nullptr, &A, kernel_mode(mode), r->stats_on, r->compute);
+    }
+    return (uint32_t)hipGetLastError();
+}
+
+// Gpu1x32 / Gpu1x64 / Gpu2x32 PerturbedLAv2*: no CPU RenderAlgorithm exists for LAv2 on a plain type, the kernel
+// restates the reference's CUDA kernel and ignores `parity`.  coords = float[4] / double[4] / fs_real_p2x32[4].
+static uint32_t lav2_plain(fs_renderer *r, int type_tag, int mode, const void *coords, uint64_t n_iterations)
+{
+    FsLav2ArgsPlain A;
+    init_args(r, A, n_iterations);
+    // (the waypoint-resident instantiations are built without the step counters too: fs_read_step_count must refuse, not
+    // report zeros)
+    r->last_launch_wide = A.frame.wide != 0u || r->orbit_seq;
+    A.las = r->las.p;
+    A.stages = r->stages.as<fs_la_stage_u32>();
+    memcpy(A.coords, coords, type_tag == FS_T_F32 ? 4 * sizeof(float) : 4 * sizeof(double));
+    memcpy(A.at, r->at_plain, sizeof(A.at));
+    A.orbit_count = (uint32_t)r->orbit_uncompressed;
+    A.stage_count = r->n_stages;
+    A.la_valid = (r->la_ok && r->la_type == type_tag) ? r->la_valid : 0;
+    A.use_at = r->use_at;
+    if (r->orbit_seq) { // waypoint-resident orbit: a cursor per pixel (k_lav2_plain<.., kSeq>)
+        A.wp = r->wp_raw;
+        A.n_wp = (uint32_t)r->orbit_size;
+        memcpy(A.c_low[0], r->c_low_plain[0], 8);
+        memcpy(A.c_low[1], r->c_low_plain[1], 8);
+    } else {
+        A.orbit = type_tag == FS_T_F64 ? (const void *)r->orbit_f64 : (const void *)r->orbit_plain;
+    }
+    TimedLaunch t(r);
+    fsk_lav2_plain(A, type_tag == FS_T_F32 ? 0 : (type_tag == FS_T_F64 ? 1 : 2), kernel_mode(mode), r->stats_on, r->compute);
+    return (uint32_t)hipGetLastError();
+}
+
+// HDRFloat<CudaDblflt>.  No CPU RenderAlgorithm exists for this type: the kernel restates the reference's CUDA kernel and
+// ignores `parity` (coords are fs_real_2x32[4]).
+static uint32_t lav2_2x32(fs_renderer *r, int mode, const void *coords, uint64_t n_iterations)
+{
+    FsLav2Args2x32 A;
+    init_args(r, A, n_iterations);
+    r->last_launch_wide = A.frame.wide != 0u || r->orbit_seq; // (kSeq: no counters either)
+    A.las = r->las.as<const fs_la_2x32_u32>();
+    A.stages = r->stages.as<fs_la_stage_u32>();
+    memcpy(A.coords, coords, sizeof(A.coords));
+    A.at = r->at2x32;
+    A.orbit_count = (uint32_t)r->orbit_uncompressed;
+    A.stage_count = r->n_stages;
+    A.la_valid = (r->la_ok && r->la_type == FS_T_HDR2X32) ? r->la_valid : 0;
+    A.use_at = r->use_at;
+    if (r->orbit_seq) { // waypoint-resident orbit: a cursor per pixel (k_lav2_2x32<.., kSeq>)
+        A.wp = (const fs_orbit_2x32_rc *)r->wp_raw;
+        A.n_wp = (uint32_t)r->orbit_size;
+        memcpy(&A.cxLow, r->c_low_plain[0], sizeof(fs_real_2x32));
+        memcpy(&A.cyLow, r->c_low_plain[1], sizeof(fs_real_2x32));
+    } else {
+        A.orbit = r->orbit_2x32;
+    }
+    const fs_renderer::PixKey pk = pix_key_of(r, A.frame, FS_T_HDR2X32, mode, 0, coords, sizeof(A.coords), n_iterations);
+    A.pixel_order = r->orbit_seq ? nullptr : pix_order_for(r, A.frame, pk);
+    const bool second = !r->orbit_seq && A.pixel_order == nullptr && pix_second_sighting(r, A.frame, pk);
+    A.pixel_cost = second ? pix_cost_for(r, A.frame, false) : nullptr;
+    {
+        TimedLaunch t(r);
+        if (!r->orbit_seq && A.pixel_order == nullptr && !second && mode != FS_LAV2_PO && A.use_at && A.la_valid) {
+            // a view's first frame: tiles in the order of a sampled PerformAT count (the record's values in binary64: head + tail, exact)
+            auto R = [](const fs_real_2x32 &x) { return fs::hreal<double>{(double)x.head + (double)x.tail, x.e}; };
+            auto Cx = [](const fs_cplx_2x32 &c) {
+                return fs::hcplx<double>{(double)c.re_head + (double)c.re_tail, (double)c.im_head + (double)c.im_tail, c.e};
+            };
+            FsTileSampleArgs S;
+            memset(&S, 0, sizeof(S));
+            S.frame = A.frame;
+            S.coords = FsCoordsT<double>{R(A.coords[0]), R(A.coords[1]), R(A.coords[2]), R(A.coords[3])};
+            S.ThresholdC = R(A.at.ThresholdC), S.SqrEscapeRadius = R(A.at.SqrEscapeRadius);
+            S.RefC = Cx(A.at.RefC), S.CCoeff = Cx(A.at.CCoeff);
+            S.StepLength = A.at.StepLength, S.n_iterations = A.n_iterations;
+            A.tile_order = cold_tile_order(r, S);
+            A.tiles_x = S.tiles_x;
+        }
+        fsk_lav2_2x32(A, kernel_mode(mode), r->stats_on, r->compute);
+    }
+    if (second)
+        pix_order_after(r, A.frame, pk, false, A.pixel_cost);
+    return (uint32_t)hipGetLastError();
+}
+
+static uint32_t lav2_hdr32(fs_renderer *r, int mode, int parity, const void *coords, uint64_t n_iterations)
+{
+    FsLav2ArgsT<float> A;
+    fill_lav2<float>(r, A, coords, n_iterations, parity);
+    set_orbit_hdr32(r, A);
+    // Longest tiles first, self-recorded.  Every frame of the tuned kernel stores one cost word per 8 x 8 tile (its
+    // longest lane's step count); the NEXT frame of the same geometry, band layout and orbit generation is launched in
+    // descending cost order (64 classes, raster order inside a class).  A frame ends one long wave after its last wave
+    // was dispatched and the waves differ 2.5x in length, so the drain at the end of the launch shrinks from the longest
+    // wave's duration towards the shortest's.  Which wave renders which tile changes no pixel; the first frame (and
+    // every frame after fs_forget_tile_costs, or with FS_VARIANT_NATURAL_TILE_ORDER) runs in natural order.
+    const uint32_t tiles_x = (r->width + 7u) / 8u, tiles_y = (r->local_rows + 7u) / 8u;
+    const uint32_t n_tiles = tiles_x * tiles_y;
+    const uint32_t n_slots = fsk_lav2_hdr32_slots(A.frame);
+    const bool tuned = (r->variant & FS_VARIANT_BASE_MASK) != FS_VARIANT_LITERAL;
+    const bool record = tuned && n_tiles >= kLav2OrderMinTiles && (r->variant & FS_VARIANT_FLAG_NATURAL_ORDER) == 0;
+    if (record) {
+        FS_TRY(buf_reserve(r, {{&r->lav2_cost, (size_t)n_tiles * sizeof(uint32_t)},
+                               {&r->lav2_sort_tmp, (size_t)fsk_tile_order_work_words(n_tiles) * sizeof(uint32_t)}},
+                           kFrame, &r->lav2_cost_valid));
+        FS_TRY(buf_reserve(r, r->lav2_order, ((size_t)n_slots + 1) * sizeof(uint32_t), kFrame));
+        const fs_renderer::CostKey key{r->width, r->local_rows, A.frame.band_first, A.frame.band_rows,
+                                       A.frame.band_stride, r->orbit_gen};
+        A.tile_cost = r->lav2_cost.as<uint32_t>();
+        A.tiles_x = tiles_x;
+        if (r->lav2_cost_valid && r->lav2_cost_key == key)
+            A.tile_order = r->lav2_order.as<uint32_t>();
+        r->lav2_cost_key = key;
+    }
+    if (A.tile_order) {
+        fsk_tile_order_by_cost(A.tile_cost, n_tiles, r->lav2_sort_tmp.as<uint32_t>(), r->lav2_order.as<uint32_t>(), n_slots,
+                               r->compute);
+        r->last_frame_ordered = true;
+        r->lav2_last_ordered = true;
+    }
+    TimedLaunch t(r);
+    fsk_lav2_hdr32(A, kernel_mode(mode), r->stats_on, r->variant, r->compute);
+    r->lav2_cost_valid = record;
+    return (uint32_t)hipGetLastError();
+}
+
+static uint32_t lav2_hdr64(fs_renderer *r, int mode, int parity, const void *coords, uint64_t n_iterations)
+{
+    FsLav2ArgsT<double> A;
+    fill_lav2<double>(r, A, coords, n_iterations, parity);
+    A.zref = r->zref64;
+    A.at = r->at64;
+    const fs_renderer::PixKey pk = pix_key_of(r, A.frame, FS_T_HDR64, mode, parity, coords, 4 * sizeof(fs_real_hdr64), n_iterations);
+    A.pixel_order = pix_order_for(r, A.frame, pk);
+    // PerformAT in a pass of its own, in the order of the AT iterations every pixel needs by itself (recorded by the view's
+    // first frame): the AT loop reads no memory, so its waves can be made of pixels from anywhere -- equal work per wave --
+    // while the frame's kernel keeps the order that keeps neighbours together (below).  A view's first frame has no such pass:
+    // without an order its waves wait for their slowest pixel just as the kernel's do.
+    const bool second = A.pixel_order == nullptr && pix_second_sighting(r, A.frame, pk);
+    bool at_split = mode != FS_LAV2_PO && A.use_at && A.la_valid && pix_order_wanted(r, A.frame) &&
+                    (A.pixel_order != nullptr || second);
+    const uint32_t n_buf = (uint32_t)buffer_elems(A.frame); // (below 2^31 wherever an order is wanted)
+    if (at_split &&
+        buf_reserve(r, {{&r->at_res, n_buf * sizeof(FsAtRes)}, {&r->at_cost, n_buf * sizeof(uint32_t)},
+                        {&r->at_order, n_buf * sizeof(uint32_t)}}, kFrame, &r->at_order_valid) != hipSuccess) {
+        (void)hipGetLastError(); // no memory for it: PerformAT stays inside the frame's kernel
+        at_split = false;
+    }
+    // (the AT order has a key of its own: it is a permutation of the buffer it was recorded on, and pix_order can be rebuilt
+    // -- other row bands, a table without AT in between -- without it)
+    const bool at_warm = at_split && r->at_order_valid && r->at_key == pk;
+    const bool at_record = at_split && !at_warm; // (a view's first frame records nothing: a viewer that zooms never uses it)
+    {
+        TimedLaunch t(r);
+        if (at_split) {
+            FsLav2ArgsT<double> P = A;
+            P.at_res = r->at_res.as<FsAtRes>();
+            P.pixel_order = at_warm ? r->at_order.as<uint32_t>() : nullptr;
+            if (at_record) {
+                P.at_cost = r->at_cost.as<uint32_t>();
+                FS_TRY(hipMemsetAsync(P.at_cost, 0, n_buf * sizeof(uint32_t), r->compute));
+                r->at_order_valid = false;
+            }
+            fsk_at_pass64(P, r->compute);
+            t.mid();
+            A.at_res = P.at_res;
+        }
+        if (A.pixel_order == nullptr && !second && !at_split && mode != FS_LAV2_PO && A.use_at && A.la_valid) {
+            // a view's first frame: tiles in the order of a sampled PerformAT count (kernels_tile_sample.hip)
+            FsTileSampleArgs S;
+            memset(&S, 0, sizeof(S));
+            S.frame = A.frame;
+            S.coords = A.coords;
+            S.ThresholdC = fs::hreal<double>{A.at.ThresholdC.m, A.at.ThresholdC.e};
+            S.SqrEscapeRadius = fs::hreal<double>{A.at.SqrEscapeRadius.m, A.at.SqrEscapeRadius.e};
+            S.RefC = fs::hcplx<double>{A.at.RefC.re, A.at.RefC.im, A.at.RefC.e};
+            S.CCoeff = fs::hcplx<double>{A.at.CCoeff.re, A.at.CCoeff.im, A.at.CCoeff.e};
+            S.StepLength = A.at.StepLength, S.n_iterations = A.n_iterations;
+            A.tile_order = cold_tile_order(r, S);
+            A.tiles_x = S.tiles_x;
+        }
+        // the production kernel (kernels_hdr64.hip); FS_VARIANT_LITERAL keeps the operation-by-operation one for A/B
+        // (k_lav2_hdr64 addresses its records with 32-bit byte offsets: an orbit or a table of 4 GB and more stays with the literal kernel)
+        const bool small = (uint64_t)A.orbit_count * sizeof(FsZ64) < 0xFFFFFF00ull &&
+                           (uint64_t)r->n_las * sizeof(fs_la_hdr64_u32) < 0xFFFFFF00ull;
+        if (!small || (r->variant & FS_VARIANT_BASE_MASK) == FS_VARIANT_LITERAL)
+            fsk_lav2_hdr64(A, kernel_mode(mode), r->stats_on, r->compute);
+        else
+            fsk_lav2_hdr64_fast(A, kernel_mode(mode), r->stats_on, r->compute);
+    }
+    // (sorted by COUNT, not by a recorded cost as the 2x32 frames are: this kernel's steps are cheap enough for the loads of
+    // a wave whose lanes are scattered over the frame to cost more than the idle lanes they save -- 81 ms with the cost as
+    // the key, 68 with its binades, 53 with the counts, which keep the pixels inside the set side by side: DESIGN.md 7)
+    if (second)
+        pix_order_after(r, A.frame, pk, false);
+    if (at_record && r->pix_valid && r->pix_work.cap >= (size_t)n_buf * 2 * sizeof(uint32_t)) {
+        // the AT pass's own order, from the costs it has just recorded (the sort's work memory is the pixel order's)
+        if (fsk_pixel_order_build(r->at_cost.as<uint32_t>(), n_buf, r->pix_work.as<uint32_t>(), r->at_order.as<uint32_t>(),
+                                  r->pix_temp.p, r->pix_temp.cap, r->compute) == hipSuccess) {
+            r->at_order_valid = true;
+            r->at_key = pk;
+        } else
+            (void)hipGetLastError();
+    }
+    return (uint32_t)hipGetLastError();
+}
+
 uint32_t fs_render_lav2(fs_renderer *r, int type_tag, int mode, int parity, const void *coords, uint64_t n_iterations)
 {
-    if (uint32_t e = use_device(r))
-        return e;
-    if (!r->memory_initialized())
-        return 0; // GPU_Render.cu:1007-1009
-    if (r->local_rows == 0)
-        return 0; // this renderer owns no row of the frame (a rank beyond the last band)
+    const bool plain = type_tag == FS_T_F32 || type_tag == FS_T_F64 || type_tag == FS_T_2X32;
+    const bool hdr = type_tag == FS_T_HDR32 || type_tag == FS_T_HDR64;
+    // iteration caps of 2^32 and above need IterType = uint64_t (an 8-byte buffer): every type then runs an instantiation
+    // of its kernel that counts in 64 bits (the literal one for HDRFloat<float|double>)
+    uint32_t rc;
+    const Begin b = render_begin(r, hdr || plain || type_tag == FS_T_HDR2X32, n_iterations, &rc);
+    if (b == Begin::kNoFrame)
+        return rc;
     r->last_frame_ordered = false; // (every path below that uses a recorded order says so itself)
     r->lav2_last_ordered = false;
     r->last_cold_ordered = false;
-    const bool plain = type_tag == FS_T_F32 || type_tag == FS_T_F64 || type_tag == FS_T_2X32;
-    // iteration caps of 2^32 and above need IterType = uint64_t (an 8-byte buffer): every type then runs an instantiation
-    // of its kernel that counts in 64 bits (the literal one for HDRFloat<float|double>)
-    if (type_tag != FS_T_HDR32 && type_tag != FS_T_HDR64 && type_tag != FS_T_HDR2X32 && !plain)
-        return FS_ERR_UNSUPPORTED;
-    if (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8)
-        return (uint32_t)hipErrorInvalidValue; // a 4-byte IterType cannot hold such a count
+    if (b == Begin::kRefused)
+        return rc;
     // (the 64-bit counting kernels can also be forced at small caps: FS_VARIANT_WIDE_COUNTERS, a test switch)
     const bool wide = n_iterations > 0xFFFFFFFFull || (r->variant & FS_VARIANT_FLAG_WIDE) != 0;
     if (!r->orbit_ok || r->orbit_type != type_tag)
         return FS_ERR_6; // GPU_Render.cu:1015-1022
-    if (r->orbit_seq && (type_tag == FS_T_HDR32 || type_tag == FS_T_HDR64)) {
-        // the orbit is resident as waypoints only (fs_set_compressed_orbit_mode 1): the literal kernel with a sequential
-        // decompression cursor per pixel.  Perturbation-only with CPU parity has its twin in the scalar kernel, which reads
-        // an expanded orbit: not served in this mode.
-        if (mode == FS_LAV2_PO && parity == FS_PARITY_CPU)
-            return FS_ERR_UNSUPPORTED;
-        if (mode != FS_LAV2_PO && (!r->la_ok || r->la_type != type_tag))
-            return FS_ERR_6;
-        const int kmode = mode == FS_LAV2_FULL ? FS_MODE_FULL : (mode == FS_LAV2_PO ? FS_MODE_PO : FS_MODE_LAO);
-        // 64-bit POSITIONS (and counters) whenever something does not fit 32 bits: the orbit's uncompressed length or period,
-        // a table kept in the uint64_t layout -- besides the iteration cap and the test switch
-        const bool wide_pos = wide || r->la_u64 || r->orbit_uncompressed > 0xFFFFFFFFull || r->orbit_period > 0xFFFFFFFFull;
-        TimedLaunch t(r);
-        if (type_tag == FS_T_HDR32) {
-            FsLav2ArgsT<float> A;
-            fill_lav2<float>(r, A, coords, n_iterations, parity);
-            A.frame.wide |= wide_pos ? 1u : 0u;
-            r->last_launch_wide = A.frame.wide != 0u;
-            A.at = r->at;
-            A.wp = r->wp_raw, A.n_wp = (uint32_t)r->orbit_size;
-            A.cxLow = r->c_low32[0], A.cyLow = r->c_low32[1];
-            fsk_lav2_seq(&A, nullptr, kmode, r->stats_on, r->compute);
-        } else {
-            FsLav2ArgsT<double> A;
-            fill_lav2<double>(r, A, coords, n_iterations, parity);
-            A.frame.wide |= wide_pos ? 1u : 0u;
-            r->last_launch_wide = A.frame.wide != 0u;
-            A.at = r->at64;
-            A.wp = r->wp_raw, A.n_wp = (uint32_t)r->orbit_size;
-            A.cxLow = r->c_low64[0], A.cyLow = r->c_low64[1];
-            fsk_lav2_seq(nullptr, &A, kmode, r->stats_on, r->compute);
-        }
-        return (uint32_t)hipGetLastError();
+    // Perturbation-only with CPU parity: no dispatched CPU RenderAlgorithm is perturbation-only in HDRFloatComplex arithmetic;
+    // the parity target is the single-step branch of CalcCpuPerturbationFractalBLA, the scalar kernel
+    const bool po_cpu = mode == FS_LAV2_PO && parity == FS_PARITY_CPU;
+    const bool no_table = mode != FS_LAV2_PO && (!r->la_ok || r->la_type != type_tag);
+    if (r->orbit_seq && hdr) {
+        if (po_cpu)
+            return FS_ERR_UNSUPPORTED; // the scalar kernel reads an expanded orbit: not served in this mode
+        return no_table ? FS_ERR_6 : lav2_seq(r, type_tag, mode, parity, coords, n_iterations, wide);
     }
     if (r->la_u64 && mode != FS_LAV2_PO)
         return FS_ERR_UNSUPPORTED; // the table is in the uint64_t layout: only the waypoint-resident kernel reads it
-    if (wide && (type_tag == FS_T_HDR32 || type_tag == FS_T_HDR64) && !(mode == FS_LAV2_PO && parity == FS_PARITY_CPU)) {
-        // GPURenderer::RenderPerturbLAv2<uint64_t, ...> with a cap the 32-bit counters cannot hold: the literal kernel
-        // instantiated with 64-bit counters (all three modes; the reference's arithmetic, operation by operation)
-        if (mode != FS_LAV2_PO && (!r->la_ok || r->la_type != type_tag))
-            return FS_ERR_6;
-        const int kmode = mode == FS_LAV2_FULL ? FS_MODE_FULL : (mode == FS_LAV2_PO ? FS_MODE_PO : FS_MODE_LAO);
-        TimedLaunch t(r);
-        if (type_tag == FS_T_HDR32) {
-            FsLav2ArgsT<float> A;
-            fill_lav2<float>(r, A, coords, n_iterations, parity);
-            A.zref = r->zref;
-            A.zq = r->zq;
-            A.zs = r->zq + r->zq_n;
-        A.zs2 = r->zs2;
-        A.zqb = r->zqb;
-            A.at = r->at;
-            fsk_lav2_wide(&A, nullptr, kmode, r->stats_on, r->compute);
-        } else {
-            FsLav2ArgsT<double> A;
-            fill_lav2<double>(r, A, coords, n_iterations, parity);
-            A.zref = r->zref64;
-            A.at = r->at64;
-            fsk_lav2_wide(nullptr, &A, kmode, r->stats_on, r->compute);
-        }
-        return (uint32_t)hipGetLastError();
-    }
-    if (plain) {
-        // Gpu1x32 / Gpu1x64 / Gpu2x32 PerturbedLAv2*: no CPU RenderAlgorithm exists for LAv2 on a plain type, the kernel
-        // restates the reference's CUDA kernel and ignores `parity`.  coords = float[4] / double[4] / fs_real_p2x32[4].
-        if (mode != FS_LAV2_PO && (!r->la_ok || r->la_type != type_tag))
-            return FS_ERR_6;
-        FsLav2ArgsPlain A;
-        memset(&A, 0, sizeof(A));
-        A.out = (uint32_t *)r->iters();
-        A.orbit = type_tag == FS_T_F64 ? (const void *)r->orbit_f64 : (const void *)r->orbit_plain;
-        A.las = r->las;
-        A.stages = r->stages;
-        A.stats = r->stats;
-        A.frame = make_frame(r);
-        memcpy(A.coords, coords, type_tag == FS_T_F32 ? 4 * sizeof(float) : 4 * sizeof(double));
-        memcpy(A.at, r->at_plain, sizeof(A.at));
-        A.orbit_count = (uint32_t)r->orbit_uncompressed;
-        A.stage_count = r->n_stages;
-        A.n_iterations = (uint32_t)n_iterations;
-        A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        // (the waypoint-resident instantiations are built without the step counters too: fs_read_step_count must refuse, not
-        // report zeros)
-        r->last_launch_wide = A.frame.wide != 0u || r->orbit_seq;
-        A.la_valid = (r->la_ok && r->la_type == type_tag) ? r->la_valid : 0;
-        A.use_at = r->use_at;
-        if (r->orbit_seq) { // waypoint-resident orbit: a cursor per pixel (k_lav2_plain<.., kSeq>)
-            A.orbit = nullptr;
-            A.wp = r->wp_raw;
-            A.n_wp = (uint32_t)r->orbit_size;
-            memcpy(A.c_low[0], r->c_low_plain[0], 8);
-            memcpy(A.c_low[1], r->c_low_plain[1], 8);
-        }
-        TimedLaunch t(r);
-        fsk_lav2_plain(A, type_tag == FS_T_F32 ? 0 : (type_tag == FS_T_F64 ? 1 : 2),
-                       mode == FS_LAV2_FULL ? FS_MODE_FULL : (mode == FS_LAV2_PO ? FS_MODE_PO : FS_MODE_LAO), r->stats_on,
-                       r->compute);
-        return (uint32_t)hipGetLastError();
-    }
-    if (type_tag == FS_T_HDR2X32) {
-        // No CPU RenderAlgorithm exists for this type: the kernel restates the reference's CUDA kernel and ignores
-        // `parity` (coords are fs_real_2x32[4]).
-        if (mode != FS_LAV2_PO && (!r->la_ok || r->la_type != type_tag))
-            return FS_ERR_6;
-        FsLav2Args2x32 A;
-        memset(&A, 0, sizeof(A));
-        A.out = (uint32_t *)r->iters();
-        A.orbit = r->orbit_2x32;
-        A.las = (const fs_la_2x32_u32 *)r->las;
-        A.stages = r->stages;
-        A.stats = r->stats;
-        A.frame = make_frame(r);
-        memcpy(A.coords, coords, sizeof(A.coords));
-        A.at = r->at2x32;
-        A.orbit_count = (uint32_t)r->orbit_uncompressed;
-        A.stage_count = r->n_stages;
-        A.n_iterations = (uint32_t)n_iterations;
-        A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u || r->orbit_seq; // (kSeq: no counters either)
-        A.la_valid = (r->la_ok && r->la_type == type_tag) ? r->la_valid : 0;
-        A.use_at = r->use_at;
-        if (r->orbit_seq) { // waypoint-resident orbit: a cursor per pixel (k_lav2_2x32<.., kSeq>)
-            A.orbit = nullptr;
-            A.wp = (const fs_orbit_2x32_rc *)r->wp_raw;
-            A.n_wp = (uint32_t)r->orbit_size;
-            memcpy(&A.cxLow, r->c_low_plain[0], sizeof(fs_real_2x32));
-            memcpy(&A.cyLow, r->c_low_plain[1], sizeof(fs_real_2x32));
-        }
-        const fs_renderer::PixKey pk = pix_key_of(r, A.frame, type_tag, mode, 0, coords, sizeof(A.coords), n_iterations);
-        A.pixel_order = r->orbit_seq ? nullptr : pix_order_for(r, A.frame, pk);
-        const bool second = !r->orbit_seq && A.pixel_order == nullptr && pix_second_sighting(r, A.frame, pk);
-        A.pixel_cost = second ? pix_cost_for(r, A.frame, false) : nullptr;
-        {
-            TimedLaunch t(r);
-            if (!r->orbit_seq && A.pixel_order == nullptr && !second && mode != FS_LAV2_PO && A.use_at && A.la_valid) {
-                // a view's first frame: tiles in the order of a sampled PerformAT count (the record's values in binary64: head + tail, exact)
-                auto R = [](const fs_real_2x32 &x) { return fs::hreal<double>{(double)x.head + (double)x.tail, x.e}; };
-                auto Cx = [](const fs_cplx_2x32 &c) {
-                    return fs::hcplx<double>{(double)c.re_head + (double)c.re_tail, (double)c.im_head + (double)c.im_tail, c.e};
-                };
-                FsTileSampleArgs S;
-                memset(&S, 0, sizeof(S));
-                S.frame = A.frame;
-                S.coords = FsCoordsT<double>{R(A.coords[0]), R(A.coords[1]), R(A.coords[2]), R(A.coords[3])};
-                S.ThresholdC = R(A.at.ThresholdC), S.SqrEscapeRadius = R(A.at.SqrEscapeRadius);
-                S.RefC = Cx(A.at.RefC), S.CCoeff = Cx(A.at.CCoeff);
-                S.StepLength = A.at.StepLength, S.n_iterations = A.n_iterations;
-                A.tile_order = cold_tile_order(r, S);
-                A.tiles_x = S.tiles_x;
-            }
-            fsk_lav2_2x32(A, mode == FS_LAV2_FULL ? FS_MODE_FULL : (mode == FS_LAV2_PO ? FS_MODE_PO : FS_MODE_LAO),
-                          r->stats_on, r->compute);
-        }
-        if (second)
-            pix_order_after(r, A.frame, pk, false, A.pixel_cost);
-        return (uint32_t)hipGetLastError();
-    }
-    if (mode == FS_LAV2_PO && parity == FS_PARITY_CPU) {
-        // No dispatched CPU RenderAlgorithm is perturbation-only in HDRFloatComplex arithmetic; the CPU parity
-        // target for PO is the single-step branch of CalcCpuPerturbationFractalBLA.
+    if (wide && hdr && !po_cpu)
+        return no_table ? FS_ERR_6 : lav2_wide(r, type_tag, mode, parity, coords, n_iterations);
+    if (plain)
+        return no_table ? FS_ERR_6 : lav2_plain(r, type_tag, mode, coords, n_iterations);
+    if (type_tag == FS_T_HDR2X32)
+        return no_table ? FS_ERR_6 : lav2_2x32(r, mode, coords, n_iterations);
+    if (po_cpu) {
         const int32_t saved = r->bla_n_levels;
         r->bla_n_levels = 0;
         const uint32_t e = fs_render_bla(r, type_tag, coords, n_iterations);
         r->bla_n_levels = saved;
         return e;
     }
-    if (mode != FS_LAV2_PO && (!r->la_ok || r->la_type != type_tag))
+    if (no_table)
         return FS_ERR_6;
-    const int kmode = mode == FS_LAV2_FULL ? FS_MODE_FULL : (mode == FS_LAV2_PO ? FS_MODE_PO : FS_MODE_LAO);
-    if (type_tag == FS_T_HDR32) {
-        FsLav2ArgsT<float> A;
-        fill_lav2<float>(r, A, coords, n_iterations, parity);
-        A.zref = r->zref;
-        A.zq = r->zq;
-        A.zs = r->zq + r->zq_n;
-        A.zs2 = r->zs2;
-        A.zqb = r->zqb;
-        A.at = r->at;
-        // Longest tiles first, self-recorded.  Every frame of the tuned kernel stores one cost word per 8 x 8 tile (its
-        // longest lane's step count); the NEXT frame of the same geometry, band layout and orbit generation is launched in
-        // descending cost order (64 classes, raster order inside a class).  A frame ends one long wave after its last wave
-        // was dispatched and the waves differ 2.5x in length, so the drain at the end of the launch shrinks from the longest
-        // wave's duration towards the shortest's.  Which wave renders which tile changes no pixel; the first frame (and
-        // every frame after fs_forget_tile_costs, or with FS_VARIANT_NATURAL_TILE_ORDER) runs in natural order.
-        const uint32_t tiles_x = (r->width + 7u) / 8u, tiles_y = (r->local_rows + 7u) / 8u;
-        const uint32_t n_tiles = tiles_x * tiles_y;
-        const uint32_t n_slots = fsk_lav2_hdr32_slots(A.frame);
-        const bool tuned = (r->variant & FS_VARIANT_BASE_MASK) != FS_VARIANT_LITERAL;
-        const bool record = tuned && n_tiles >= kLav2OrderMinTiles &&
-                            (r->variant & FS_VARIANT_FLAG_NATURAL_ORDER) == 0;
-        r->last_frame_ordered = false;
-        if (record) {
-            if (r->lav2_cost_cap < n_tiles) {
-                (void)r_free(r, r->lav2_cost);
-                (void)r_free(r, r->lav2_sort_tmp);
-                r->lav2_cost = r->lav2_sort_tmp = nullptr;
-                r->lav2_cost_cap = 0;
-                r->lav2_cost_valid = false;
-                FS_TRY(r_alloc(r, (void **)&r->lav2_cost, (size_t)n_tiles * sizeof(uint32_t), kFrame));
-                FS_TRY(r_alloc(r, (void **)&r->lav2_sort_tmp, (size_t)fsk_tile_order_work_words(n_tiles) * sizeof(uint32_t), kFrame));
-                r->lav2_cost_cap = n_tiles;
-            }
-            if (r->lav2_order_cap < n_slots) {
-                (void)r_free(r, r->lav2_order);
-                r->lav2_order = nullptr;
-                r->lav2_order_cap = 0;
-                FS_TRY(r_alloc(r, (void **)&r->lav2_order, ((size_t)n_slots + 1) * sizeof(uint32_t), kFrame));
-                r->lav2_order_cap = n_slots;
-            }
-            const fs_renderer::CostKey key{r->width, r->local_rows, A.frame.band_first, A.frame.band_rows,
-                                           A.frame.band_stride, r->orbit_gen};
-            A.tile_cost = r->lav2_cost;
-            A.tiles_x = tiles_x;
-            if (r->lav2_cost_valid && r->lav2_cost_key == key)
-                A.tile_order = r->lav2_order;
-            r->lav2_cost_key = key;
-        }
-        if (A.tile_order) {
-            fsk_tile_order_by_cost(r->lav2_cost, n_tiles, r->lav2_sort_tmp, r->lav2_order, n_slots, r->compute);
-            r->last_frame_ordered = true;
-            r->lav2_last_ordered = true;
-        }
-        TimedLaunch t(r);
-        fsk_lav2_hdr32(A, kmode, r->stats_on, r->variant, r->compute);
-        r->lav2_cost_valid = record;
-    } else {
-        FsLav2ArgsT<double> A;
-        fill_lav2<double>(r, A, coords, n_iterations, parity);
-        A.zref = r->zref64;
-        A.at = r->at64;
-        const fs_renderer::PixKey pk = pix_key_of(r, A.frame, type_tag, mode, parity, coords, 4 * sizeof(fs_real_hdr64), n_iterations);
-        A.pixel_order = pix_order_for(r, A.frame, pk);
-        // PerformAT in a pass of its own, in the order of the AT iterations every pixel needs by itself (recorded by the view's
-        // first frame): the AT loop reads no memory, so its waves can be made of pixels from anywhere -- equal work per wave --
-        // while the frame's kernel keeps the order that keeps neighbours together (below).  A view's first frame has no such pass:
-        // without an order its waves wait for their slowest pixel just as the kernel's do.
-        const bool second = A.pixel_order == nullptr && pix_second_sighting(r, A.frame, pk);
-        bool at_split = mode != FS_LAV2_PO && A.use_at && A.la_valid && pix_order_wanted(r, A.frame) &&
-                        (A.pixel_order != nullptr || second);
-        if (at_split) {
-            const size_t n = (size_t)A.frame.rounded_width * ((A.frame.local_rows + 7u) & ~7u);
-            if (r->at_cap < n) {
-                (void)r_free(r, r->at_res);
-                (void)r_free(r, r->at_cost);
-                (void)r_free(r, r->at_order);
-                r->at_res = nullptr;
-                r->at_cost = r->at_order = nullptr;
-                r->at_cap = 0;
-                r->at_order_valid = false;
-                if (r_alloc(r, (void **)&r->at_res, n * sizeof(FsAtRes), kFrame) != hipSuccess ||
-                    r_alloc(r, (void **)&r->at_cost, n * sizeof(uint32_t), kFrame) != hipSuccess ||
-                    r_alloc(r, (void **)&r->at_order, n * sizeof(uint32_t), kFrame) != hipSuccess) {
-                    (void)hipGetLastError(); // no memory for it: PerformAT stays inside the frame's kernel
-                    (void)r_free(r, r->at_res);
-                    (void)r_free(r, r->at_cost);
-                    (void)r_free(r, r->at_order);
-                    r->at_res = nullptr;
-                    r->at_cost = r->at_order = nullptr;
-                    at_split = false;
-                } else {
-                    r->at_cap = n;
-                }
-            }
-        }
-        // (the AT order has a key of its own: it is a permutation of the buffer it was recorded on, and pix_order can be rebuilt
-        // -- other row bands, a table without AT in between -- without it)
-        const bool at_warm = at_split && r->at_order_valid && r->at_key == pk;
-        const bool at_record = at_split && !at_warm && (second || A.pixel_order != nullptr);
-        {
-            TimedLaunch t(r);
-            if (at_split) {
-                const uint32_t n = A.frame.rounded_width * ((A.frame.local_rows + 7u) & ~7u);
-                FsLav2ArgsT<double> P = A;
-                P.at_res = r->at_res;
-                if (at_warm) {
-                    P.pixel_order = r->at_order;
-                } else {
-                    P.pixel_order = nullptr;
-                    if (at_record) { // (a view's first frame records nothing: a viewer that zooms never uses it)
-                        P.at_cost = r->at_cost;
-                        FS_TRY(hipMemsetAsync(r->at_cost, 0, (size_t)n * sizeof(uint32_t), r->compute));
-                    }
-                    r->at_order_valid = false;
-                }
-                fsk_at_pass64(P, r->compute);
-                t.mid();
-                A.at_res = r->at_res;
-            }
-            if (A.pixel_order == nullptr && !second && !at_split && mode != FS_LAV2_PO && A.use_at && A.la_valid) {
-                // a view's first frame: tiles in the order of a sampled PerformAT count (kernels_tile_sample.hip)
-                FsTileSampleArgs S;
-                memset(&S, 0, sizeof(S));
-                S.frame = A.frame;
-                S.coords = A.coords;
-                S.ThresholdC = fs::hreal<double>{A.at.ThresholdC.m, A.at.ThresholdC.e};
-                S.SqrEscapeRadius = fs::hreal<double>{A.at.SqrEscapeRadius.m, A.at.SqrEscapeRadius.e};
-                S.RefC = fs::hcplx<double>{A.at.RefC.re, A.at.RefC.im, A.at.RefC.e};
-                S.CCoeff = fs::hcplx<double>{A.at.CCoeff.re, A.at.CCoeff.im, A.at.CCoeff.e};
-                S.StepLength = A.at.StepLength, S.n_iterations = A.n_iterations;
-                A.tile_order = cold_tile_order(r, S);
-                A.tiles_x = S.tiles_x;
-            }
-            // the production kernel (kernels_hdr64.hip); FS_VARIANT_LITERAL keeps the operation-by-operation one for A/B
-            // (k_lav2_hdr64 addresses its records with 32-bit byte offsets: an orbit or a table of 4 GB and more stays with the literal kernel)
-            const bool small = (uint64_t)A.orbit_count * sizeof(FsZ64) < 0xFFFFFF00ull &&
-                               (uint64_t)r->n_las * sizeof(fs_la_hdr64_u32) < 0xFFFFFF00ull;
-            if (!small || (r->variant & FS_VARIANT_BASE_MASK) == FS_VARIANT_LITERAL)
-                fsk_lav2_hdr64(A, kmode, r->stats_on, r->compute);
-            else
-                fsk_lav2_hdr64_fast(A, kmode, r->stats_on, r->compute);
-        }
-        // (sorted by COUNT, not by a recorded cost as the 2x32 frames are: this kernel's steps are cheap enough for the loads of
-        // a wave whose lanes are scattered over the frame to cost more than the idle lanes they save -- 81 ms with the cost as
-        // the key, 68 with its binades, 53 with the counts, which keep the pixels inside the set side by side: DESIGN.md 7)
-        if (second)
-            pix_order_after(r, A.frame, pk, false);
-        const uint32_t n_buf = A.frame.rounded_width * ((A.frame.local_rows + 7u) & ~7u);
-        if (at_split && at_record && r->pix_valid && r->pix_work && r->pix_temp && r->pix_cap >= n_buf) {
-            // the AT pass's own order, from the costs it has just recorded (the sort's work memory is the pixel order's)
-            const uint32_t n = n_buf;
-            if (fsk_pixel_order_build(r->at_cost, n, r->pix_work, r->at_order, r->pix_temp, r->pix_temp_bytes, r->compute) == hipSuccess) {
-                r->at_order_valid = true;
-                r->at_key = pk;
-            } else
-                (void)hipGetLastError();
-        }
-    }
-    return (uint32_t)hipGetLastError();
+    return type_tag == FS_T_HDR32 ? lav2_hdr32(r, mode, parity, coords, n_iterations)
+                                  : lav2_hdr64(r, mode, parity, coords, n_iterations);
 }
 
 uint32_t fs_render_bla(fs_renderer *r, int type_tag, const void *coords, uint64_t n_iterations)
 {
-    if (uint32_t e = use_device(r))
-        return e;
-    if (!r->memory_initialized())
-        return 0;
-    if (r->local_rows == 0)
-        return 0; // this renderer owns no row of the frame (a rank beyond the last band)
-    if (type_tag != FS_T_HDR32 && type_tag != FS_T_HDR64 && type_tag != FS_T_F64)
-        return FS_ERR_UNSUPPORTED;
-    if (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8)
-        return (uint32_t)hipErrorInvalidValue; // a 4-byte IterType cannot hold such a count
+    uint32_t rc;
+    if (render_begin(r, type_tag == FS_T_HDR32 || type_tag == FS_T_HDR64 || type_tag == FS_T_F64, n_iterations, &rc) != Begin::kGo)
+        return rc;
     if (!r->orbit_ok || r->orbit_type != type_tag)
         return FS_ERR_6;
     if (r->orbit_seq)
@@ -2923,54 +2707,40 @@ uint32_t fs_render_bla(fs_renderer *r, int type_tag, const void *coords, uint64_
     if (type_tag == FS_T_F64) {
         const double *c = (const double *)coords;
         FsBlaArgsF64 A;
-        memset(&A, 0, sizeof(A));
-        A.out = (uint32_t *)r->iters();
+        init_args(r, A, n_iterations);
         A.orbit = r->orbit_f64;
         A.levels = (const fs_bla_f64 *const *)r->bla_levels_dev;
-        A.stats = r->stats;
-        A.frame = make_frame(r);
         A.dx = c[0];
         A.dy = c[1];
         A.centerX = c[2];
         A.centerY = c[3];
         A.orbit_count = (uint32_t)r->orbit_uncompressed;
-        A.n_iterations = (uint32_t)n_iterations;
-        A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
         A.lm2 = r->bla_lm2;
         TimedLaunch t(r);
         fsk_perturb_bla_f64(A, use_bla, r->stats_on, r->compute);
     } else if (type_tag == FS_T_HDR32) {
         FsBlaArgsT<float> A;
-        memset(&A, 0, sizeof(A));
-        A.out = (uint32_t *)r->iters();
+        init_args(r, A, n_iterations);
         A.zref = r->zref;
         A.zq = r->zq;
         A.zs = r->zq + r->zq_n;
         A.zs2 = r->zs2;
         A.zqb = r->zqb;
         A.levels = (const fs_bla_hdr32 *const *)r->bla_levels_dev;
-        A.stats = r->stats;
         A.queue = r->queue;
-        A.frame = make_frame(r);
         fill_coords(A.coords, coords);
         A.orbit_count = (uint32_t)r->orbit_uncompressed;
-        A.n_iterations = (uint32_t)n_iterations;
-        A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
         A.lm2 = r->bla_lm2;
         if (use_bla && r->bla_native_stale)
             if (uint32_t e = bla_make_native(r, r->bla_n_levels))
                 return e;
         if (use_bla && r->bla_native_ok) {
-            A.nrec = (const FsBlaRec *)((const char *)r->bla_native + 256);
+            A.nrec = (const FsBlaRec *)(r->bla_native.as<const char>() + 256);
             A.nlad = (const int4 *)((const char *)A.nrec + (size_t)r->bla_native_total * sizeof(FsBlaRec));
             A.nkmax = (const long long *)(A.nlad + 2 * (size_t)r->bla_native_total);
             memcpy(A.level_off, r->bla_level_off, sizeof(A.level_off));
             if (r->bla_heap_ok) {
-                A.hrec = (const FsBlaRec *)r->bla_heap;
+                A.hrec = r->bla_heap.as<const FsBlaRec>();
                 A.hlad = (const int4 *)(A.hrec + r->bla_heap_positions);
                 A.hq = A.hlad + 2 * (size_t)r->bla_heap_positions;
                 A.zb = (const float4 *)(A.hq + 3 * (size_t)r->bla_heap_nq);
@@ -2988,23 +2758,8 @@ uint32_t fs_render_bla(fs_renderer *r, int type_tag, const void *coords, uint64_
                              n_slots >= kTileOrderMinTiles && (r->variant & FS_VARIANT_FLAG_NATURAL_ORDER) == 0 &&
                              (r->variant & FS_VARIANT_BASE_MASK) == FS_VARIANT_TUNED;
         if (reorder) {
-            if (r->tile_probe_cap < (size_t)tiles_x * tiles_y) {
-                if (r->tile_probe)
-                    FS_TRY(r_free(r, r->tile_probe));
-                r->tile_probe = nullptr;
-                r->tile_probe_cap = 0;
-                FS_TRY(r_alloc(r, (void **)&r->tile_probe, (size_t)tiles_x * tiles_y * sizeof(uint32_t), kFrame));
-                r->tile_probe_cap = (size_t)tiles_x * tiles_y;
-            }
-            if (r->tile_order_cap < n_slots) {
-                if (r->tile_order)
-                    FS_TRY(r_free(r, r->tile_order));
-                r->tile_order = nullptr;
-                r->tile_order_cap = 0;
-                FS_TRY(r_alloc(r, (void **)&r->tile_order, ((size_t)n_slots + 1) * sizeof(uint32_t), kFrame));
-                r->tile_order_cap = n_slots;
-                r->po_order_valid = false;
-            }
+            FS_TRY(buf_reserve(r, r->tile_probe, (size_t)tiles_x * tiles_y * sizeof(uint32_t), kFrame));
+            FS_TRY(buf_reserve(r, r->tile_order, ((size_t)n_slots + 1) * sizeof(uint32_t), kFrame, &r->po_order_valid));
         }
         TimedLaunch t(r);
         r->last_frame_ordered = false;
@@ -3017,11 +2772,12 @@ uint32_t fs_render_bla(fs_renderer *r, int type_tag, const void *coords, uint64_
                               r->po_order_iterations == n_iterations && memcmp(r->po_order_coords, coords, 32) == 0;
             if (!warm) {
                 FsBlaArgsT<float> P = A;
-                P.probe_out = r->tile_probe;
+                P.probe_out = r->tile_probe.as<uint32_t>();
                 P.probe_pitch = tiles_x;
                 P.n_iterations = (uint32_t)(n_iterations / kTileProbeDivisor);
                 fsk_perturb_scalar_hdr32(P, use_bla, false, r->variant, r->compute);
-                fsk_tile_order(r->tile_probe, tiles_x, tiles_x, tiles_y, P.n_iterations, r->tile_order, n_slots, r->compute);
+                fsk_tile_order(P.probe_out, tiles_x, tiles_x, tiles_y, P.n_iterations, r->tile_order.as<uint32_t>(), n_slots,
+                               r->compute);
                 r->po_order_key = key;
                 r->po_order_epoch = r->orbit_epoch;
                 r->po_order_iterations = n_iterations;
@@ -3029,24 +2785,17 @@ uint32_t fs_render_bla(fs_renderer *r, int type_tag, const void *coords, uint64_
                 r->po_order_valid = true;
             }
             r->last_frame_ordered = warm;
-            A.tile_order = r->tile_order;
+            A.tile_order = r->tile_order.as<uint32_t>();
         }
         fsk_perturb_scalar_hdr32(A, use_bla, r->stats_on, r->variant, r->compute);
     } else {
         FsBlaArgsT<double> A;
-        memset(&A, 0, sizeof(A));
-        A.out = (uint32_t *)r->iters();
+        init_args(r, A, n_iterations);
         A.zref = r->zref64;
         A.levels = (const fs_bla_hdr64 *const *)r->bla_levels_dev;
-        A.stats = r->stats;
         A.queue = r->queue;
-        A.frame = make_frame(r);
         fill_coords(A.coords, coords);
         A.orbit_count = (uint32_t)r->orbit_uncompressed;
-        A.n_iterations = (uint32_t)n_iterations;
-        A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
         A.lm2 = r->bla_lm2;
         TimedLaunch t(r);
         fsk_perturb_scalar_hdr64(A, use_bla, r->stats_on, r->variant, r->compute);
@@ -3056,69 +2805,35 @@ uint32_t fs_render_bla(fs_renderer *r, int type_tag, const void *coords, uint64_
 
 uint32_t fs_render_direct(fs_renderer *r, int type_tag, const void *coords, uint64_t n_iterations)
 {
-    if (uint32_t e = use_device(r))
-        return e;
-    if (!r->memory_initialized())
-        return 0; // GPU_Render.cu:626-628
-    if (r->local_rows == 0)
-        return 0; // this renderer owns no row of the frame (a rank beyond the last band)
-    if (type_tag != FS_T_F64 && type_tag != FS_T_HDR32 && type_tag != FS_T_HDR64)
-        return FS_ERR_UNSUPPORTED;
-    if (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8)
-        return (uint32_t)hipErrorInvalidValue;
-    if (r->cx_row_cap < r->width) {
-        if (r->cx_row)
-            FS_TRY(r_free(r, r->cx_row));
-        r->cx_row = nullptr;
-        FS_TRY(r_alloc(r, &r->cx_row, (size_t)16 * r->width, kFrame));
-        r->cx_row_cap = r->width;
-    }
+    uint32_t rc;
+    if (render_begin(r, type_tag == FS_T_F64 || type_tag == FS_T_HDR32 || type_tag == FS_T_HDR64, n_iterations, &rc) != Begin::kGo)
+        return rc;
+    FS_TRY(buf_reserve(r, r->cx_row, (size_t)16 * r->width, kFrame));
     if (type_tag == FS_T_F64) {
         const double *c = (const double *)coords;
         FsDirectArgs64 A;
-        memset(&A, 0, sizeof(A));
-        A.out = (uint32_t *)r->iters();
-        A.cx_row = (double *)r->cx_row;
-        A.stats = r->stats;
-        A.frame = make_frame(r);
+        init_args(r, A, n_iterations);
+        A.cx_row = r->cx_row.as<double>();
         A.dy = c[1];
         A.maxY = c[3];
-        A.n_iterations = (uint32_t)n_iterations;
-        A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
         TimedLaunch t(r);
         fsk_direct_f64(A, c[2], c[0], r->stats_on, r->compute);
     } else if (type_tag == FS_T_HDR32) {
         const fs_real_hdr32 *c = (const fs_real_hdr32 *)coords;
         FsDirectHdrArgsT<float> A;
-        memset(&A, 0, sizeof(A));
-        A.out = (uint32_t *)r->iters();
-        A.cx_row = (fs::hreal<float> *)r->cx_row;
-        A.stats = r->stats;
-        A.frame = make_frame(r);
+        init_args(r, A, n_iterations);
+        A.cx_row = r->cx_row.as<fs::hreal<float>>();
         A.dy = fs::hreal32{c[1].m, c[1].e};
         A.maxY = fs::hreal32{c[3].m, c[3].e};
-        A.n_iterations = (uint32_t)n_iterations;
-        A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
         TimedLaunch t(r);
         fsk_direct_hdr32(A, fs::hreal32{c[2].m, c[2].e}, fs::hreal32{c[0].m, c[0].e}, r->stats_on, r->compute);
     } else {
         const fs_real_hdr64 *c = (const fs_real_hdr64 *)coords;
         FsDirectHdrArgsT<double> A;
-        memset(&A, 0, sizeof(A));
-        A.out = (uint32_t *)r->iters();
-        A.cx_row = (fs::hreal<double> *)r->cx_row;
-        A.stats = r->stats;
-        A.frame = make_frame(r);
+        init_args(r, A, n_iterations);
+        A.cx_row = r->cx_row.as<fs::hreal<double>>();
         A.dy = fs::hreal64{c[1].m, c[1].e};
         A.maxY = fs::hreal64{c[3].m, c[3].e};
-        A.n_iterations = (uint32_t)n_iterations;
-        A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
         TimedLaunch t(r);
         fsk_direct_hdr64(A, fs::hreal64{c[2].m, c[2].e}, fs::hreal64{c[0].m, c[0].e}, r->stats_on, r->compute);
     }
@@ -3136,14 +2851,8 @@ uint32_t fs_upload_orbit_scaled(fs_renderer *r, int type_tag, uint32_t iter_byte
         return FS_ERR_UNSUPPORTED;
     if (!r->compute)
         return FS_ERR_6;
-    if (r->scaled_t) {
-        FS_TRY(r_free(r, r->scaled_t));
-        r->scaled_t = nullptr;
-    }
-    if (r->scaled_f) {
-        FS_TRY(r_free(r, r->scaled_f));
-        r->scaled_f = nullptr;
-    }
+    FS_TRY(r_release(r, r->scaled_t));
+    FS_TRY(r_release(r, r->scaled_f));
     r->scaled_count = 0;
     const size_t t_bytes = type_tag == FS_T_HDR32 ? sizeof(fs_orbit_hdr32_bad) : sizeof(fs_orbit_f64_bad);
     FS_TRY(r_alloc(r, &r->scaled_t, orbit_size * t_bytes, kInput));
@@ -3161,52 +2870,31 @@ uint32_t fs_upload_orbit_scaled(fs_renderer *r, int type_tag, uint32_t iter_byte
 
 uint32_t fs_render_scaled(fs_renderer *r, int type_tag, const void *coords, uint64_t n_iterations)
 {
-    if (uint32_t e = use_device(r))
-        return e;
-    if (!r->memory_initialized())
-        return 0; // GPU_Render.cu:1317-1319
-    if (r->local_rows == 0)
-        return 0; // this renderer owns no row of the frame (a rank beyond the last band)
-    if (type_tag != FS_T_HDR32 && type_tag != FS_T_F64)
-        return FS_ERR_UNSUPPORTED;
-    if (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8)
-        return (uint32_t)hipErrorInvalidValue;
+    uint32_t rc;
+    if (render_begin(r, type_tag == FS_T_HDR32 || type_tag == FS_T_F64, n_iterations, &rc) != Begin::kGo)
+        return rc;
     if (!r->scaled_t || !r->scaled_f || r->scaled_count < 2 || r->scaled_type != type_tag)
         return FS_ERR_6;
     const float w2threshold = (float)exp(log((double)1e30f) / 2.0);
     if (type_tag == FS_T_F64) {
         FsScaledArgsF64 A;
-        memset(&A, 0, sizeof(A));
-        A.out = (uint32_t *)r->iters();
+        init_args(r, A, n_iterations);
         A.orbit_t = (const fs_orbit_f64_bad *)r->scaled_t;
         A.orbit_f = r->scaled_f;
-        A.stats = r->stats;
-        A.frame = make_frame(r);
         const double *c = (const double *)coords;
         A.dx = c[0], A.dy = c[1], A.centerX = c[2], A.centerY = c[3];
         A.orbit_count = (uint32_t)r->scaled_count;
-        A.n_iterations = (uint32_t)n_iterations;
-        A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
         A.w2threshold = w2threshold;
         TimedLaunch t(r);
         fsk_scaled_f64(A, r->stats_on, r->variant & FS_VARIANT_BASE_MASK, r->compute);
         return (uint32_t)hipGetLastError();
     }
     FsScaledArgs32 A;
-    memset(&A, 0, sizeof(A));
-    A.out = (uint32_t *)r->iters();
+    init_args(r, A, n_iterations);
     A.orbit_t = (const fs_orbit_hdr32_bad *)r->scaled_t;
     A.orbit_f = r->scaled_f;
-    A.stats = r->stats;
-    A.frame = make_frame(r);
     fill_coords(A.coords, coords);
     A.orbit_count = (uint32_t)r->scaled_count;
-    A.n_iterations = (uint32_t)n_iterations;
-    A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
     A.w2threshold = w2threshold;
     TimedLaunch t(r);
     fsk_scaled_hdr32(A, r->stats_on, r->variant & FS_VARIANT_BASE_MASK, r->compute);
@@ -3216,26 +2904,12 @@ uint32_t fs_render_scaled(fs_renderer *r, int type_tag, const void *coords, uint
 uint32_t fs_render_direct_lp(fs_renderer *r, int type_tag, const void *coords, uint64_t n_iterations,
                              int iteration_precision)
 {
-    if (uint32_t e = use_device(r))
-        return e;
-    if (!r->memory_initialized())
-        return 0; // GPU_Render.cu:626-628
-    if (r->local_rows == 0)
-        return 0; // this renderer owns no row of the frame (a rank beyond the last band)
-    if (type_tag != FS_T_F32 && type_tag != FS_T_2X32 && type_tag != FS_T_2X64 && type_tag != FS_T_4X32 &&
-        type_tag != FS_T_4X64)
-        return FS_ERR_UNSUPPORTED;
-    if (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8)
-        return (uint32_t)hipErrorInvalidValue;
+    uint32_t rc;
+    if (render_begin(r, type_tag == FS_T_F32 || type_tag == FS_T_2X32 || type_tag == FS_T_2X64 || type_tag == FS_T_4X32 ||
+                            type_tag == FS_T_4X64, n_iterations, &rc) != Begin::kGo)
+        return rc;
     FsDirectLpArgs A;
-    memset(&A, 0, sizeof(A));
-    A.out = (uint32_t *)r->iters();
-    A.stats = r->stats;
-    A.frame = make_frame(r);
-    A.n_iterations = (uint32_t)n_iterations;
-    A.n_iterations_hi = (uint32_t)(n_iterations >> 32);
-        A.frame.wide |= A.n_iterations_hi != 0u ? 1u : 0u;
-        r->last_launch_wide = A.frame.wide != 0u;
+    init_args(r, A, n_iterations);
     if (type_tag == FS_T_F32)
         memcpy(A.c32, coords, 4 * sizeof(float));
     else if (type_tag == FS_T_2X32)
@@ -3540,14 +3214,14 @@ uint32_t fs_read_tile_costs(fs_renderer *r, uint32_t *out, uint64_t max_words, u
 {
     if (uint32_t e = use_device(r))
         return e;
-    if (!r->lav2_cost || !r->lav2_cost_valid)
+    if (!r->lav2_cost.p || !r->lav2_cost_valid)
         return FS_ERR_6;
     const uint64_t n = (uint64_t)((r->lav2_cost_key.width + 7u) / 8u) * ((r->lav2_cost_key.local_rows + 7u) / 8u);
     if (n_tiles)
         *n_tiles = n;
     const uint64_t m = n < max_words ? n : max_words;
     if (out && m) {
-        FS_TRY(hipMemcpyAsync(out, r->lav2_cost, m * sizeof(uint32_t), hipMemcpyDeviceToHost, r->compute));
+        FS_TRY(hipMemcpyAsync(out, r->lav2_cost.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, r->compute));
         FS_TRY(hipStreamSynchronize(r->compute));
     }
     return 0;
@@ -3579,11 +3253,11 @@ uint32_t fs_read_tile_order(fs_renderer *r, uint32_t *out, uint64_t max_words)
 {
     if (uint32_t e = use_device(r))
         return e;
-    if (!r->lav2_order || !r->lav2_last_ordered)
+    if (!r->lav2_order.p || !r->lav2_last_ordered)
         return FS_ERR_6;
     const uint64_t n = (uint64_t)((r->lav2_cost_key.width + 7u) / 8u) * ((r->lav2_cost_key.local_rows + 7u) / 8u);
     const uint64_t m = n < max_words ? n : max_words;
-    FS_TRY(hipMemcpyAsync(out, r->lav2_order, m * sizeof(uint32_t), hipMemcpyDeviceToHost, r->compute));
+    FS_TRY(hipMemcpyAsync(out, r->lav2_order.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, r->compute));
     FS_TRY(hipStreamSynchronize(r->compute));
     return 0;
 }

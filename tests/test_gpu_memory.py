@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import _oracle
-from fractalshark_amd import GPURenderer, LAV2_FULL, LAV2_PO, PARITY_CPU, PARITY_CPU_GPUSTAGE, T_HDR32, T_HDR64, _capi, inputs
+from fractalshark_amd import (GPURenderer, LAV2_FULL, LAV2_PO, PARITY_CPU, PARITY_CPU_GPUSTAGE, T_F64, T_HDR32, T_HDR64, _capi,
+                              inputs)
 
 pytestmark = pytest.mark.gpu
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "golden_small.npz"))
@@ -177,3 +178,37 @@ def test_idle_blocks_of_every_renderer_on_the_device_can_be_taken_back(native_li
     finally:
         a.close()
         b.close()
+
+
+def test_a_renderer_recovers_from_an_iteration_buffer_that_cannot_be_allocated(native_libs):
+    """InitializeMemory of a geometry whose iteration buffer cannot exist on any device (2^20 x 2^20 counts of 8 bytes: 8 TiB)
+    returns the allocator's error and releases everything the renderer holds.  The next InitializeMemory -- the first
+    geometry again, the SAME palette array and generation -- must leave a renderer that is whole: the direct kernel gets a
+    column buffer again (its capacity went with the buffer) and the palette is uploaded again (its cache key went with the
+    palette), so the frame has the oracle's counts and the colours of the frame before the failure."""
+    v = inputs.View.builtin(0, 64, 48)
+    n = v.num_iterations
+    pal = _oracle.default_palette(8)
+    assert pal.dtype == np.uint16 and pal.flags.c_contiguous  # the wrapper passes this array's own pointer, every time
+    dx, dy, minx, maxy = v.coords_direct_f64()
+    r = GPURenderer(0)
+    try:
+        def frame():
+            assert r.InitializeMemory(64, 48, 1, pal, len(pal), 0, 7, False) == 0
+            assert r.Render(None, minx, maxy, dx, dy, n, T=T_F64) == 0
+            it = r.new_iter_buffer()
+            colors = np.zeros((int(r._lib.fs_color_buffer_elements(r._h)), 4), np.uint16)
+            assert r.RenderCurrent(n, it, colors) == 0
+            assert r.SyncComputeStream() == 0
+            return it, colors
+
+        want = _oracle.direct_f64(v)
+        it0, colors0 = frame()
+        assert np.array_equal(it0, want)
+        assert colors0.any()  # (a palette was applied)
+        assert r.InitializeMemory(1 << 20, 1 << 20, 1, pal, len(pal), 0, 7, False, iter_bytes=8) != 0
+        it1, colors1 = frame()
+        assert np.array_equal(it1, want)
+        assert np.array_equal(colors1, colors0)
+    finally:
+        r.close()
