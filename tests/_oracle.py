@@ -173,23 +173,25 @@ def new_buffer(w, h):
     return np.zeros(((h + 7) // 8 * 8, rounded_width(w)), np.uint32)
 
 
-def direct_f64(view, aa=1, rows=None, threads=8):
+def direct_f64(view, aa=1, rows=None, threads=8, n_iterations=None):
     w, h = view.width * aa, view.height * aa
     out = new_buffer(w, h)
     co = view.coords_direct_f64(aa)
     y0, y1 = rows if rows else (0, h)
-    lib().orc_direct_f64(w, h, y0, y1, co.ctypes.data, view.num_iterations, out.ctypes.data, out.shape[1], threads)
+    n = view.num_iterations if n_iterations is None else n_iterations
+    lib().orc_direct_f64(w, h, y0, y1, co.ctypes.data, n, out.ctypes.data, out.shape[1], threads)
     return out
 
 
-def direct_hdr(view, is64, aa=1, rows=None, threads=8):
+def direct_hdr(view, is64, aa=1, rows=None, threads=8, n_iterations=None):
     """CalcCpuHDR<u32,HDRFloat<F>,F> (CpuHDR32 / CpuHDR64)."""
     w, h = view.width * aa, view.height * aa
     out = new_buffer(w, h)
     co = view.coords_direct_hdr(is64, aa)
     y0, y1 = rows if rows else (0, h)
+    n = view.num_iterations if n_iterations is None else n_iterations
     fn = lib().orc_direct_hdr64 if is64 else lib().orc_direct_hdr32
-    fn(w, h, y0, y1, co.ctypes.data, view.num_iterations, out.ctypes.data, out.shape[1], threads)
+    fn(w, h, y0, y1, co.ctypes.data, n, out.ctypes.data, out.shape[1], threads)
     return out
 
 
