@@ -60,6 +60,15 @@ class At2x32(C.Structure):
                 ("CCoeffNormSqr", Real2x32), ("RefCNormSqr", Real2x32), ("factor", Real2x32)]
 
 
+class AutozoomResult(C.Structure):
+    """fs_autozoom_result (include/fs_layout.h)."""
+    _fields_ = [("status", u32), ("heuristic", u32), ("target_x", C.c_double), ("target_y", C.c_double),
+                ("max_iter", u64), ("num_at_limit", u64), ("num_at_max", u64), ("sum_iters", u64), ("avg", C.c_double),
+                ("candidates", u64), ("accepted", u64), ("high_hist", u64 * 9), ("run_reject", u64), ("rescored", u64),
+                ("score", C.c_double), ("sum_sq", C.c_double), ("sum_sq_x", C.c_double), ("sum_sq_y", C.c_double)]
+
+
+assert C.sizeof(AutozoomResult) == 200
 assert C.sizeof(AtHdr32) == 116 and C.sizeof(AtHdr64) == 232 and C.sizeof(At2x32) == 184
 
 DONE_CB = C.CFUNCTYPE(None, vp)
@@ -114,6 +123,8 @@ def render_lib():
     _decl(lib, "fs_feature_eval", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
     _decl(lib, "fs_feature_eval_direct", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
     _decl(lib, "fs_set_feature_slice", u32, [vp, u32])
+    _decl(lib, "fs_autozoom_pick", u32, [vp, C.c_int, u64, vp, C.POINTER(AutozoomResult)])
+    _decl(lib, "fs_set_autozoom_gather_cap", u32, [vp, u32])
     _decl(lib, "fs_render_bla", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_render_direct", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_upload_orbit_scaled", u32, [vp, C.c_int, u32, vp, vp, u64, u64])
@@ -191,6 +202,7 @@ RENDER_SYMBOLS = [
     "fs_create", "fs_destroy", "fs_test_device_is_working", "fs_device_count", "fs_error_string", "fs_init_memory", "fs_set_row_bands",
     "fs_local_rows", "fs_set_external_iter_buffer", "fs_device_iter_buffer", "fs_rounded_width", "fs_upload_orbit", "fs_upload_orbit_compressed",
     "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_feature_eval", "fs_feature_eval_direct", "fs_set_feature_slice",
+    "fs_autozoom_pick", "fs_set_autozoom_gather_cap",
     "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
     "fs_render_direct_lp", "fs_clear",
@@ -217,6 +229,7 @@ def inputs_lib():
     lib = C.CDLL(path)
     _decl(lib, "fsh_view_create", vp, [C.c_char_p] * 4 + [u32, u32])
     _decl(lib, "fsh_view_destroy", None, [vp])
+    _decl(lib, "fsh_view_autozoom_next", vp, [vp, C.c_double, C.c_double, u32, u32, u32])
     _decl(lib, "fsh_view_save_im", C.c_int, [vp, u64, C.c_char_p, C.c_int])
     _decl(lib, "fsh_view_load_im", vp, [C.c_char_p, u32, u32, C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(C.c_int)])
     _decl(lib, "fsh_view_precision_bits", u64, [vp])

@@ -466,6 +466,37 @@ void fsk_antialias(const void *iters, int iter_u64, uint32_t rounded_width, fs_c
                    uint64_t n_iterations, hipStream_t s);
 void fsk_reduce(const void *iters, int iter_u64, uint32_t rounded_width, uint32_t width, uint32_t rows,
                 fs_reduction *out, hipStream_t s);
+// ---- fs_autozoom_pick (kernels_autozoom.hip).  One device block of integer results per call, seeded by the host (zeros,
+// first_index = ~0); the passes that follow one another on the stream read what the earlier ones left in it.
+struct FsAzStats {
+    uint64_t max_iter, sum, n_ge;                 // pass 1 over the rectangle: max, integer sum, count >= n_iterations
+    uint64_t num_at_limit, first_index, num_at_max; // Max: pixels at max_iter, smallest linear index y * W + x among them
+    uint64_t candidates, accepted, run_reject, hist[9]; // FilamentTip
+    uint64_t best_key; // the largest device score as an order-preserving integer key (0 = none)
+    uint64_t gathered; // candidates that qualified in the last gather launch (may exceed what the buffer holds)
+    double sums[3];    // Default: sum of sq, sq * x, sq * y
+};
+struct FsAzTipRec {
+    uint32_t x, y;
+    uint64_t iter;
+    uint32_t high, pad_;
+};
+struct FsAzFrame {
+    const void *iters;
+    uint32_t iter_u64, pitch, W, H; // pitch in elements
+    uint64_t n_iterations;
+};
+// rectangle [x0, x0 + w) x [y0, y0 + h)
+void fsk_az_stats(const FsAzFrame &F, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, FsAzStats *st, hipStream_t s);
+void fsk_az_max(const FsAzFrame &F, FsAzStats *st, hipStream_t s);
+// slab: 3 doubles per row of the rectangle
+void fsk_az_default(const FsAzFrame &F, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, double width_over_2,
+                    double height_over_2, double max_distance, FsAzStats *st, double *slab, hipStream_t s);
+void fsk_az_tip_score(const FsAzFrame &F, double max_dist, FsAzStats *st, hipStream_t s);
+// rows [ya, yb) of the frame; row_counts (or null): qualifying candidates per frame row, added to
+void fsk_az_tip_gather(const FsAzFrame &F, double max_dist, uint32_t ya, uint32_t yb, FsAzStats *st, FsAzTipRec *out,
+                       uint32_t cap, uint32_t *row_counts, hipStream_t s);
+
 // multi-GPU tiler: out row y = in row index[y] (row_bytes a multiple of 16)
 void fsk_gather_rows(const void *in, void *out, const uint32_t *index, uint32_t row_bytes, uint32_t rows, hipStream_t s);
 

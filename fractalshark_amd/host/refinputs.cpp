@@ -515,6 +515,40 @@ extern "C" fsh_view *fsh_view_load_im(const char *path, uint32_t width, uint32_t
     return out;
 }
 
+// The AutoZoomer's next view (AutoZoomer.cpp:406-412) around the screen point (x, y) of the antialiased w_aa x h_aa frame:
+// guess = (minX + x (maxX - minX) / w_aa, maxY - y (maxY - minY) / h_aa), box = guess +- (width, height) / divisor, in mpf at the
+// view's precision; then what a new view gets (finish_view: precision for the new depth, aspect squaring).  A RESTATEMENT of
+// X/YFromScreenToCalc<true> (PointZoomBBConverter.cpp:339-354): the reference goes through OriginX = w / (maxX - minX) * -minX,
+// algebraically the same point; neither form can be pinned against the other to the last bit of an mpf.
+extern "C" fsh_view *fsh_view_autozoom_next(const fsh_view *v, double x, double y, uint32_t w_aa, uint32_t h_aa, uint32_t divisor)
+{
+    if (!v || !w_aa || !h_aa || !divisor || !(x == x) || !(y == y) || std::isinf(x) || std::isinf(y))
+        return nullptr;
+    mpf_set_default_prec(v->prec_bits);
+    const uint64_t prec = v->prec_bits;
+    Mp width = v->maxX - v->minX, height = v->maxY - v->minY;
+    Mp px(prec, 0), py(prec, 0), gx(prec, 0), gy(prec, 0);
+    mpf_set_d(px.v, x);
+    mpf_set_d(py.v, y);
+    mpf_mul(gx.v, px.v, width.v);
+    mpf_div_ui(gx.v, gx.v, w_aa);
+    mpf_add(gx.v, v->minX.v, gx.v);
+    mpf_mul(gy.v, py.v, height.v);
+    mpf_div_ui(gy.v, gy.v, h_aa);
+    mpf_sub(gy.v, v->maxY.v, gy.v);
+    Mp half_w(prec, 0), half_h(prec, 0);
+    mpf_div_ui(half_w.v, width.v, divisor);
+    mpf_div_ui(half_h.v, height.v, divisor);
+    auto nv = std::make_unique<fsh_view>();
+    nv->width = v->width;
+    nv->height = v->height;
+    nv->minX = gx - half_w;
+    nv->minY = gy - half_h;
+    nv->maxX = gx + half_w;
+    nv->maxY = gy + half_h;
+    return finish_view(std::move(nv), true);
+}
+
 extern "C" void fsh_view_destroy(fsh_view *v) { delete v; }
 extern "C" uint64_t fsh_view_precision_bits(const fsh_view *v) { return v->prec_bits; }
 

@@ -94,6 +94,19 @@ class View:
         if self._lib.fsh_view_save_im(self._h, self.num_iterations, os.fsencode(path), int(exp_bytes)) != 0:
             raise OSError("could not write %s" % (path,))
 
+    def autozoom_next(self, x, y, divisor):
+        """The AutoZoomer's next view around screen position (x, y) of the antialiased frame (fsh_view_autozoom_next): the box
+        guess +- (width, height) / divisor; same window, iteration limit and antialiasing."""
+        aa = self.antialiasing
+        h = self._lib.fsh_view_autozoom_next(self._h, float(x), float(y), self.width * aa, self.height * aa, int(divisor))
+        if not h:
+            raise ValueError("fsh_view_autozoom_next: bad arguments")
+        nv = View.__new__(View)
+        nv._lib, nv._h = self._lib, h
+        nv.width, nv.height = self.width, self.height
+        nv.num_iterations, nv.antialiasing = self.num_iterations, aa
+        return nv
+
     def __del__(self):
         if getattr(self, "_h", None):
             self._lib.fsh_view_destroy(self._h)

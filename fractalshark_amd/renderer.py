@@ -153,6 +153,18 @@ class GPURenderer:
         return self._feature_eval(self._lib.fs_feature_eval_direct, T, iter_bytes, mode, radius, max_iters, records_in,
                                   records_out)
 
+    def AutozoomPick(self, heuristic, n_iterations, device_iters=None):
+        """fs_autozoom_pick: the AutoZoomer's next target from the iteration buffer on the device (include/fsmi355.h).  heuristic =
+        autozoom.DEFAULT / MAX / FILAMENT_TIP; device_iters: another device buffer of the frame's geometry (raw pointer), None =
+        the current one.  Returns (error code, _capi.AutozoomResult).  Synchronous."""
+        res = _capi.AutozoomResult()
+        err = self._lib.fs_autozoom_pick(self._h, int(heuristic), int(n_iterations), device_iters, C.byref(res))
+        return err, res
+
+    def SetAutozoomGatherCap(self, rows):
+        """Test hook (fs_set_autozoom_gather_cap): frame rows the FilamentTip gather buffer holds, 0 = default."""
+        return self._lib.fs_set_autozoom_gather_cap(self._h, int(rows))
+
     def _feature_eval(self, entry, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
         from . import features
         din, dout, dreal = features.records(T == T_HDR64)

@@ -28,6 +28,11 @@ typedef struct fsh_bla fsh_bla;
  * precision, square the box to the window aspect ratio. */
 fsh_view *fsh_view_create(const char *minX, const char *minY, const char *maxX, const char *maxY,
                           uint32_t width, uint32_t height);
+/* The AutoZoomer's next view (AutoZoomer.cpp:406-412): the box guess +- (width, height) / divisor around the point of the view
+ * that screen position (x, y) of the antialiased w_aa x h_aa frame maps to (fs_autozoom_pick's target; divisor 3 / 32 / 8 for
+ * Default / Max / FilamentTip), computed at the view's precision, then finished like any new view (precision, aspect squaring).
+ * The window size is the view's.  NULL: a zero size or divisor, a position that is not finite. */
+fsh_view *fsh_view_autozoom_next(const fsh_view *v, double x, double y, uint32_t w_aa, uint32_t h_aa, uint32_t divisor);
 void fsh_view_destroy(fsh_view *v);
 uint64_t fsh_view_precision_bits(const fsh_view *v);
 /* Imagina ".im" location files, the form the reference writes for a view without a stored orbit

@@ -479,9 +479,30 @@ typedef struct fs_feature_out_hdr64 {
     fs_real_hdr64 residual2;
 } fs_feature_out_hdr64;
 
+/* fs_autozoom_pick (fsmi355.h).  Per heuristic (fields not named are zero):
+ *   Max          target = first pixel at max_iter; max_iter, sum_iters, avg = sum / (W H) over the frame; num_at_limit = pixels at
+ *                max_iter; num_at_max = pixels >= n_iterations.
+ *   FilamentTip  sum_iters, avg, max_iter over the frame; num_at_max = candidates >= n_iterations; candidates (pixels inside the
+ *                margin at or above size_t(avg + 1)), high_hist[k] = candidates with k high directions, run_reject, accepted;
+ *                score = the winner's score and target its pixel, or -1 and the frame's centre (W / 2, H / 2) without one;
+ *                rescored = candidates the host scored with libm (not a quantity of the reference).
+ *   Default      max_iter, sum_iters, avg, num_at_limit over the inner rectangle; num_at_max = its pixels >= avg that are
+ *                >= n_iterations; sum_sq, sum_sq_x, sum_sq_y; target = (sum_sq_x, sum_sq_y) / sum_sq, or (0, 0) when sum_sq = 0. */
+typedef struct fs_autozoom_result {
+    uint32_t status; /* FS_AUTOZOOM_MOVE / _MOVE_THEN_STOP / _FLAT / _NO_TARGET */
+    uint32_t heuristic;
+    double target_x, target_y;
+    uint64_t max_iter, num_at_limit, num_at_max, sum_iters;
+    double avg;
+    uint64_t candidates, accepted, high_hist[9], run_reject, rescored;
+    double score;
+    double sum_sq, sum_sq_x, sum_sq_y;
+} fs_autozoom_result;
+
 #ifdef __cplusplus
 }
-static_assert(sizeof(fs_feature_in_hdr32) == 32 && sizeof(fs_feature_in_hdr64) == 56 && sizeof(fs_feature_out_hdr32) == 64 &&
+static_assert(sizeof(fs_autozoom_result) == 200, "autozoom record");
+static_assert(sizeof(fs_feature_in_hdr32) == 32&& sizeof(fs_feature_in_hdr64) == 56 && sizeof(fs_feature_out_hdr32) == 64 &&
                   sizeof(fs_feature_out_hdr64) == 104,
               "Feature Finder records");
 static_assert(sizeof(fs_orbit_hdr32) == 16, "orbit entry");

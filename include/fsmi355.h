@@ -197,6 +197,32 @@ uint32_t fs_feature_eval(fs_renderer *r, int type_tag, uint32_t iter_bytes, int 
 uint32_t fs_feature_eval_direct(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius,
                                 uint64_t max_iters, const void *in, void *out, uint64_t n);
 
+/* The AutoZoomer's choice of the next zoom target (AutoZoomer::Run, AutoZoomer.cpp:74-393) on the device, from the iteration
+ * buffer the render kernels wrote: the frame is never read back.  W x H below = the frame of fs_init_memory (antialiasing
+ * included), row 0 = the buffer's row 0.  device_iters: another device buffer of the same geometry and IterType, NULL = the
+ * renderer's current one.  out = fs_autozoom_result (fs_layout.h), which says per heuristic what every field holds.
+ *   FS_AUTOZOOM_MAX           the first pixel in raster order that holds the frame's largest count (zoom divisor 32)
+ *   FS_AUTOZOOM_FILAMENT_TIP  the best-scoring filament tip inside the 18-pixel margin (divisor 8).  Classification and counts
+ *                             are integer work on the device; the score involves log(), which the device does not compute as the
+ *                             host's libm does, so the device score only SELECTS candidates: every accepted candidate within
+ *                             2^-40 of the device maximum is re-scored on the host with libm, in raster order, strict `>`.
+ *   FS_AUTOZOOM_DEFAULT       the weighted mean position over the inner rectangle (divisor 3).  Its three sums are non-integer
+ *                             doubles: summed in a fixed tree (bitwise equal from run to run), not in the reference's raster
+ *                             order -- target_x / target_y agree with a sequential sum to 4 n 2^-53 relative, n = pixels of the
+ *                             rectangle.
+ * status follows the reference's order of tests: FS_AUTOZOOM_FLAT = Max / Default "flat screen", and FilamentTip's stop on
+ * num_at_max > W H / 2 (none of them moves); FS_AUTOZOOM_NO_TARGET = FilamentTip without an accepted candidate (or an all-zero
+ * frame); FS_AUTOZOOM_MOVE_THEN_STOP = Max / Default with num_at_max > 500: move, then stop.
+ * Sums of counts are integers on the device, converted to double once: the reference's running double sum rounds on the way once
+ * it passes 2^53, this one does not (no test goes there).
+ * Synchronous on the compute stream, behind the render.  Frame state (iteration buffer, recorded tile costs and orders, orbit / LA
+ * caches, kernel-time history) is left as it was.  FS_ERR_6: no fs_init_memory yet.  FS_ERR_UNSUPPORTED: row bands set
+ * (fs_set_row_bands), an unknown heuristic, a frame smaller than the heuristic's margins (FilamentTip: W or H <= 36). */
+enum { FS_AUTOZOOM_DEFAULT = 0, FS_AUTOZOOM_MAX = 1, FS_AUTOZOOM_FILAMENT_TIP = 2 };
+enum { FS_AUTOZOOM_MOVE = 0, FS_AUTOZOOM_MOVE_THEN_STOP = 1, FS_AUTOZOOM_FLAT = 2, FS_AUTOZOOM_NO_TARGET = 3 };
+uint32_t fs_autozoom_pick(fs_renderer *r, int heuristic, uint64_t n_iterations, const void *device_iters,
+                          fs_autozoom_result *out);
+
 /* BLA table upload (GPU_BLAS ctor, BLA.cuh:123-160); the reference does this inside RenderPerturbBLA. */
 uint32_t fs_upload_bla(fs_renderer *r, int type_tag, const void *const *levels, const uint64_t *level_sizes,
                        int32_t n_levels, int32_t lm2);

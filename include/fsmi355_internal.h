@@ -95,6 +95,10 @@ uint32_t fs_read_tile_order(fs_renderer *r, uint32_t *out, uint64_t max_words);
  * default, 2^18.  A Direct period search never runs that long, so only a small slice exercises the lane state that is carried
  * from launch to launch.  Changes no result. */
 uint32_t fs_set_feature_slice(fs_renderer *r, uint32_t steps);
+/* Test hook: rows of the frame that the FilamentTip gather buffer of fs_autozoom_pick holds (W records each); 0 = the default,
+ * 32.  When more candidates qualify than fit, the gather is repeated over bands of rows: a small cap exercises that path.
+ * Changes no result. */
+uint32_t fs_set_autozoom_gather_cap(fs_renderer *r, uint32_t rows);
 uint32_t fs_enable_step_count(fs_renderer *r, int enable);
 uint32_t fs_read_step_count(fs_renderer *r, uint64_t counts[8]);
 /* The whole statistics buffer (measurement builds append per-wave trace records behind the 8 counters: library built
