@@ -125,6 +125,10 @@ def render_lib():
     _decl(lib, "fs_set_feature_slice", u32, [vp, u32])
     _decl(lib, "fs_autozoom_pick", u32, [vp, C.c_int, u64, vp, C.POINTER(AutozoomResult)])
     _decl(lib, "fs_set_autozoom_gather_cap", u32, [vp, u32])
+    _decl(lib, "fs_render_exact", u32, [vp, u32, u32, u32, vp, vp, u32, C.c_int, u64])
+    _decl(lib, "fs_exact_stable_mask", u32, [vp, u32, u32, vp, vp, u32, u64, vp])
+    _decl(lib, "fs_set_exact_slice", u32, [vp, u32, C.c_int])
+    _decl(lib, "fs_read_exact_stats", u32, [vp, vp])
     _decl(lib, "fs_render_bla", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_render_direct", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_upload_orbit_scaled", u32, [vp, C.c_int, u32, vp, vp, u64, u64])
@@ -203,6 +207,7 @@ RENDER_SYMBOLS = [
     "fs_local_rows", "fs_set_external_iter_buffer", "fs_device_iter_buffer", "fs_rounded_width", "fs_upload_orbit", "fs_upload_orbit_compressed",
     "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_feature_eval", "fs_feature_eval_direct", "fs_set_feature_slice",
     "fs_autozoom_pick", "fs_set_autozoom_gather_cap",
+    "fs_render_exact", "fs_exact_stable_mask", "fs_set_exact_slice", "fs_read_exact_stats",
     "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
     "fs_render_direct_lp", "fs_clear",
@@ -233,6 +238,7 @@ def inputs_lib():
     _decl(lib, "fsh_view_save_im", C.c_int, [vp, u64, C.c_char_p, C.c_int])
     _decl(lib, "fsh_view_load_im", vp, [C.c_char_p, u32, u32, C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(C.c_int)])
     _decl(lib, "fsh_view_precision_bits", u64, [vp])
+    _decl(lib, "fsh_view_exact_axes", C.c_int, [vp, u32, u32, u32, C.c_int, u32, vp, vp])
     _decl(lib, "fsh_view_bbox_str", C.c_int, [vp, C.c_int, C.c_char_p, C.c_size_t])
     _decl(lib, "fsh_view_coords_direct_f64", None, [vp, u32, u32, vp])
     _decl(lib, "fsh_view_coords_direct_hdr32", None, [vp, u32, u32, vp])

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/fs_layout.h"
+#include "exact_math.hpp"
 #include "hdr_math.hpp"
 
 enum { FS_MODE_FULL = 0, FS_MODE_PO = 1, FS_MODE_LAO = 2 };
@@ -496,6 +497,35 @@ void fsk_az_tip_score(const FsAzFrame &F, double max_dist, FsAzStats *st, hipStr
 // rows [ya, yb) of the frame; row_counts (or null): qualifying candidates per frame row, added to
 void fsk_az_tip_gather(const FsAzFrame &F, double max_dist, uint32_t ya, uint32_t yb, FsAzStats *st, FsAzTipRec *out,
                        uint32_t cap, uint32_t *row_counts, hipStream_t s);
+
+// ---- exact renderer (kernels_exact.hip): one slice of a frame's fixed-point iteration
+struct FsExactArgs {
+    const uint32_t *cx, *cy; // limb-major axes: cx[l * W + column], cy[l * H + row]
+    uint32_t W, H, rounded_width;
+    uint32_t iter_u64;
+    void *iters;             // the frame the finished samples write their counts to
+    uint64_t cap;            // N
+    fsx::Params P;
+    // running samples: limb planes of x, then of y (stride slots each), n (0 = finished, only without compaction) and pixel
+    const uint32_t *src_xy;
+    const uint64_t *src_n;
+    const uint32_t *src_pix;
+    uint32_t *dst_xy;
+    uint64_t *dst_n;
+    uint32_t *dst_pix;
+    uint32_t stride;
+    uint32_t n_src;          // slots of the source list (first slice: W * H, and the lists are not read)
+    uint32_t first;
+    uint32_t compact;        // 0: every sample keeps its slot and dst == src (A/B of the compaction)
+    uint32_t slice;          // steps per lane at most
+    uint32_t *dst_count;     // += samples still running
+    unsigned long long *stats; // [0] += lane slots occupied in the step loop, [1] += steps taken
+};
+// false: `limbs` is not an instantiated limb count (nothing launched)
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, hipStream_t s);
+// mask[y * W + x] = (first ? 1 : mask) & (centre == shifted) over two frames of the same pitch (elements)
+void fsk_exact_mask(const void *centre, const void *shifted, int iter_u64, uint8_t *mask, uint32_t W, uint32_t H, uint32_t pitch,
+                    int first, hipStream_t s);
 
 // multi-GPU tiler: out row y = in row index[y] (row_bytes a multiple of 16)
 void fsk_gather_rows(const void *in, void *out, const uint32_t *index, uint32_t row_bytes, uint32_t rows, hipStream_t s);

@@ -1,0 +1,149 @@
+// kernels_exact.hip -- the exact renderer (fs_render_exact, fs_exact_stable_mask): fixed-point escape counts, one lane per sample,
+// no reference orbit and no rounding anywhere (exact_math.hpp holds the arithmetic and the limb bound).
+//
+// A frame advances in slices of at most `slice` steps per lane.  Between slices the running samples live in device memory as
+// (x, y, n, pixel), limb-major: plane l of a list holds limb l of every slot, so a wave's loads and stores are contiguous.  A
+// slice reads list A and writes the samples that are still running to list B: a ballot and a prefix count inside the wave, ONE
+// atomic add per wave for the wave's block of slots.  The next slice then runs full waves instead of one slow lane per wave.
+// A sample that finishes writes its count into the frame at once.  c never changes: the lanes read their column's cx and their
+// row's cy (limb-major arrays of the whole axes) at the start of every slice.
+//
+// Counting: n is the index of the z the lane holds (z_1 = c).  The test comes first: an escape at n leaves n - 1; a z_{N+1} that
+// has not escaped leaves N.  That is min(E - 1, N) of every other path.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace {
+
+template <int L> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
+{
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    bool alive = i < A.n_src;
+    const uint32_t slot = alive ? i : 0u; // (a lane beyond the list reads slot 0 and writes nothing)
+    uint64_t n = 1;
+    uint32_t pix = slot;
+    if (!A.first) {
+        n = A.src_n[slot];
+        pix = A.src_pix[slot];
+        alive = alive && n != 0; // (without compaction a finished sample keeps its slot, marked n = 0)
+    }
+    if (__ballot(alive) == 0)
+        return;
+    const uint32_t col = pix % A.W, row = pix / A.W;
+    uint32_t x[L], y[L], cx[L], cy[L];
+#pragma unroll
+    for (int l = 0; l < L; l++) {
+        cx[l] = A.cx[(size_t)l * A.W + col];
+        cy[l] = A.cy[(size_t)l * A.H + row];
+    }
+    if (A.first) {
+#pragma unroll
+        for (int l = 0; l < L; l++)
+            x[l] = cx[l], y[l] = cy[l];
+    } else {
+#pragma unroll
+        for (int l = 0; l < L; l++) {
+            x[l] = A.src_xy[(size_t)l * A.stride + slot];
+            y[l] = A.src_xy[(size_t)(L + l) * A.stride + slot];
+        }
+    }
+
+    const size_t out_idx = (size_t)row * A.rounded_width + col;
+    uint32_t my_steps = 0, wave_steps = 0;
+    for (uint32_t k = 0; k < A.slice; k++) {
+        if (__ballot(alive) == 0)
+            break;
+        wave_steps++;
+        if (alive) {
+            my_steps++;
+            const bool escaped = fsx::step<L>(x, y, cx, cy, A.P);
+            if (escaped || n == A.cap + 1) {
+                const uint64_t v = escaped ? n - 1 : A.cap;
+                if (A.iter_u64)
+                    ((uint64_t *)A.iters)[out_idx] = v;
+                else
+                    ((uint32_t *)A.iters)[out_idx] = (uint32_t)v;
+                alive = false;
+            } else {
+                n++;
+            }
+        }
+    }
+
+    // the samples still running go to the next slice's list
+    const uint64_t live = __ballot(alive);
+    const uint32_t n_live = (uint32_t)__popcll(live);
+    uint32_t dst = i;
+    if (A.compact) {
+        uint32_t base = 0;
+        if (threadIdx.x == 0 && n_live != 0)
+            base = atomicAdd(A.dst_count, n_live);
+        base = __shfl(base, 0);
+        dst = base + (uint32_t)__popcll(live & ((1ull << threadIdx.x) - 1ull));
+    } else if (threadIdx.x == 0 && n_live != 0) {
+        atomicAdd(A.dst_count, n_live);
+    }
+    if (alive) {
+#pragma unroll
+        for (int l = 0; l < L; l++) {
+            A.dst_xy[(size_t)l * A.stride + dst] = x[l];
+            A.dst_xy[(size_t)(L + l) * A.stride + dst] = y[l];
+        }
+        A.dst_n[dst] = n;
+        A.dst_pix[dst] = pix;
+    } else if (!A.compact && i < A.n_src) {
+        A.dst_n[dst] = 0;
+        A.dst_pix[dst] = 0;
+    }
+
+    // lane slots the wave occupied in its step loop, and the steps its lanes really took
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        my_steps += __shfl_xor(my_steps, off);
+    if (threadIdx.x == 0) {
+        atomicAdd(&A.stats[0], 64ull * wave_steps);
+        atomicAdd(&A.stats[1], (unsigned long long)my_steps);
+    }
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_exact_mask(const T *__restrict__ centre, const T *__restrict__ shifted, uint8_t *__restrict__ mask,
+                                                     uint32_t W, uint32_t H, uint32_t pitch, int first)
+{
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= W * H)
+        return;
+    const size_t idx = (size_t)(p / W) * pitch + p % W;
+    const uint8_t same = centre[idx] == shifted[idx] ? 1 : 0;
+    mask[p] = first ? same : (uint8_t)(mask[p] & same);
+}
+
+} // namespace
+
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, hipStream_t s)
+{
+    const dim3 grid((A.n_src + 63u) / 64u), block(64);
+    switch (limbs) {
+#define FS_EXACT_CASE(L)                                                                                                \
+    case L:                                                                                                             \
+        hipLaunchKernelGGL(k_exact_slice<L>, grid, block, 0, s, A);                                                     \
+        return true;
+        FS_EXACT_FOR_EACH_L(FS_EXACT_CASE)
+#undef FS_EXACT_CASE
+    default:
+        return false;
+    }
+}
+
+void fsk_exact_mask(const void *centre, const void *shifted, int iter_u64, uint8_t *mask, uint32_t W, uint32_t H, uint32_t pitch,
+                    int first, hipStream_t s)
+{
+    const dim3 grid((W * H + 255u) / 256u), block(256);
+    if (iter_u64)
+        hipLaunchKernelGGL(k_exact_mask<uint64_t>, grid, block, 0, s, (const uint64_t *)centre, (const uint64_t *)shifted, mask, W, H,
+                           pitch, first);
+    else
+        hipLaunchKernelGGL(k_exact_mask<uint32_t>, grid, block, 0, s, (const uint32_t *)centre, (const uint32_t *)shifted, mask, W, H,
+                           pitch, first);
+}

@@ -192,6 +192,9 @@ struct fs_renderer {
     std::mutex kept_mu; // kept_blocks only: another renderer of the same device may drain them when IT runs out of memory
     size_t host_alloc_bytes = 0;
     uint32_t feature_slice = 0;      // fs_set_feature_slice (tests): steps per launch of the Feature Finder evaluators, 0 = default
+    uint32_t exact_slice = 0;        // fs_set_exact_slice (tests, tools): steps per lane per launch of the exact renderer, 0 = default
+    bool exact_no_compaction = false; // ... and its A/B switch: every sample keeps its slot from slice to slice
+    uint64_t exact_stats[4] = {};    // fs_read_exact_stats: what the last exact frame did
     uint32_t az_gather_rows = 0;     // fs_set_autozoom_gather_cap (tests): frame rows the FilamentTip gather buffer holds, 0 = default
     FsAzStats az_seed{};             // source of the stream-ordered seed copy in fs_autozoom_pick (must outlive the copy)
     bool inject_input_oom = false;   // fault injection: FSMI355_FAIL_INPUT_ALLOC=1 at fs_create time
@@ -2537,6 +2540,196 @@ uint32_t fs_autozoom_pick(fs_renderer *r, int heuristic, uint64_t n_iterations, 
         out->status = st.sum == 0 || best < 0 ? FS_AUTOZOOM_NO_TARGET : st.num_at_max > n_rect / 2 ? FS_AUTOZOOM_FLAT : FS_AUTOZOOM_MOVE;
     }
     return 0;
+}
+
+// ---- fs_render_exact / fs_exact_stable_mask: the host side (kernels_exact.hip, exact_math.hpp).
+// Steps per lane per launch: at most 4096 -- one wave's pace with 24 limbs is 11.7 us per step, 48 ms a launch --
+// and fewer when the list is long enough to fill the chip several times over: the chip sustains 5.6e9 lane steps per second with 24
+// limbs and about (24 / L)^2 times that with L, so 1.5e11 / L^2 lane steps per launch keep a launch near 50 ms at any frame size and
+// limb count.  As the compaction shortens the list the slices grow back to 4096.  Never under 64: a launch is not worth less.
+static constexpr uint32_t kExactSlice = 4096, kExactSliceMin = 64;
+static uint32_t exact_default_slice(uint32_t limbs, uint32_t n_src)
+{
+    const uint64_t k = (uint64_t)(1.5e11 / ((double)limbs * limbs)) / (n_src ? n_src : 1u);
+    return (uint32_t)(k > kExactSlice ? kExactSlice : k < kExactSliceMin ? kExactSliceMin : k);
+}
+
+uint32_t fs_set_exact_slice(fs_renderer *r, uint32_t steps, int no_compaction)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    r->exact_slice = steps;
+    r->exact_no_compaction = no_compaction != 0;
+    return 0;
+}
+
+uint32_t fs_read_exact_stats(const fs_renderer *r, uint64_t out[4])
+{
+    if (!r || !out)
+        return hipErrorInvalidValue;
+    memcpy(out, r->exact_stats, sizeof r->exact_stats);
+    return 0;
+}
+
+// What both entry points refuse, in the order the header lists it.
+static uint32_t exact_begin(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, uint32_t bailout, uint64_t n_iterations)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (!r->memory_initialized() || !r->compute)
+        return FS_ERR_6;
+    if (r->local_rows != r->height)
+        return FS_ERR_UNSUPPORTED; // this renderer holds some rows of the frame only
+    if (limbs < fsx::kMinLimbs || limbs > fsx::kMaxLimbs || 32u * limbs < frac_bits + 10u || bailout < 1 ||
+        bailout > fsx::kMaxBailout)
+        return FS_ERR_UNSUPPORTED;
+    if ((n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8) || n_iterations == ~0ull ||
+        (uint64_t)r->width * r->height > 0xFFFFFFFFull)
+        return (uint32_t)hipErrorInvalidValue;
+    return 0;
+}
+
+// every value of a limb-major axis (n values of `limbs` limbs) in [-32 * 2^F, 32 * 2^F): bits F + 5 and up all equal the sign
+static bool exact_axis_in_range(const uint32_t *axis, uint32_t n, uint32_t limbs, uint32_t frac_bits)
+{
+    const uint32_t lo = frac_bits + fsx::kCBoundLog2;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t ext = 0u - (axis[(size_t)(limbs - 1) * n + i] >> 31);
+        for (uint32_t l = lo / 32; l < limbs; l++) {
+            const uint32_t mask = l == lo / 32 ? ~0u << (lo % 32) : ~0u;
+            if ((axis[(size_t)l * n + i] ^ ext) & mask)
+                return false;
+        }
+    }
+    return true;
+}
+
+// One exact frame into `out` (a buffer of the iteration buffer's geometry).  One device block per call: [counter, statistics | cx |
+// cy | two lists of running samples]; synchronous.
+static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                            uint32_t bailout, int inclusive, uint64_t n_iterations, void *out)
+{
+    const uint32_t W = r->width, H = r->height, npix = W * H;
+    const size_t head = 256;
+    const size_t cx_bytes = ((size_t)limbs * W * 4 + 255) / 256 * 256, cy_bytes = ((size_t)limbs * H * 4 + 255) / 256 * 256;
+    const size_t xy_bytes = ((size_t)2 * limbs * npix * 4 + 255) / 256 * 256, n_bytes = ((size_t)npix * 8 + 255) / 256 * 256,
+                 pix_bytes = ((size_t)npix * 4 + 255) / 256 * 256;
+    const size_t list_bytes = xy_bytes + n_bytes + pix_bytes;
+    const bool compact = !r->exact_no_compaction;
+    char *blk = nullptr;
+    hipStream_t s = r->compute;
+    FS_TRY(r_alloc(r, (void **)&blk, head + cx_bytes + cy_bytes + (compact ? 2 : 1) * list_bytes, kFrame));
+    uint32_t *d_cnt = (uint32_t *)blk;
+    unsigned long long *d_stats = (unsigned long long *)(blk + 16);
+    uint32_t *d_cx = (uint32_t *)(blk + head), *d_cy = (uint32_t *)(blk + head + cx_bytes);
+    char *lists[2] = {blk + head + cx_bytes + cy_bytes, blk + head + cx_bytes + cy_bytes + (compact ? list_bytes : 0)};
+
+    FsExactArgs A{};
+    A.cx = d_cx, A.cy = d_cy;
+    A.W = W, A.H = H, A.rounded_width = r->w_block * 16u;
+    A.iter_u64 = r->iter_bytes == 8 ? 1u : 0u;
+    A.iters = out;
+    A.cap = n_iterations;
+    A.P = fsx::make_params(frac_bits, bailout, inclusive);
+    A.stride = npix;
+    A.n_src = npix;
+    A.first = 1;
+    A.compact = compact ? 1u : 0u;
+    A.dst_count = d_cnt;
+    A.stats = d_stats;
+
+    uint64_t slices = 0, after_first = 0;
+    hipError_t e = hipMemsetAsync(blk, 0, head, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_cx, cx, (size_t)limbs * W * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_cy, cy, (size_t)limbs * H * 4, hipMemcpyHostToDevice, s);
+    while (e == hipSuccess) {
+        char *src = lists[(slices & 1) ^ 1], *dst = lists[slices & 1];
+        A.src_xy = (const uint32_t *)src, A.src_n = (const uint64_t *)(src + xy_bytes), A.src_pix = (const uint32_t *)(src + xy_bytes + n_bytes);
+        A.dst_xy = (uint32_t *)dst, A.dst_n = (uint64_t *)(dst + xy_bytes), A.dst_pix = (uint32_t *)(dst + xy_bytes + n_bytes);
+        uint32_t left = 0;
+        A.slice = r->exact_slice ? r->exact_slice : exact_default_slice(limbs, A.n_src);
+        e = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), s);
+        if (e != hipSuccess)
+            break;
+        if (!fsk_exact_slice(A, limbs, s)) {
+            e = hipErrorInvalidValue;
+            break;
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(&left, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (e != hipSuccess)
+            break;
+        if (slices++ == 0)
+            after_first = left;
+        if (left == 0)
+            break;
+        A.first = 0;
+        if (compact)
+            A.n_src = left;
+    }
+    unsigned long long st[2] = {0, 0};
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(st, d_stats, sizeof st, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    r->exact_stats[0] += st[0], r->exact_stats[1] += st[1], r->exact_stats[2] += slices, r->exact_stats[3] += after_first;
+    (void)r_free(r, blk);
+    return (uint32_t)e;
+}
+
+uint32_t fs_render_exact(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                         uint32_t bailout, int inclusive, uint64_t n_iterations)
+{
+    if (uint32_t e = exact_begin(r, frac_bits, limbs, bailout, n_iterations))
+        return e;
+    if (iter_bytes != 4 && iter_bytes != 8)
+        return FS_ERR_UNSUPPORTED;
+    if (iter_bytes != r->iter_bytes || !cx || !cy)
+        return (uint32_t)hipErrorInvalidValue;
+    if (!exact_axis_in_range(cx, r->width, limbs, frac_bits) || !exact_axis_in_range(cy, r->height, limbs, frac_bits))
+        return FS_ERR_UNSUPPORTED;
+    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    return exact_frame(r, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations, r->iters());
+}
+
+uint32_t fs_exact_stable_mask(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *const cx[3], const uint32_t *const cy[3],
+                              uint32_t bailout, uint64_t n_iterations, uint8_t *host_mask)
+{
+    if (uint32_t e = exact_begin(r, frac_bits, limbs, bailout, n_iterations))
+        return e;
+    if (!cx || !cy || !host_mask)
+        return (uint32_t)hipErrorInvalidValue;
+    for (int k = 0; k < 3; k++) {
+        if (!cx[k] || !cy[k])
+            return (uint32_t)hipErrorInvalidValue;
+        if (!exact_axis_in_range(cx[k], r->width, limbs, frac_bits) || !exact_axis_in_range(cy[k], r->height, limbs, frac_bits))
+            return FS_ERR_UNSUPPORTED;
+    }
+    const uint32_t W = r->width, H = r->height, pitch = r->w_block * 16u;
+    const size_t frame_bytes = ((size_t)pitch * r->local_rows_padded * r->iter_bytes + 255) / 256 * 256;
+    char *blk = nullptr;
+    FS_TRY(r_alloc(r, (void **)&blk, frame_bytes + (size_t)W * H, kFrame));
+    uint8_t *d_mask = (uint8_t *)(blk + frame_bytes);
+    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    uint32_t rc = 0;
+    for (int d = 0; d < 4 && rc == 0; d++) { // c + s, c - s, c + is, c - is
+        rc = exact_frame(r, frac_bits, limbs, d < 2 ? cx[1 + d] : cx[0], d < 2 ? cy[0] : cy[d - 1], bailout, 0, n_iterations, blk);
+        if (rc == 0) {
+            fsk_exact_mask(r->iters(), blk, r->iter_bytes == 8, d_mask, W, H, pitch, d == 0, r->compute);
+            rc = (uint32_t)hipGetLastError();
+        }
+    }
+    if (rc == 0)
+        rc = (uint32_t)hipMemcpyAsync(host_mask, d_mask, (size_t)W * H, hipMemcpyDeviceToHost, r->compute);
+    if (rc == 0)
+        rc = (uint32_t)hipStreamSynchronize(r->compute);
+    (void)r_free(r, blk);
+    return rc;
 }
 
 // How every fs_render_* begins.  kNoFrame: return *rc now -- the HIP error of a device that cannot be selected, else 0: there is

@@ -1,0 +1,62 @@
+"""The exact renderer: fixed-point escape counts at any depth on the GPU, with no reference orbit and no rounding.
+
+The render path of the reference's CpuHigh (CalcCpuHDR<IterType, HighPrecision, double>, Fractal.cpp:1200-1201, 2096-2206): every
+sample is iterated by itself in high precision.  Here that is integer arithmetic on 32-bit limbs (csrc/exact_math.hpp,
+csrc/kernels_exact.hip): x' = floor((x^2 - y^2) / 2^F) + cx, y' = floor(2xy / 2^F) + cy, escape when x^2 + y^2 > R 2^2F.  The frame
+equals GMP integer iteration of that recurrence on every pixel, and is an ordinary frame in the renderer's iteration buffer:
+min(E - 1, N) like every other path.  The axes come from the view's bounding-box strings read as exact rationals
+(fsh_view_exact_axes).
+"""
+import numpy as np
+
+GUARD_BITS = 64  # default frac_bits = the view's precision + this
+MIN_LIMBS, MAX_LIMBS = 2, 24  # instantiated limb counts (csrc/exact_math.hpp)
+MAX_FRAC_BITS = 32 * MAX_LIMBS - 10
+
+
+def limbs_for(frac_bits):
+    """The limb count a frac_bits needs: ceil((F + 10) / 32) (the bound is derived in csrc/exact_math.hpp), at least 2."""
+    return max(MIN_LIMBS, (int(frac_bits) + 10 + 31) // 32)
+
+
+def axes(view, frac_bits, level=None, limbs=None):
+    """(cx, cy) = uint32[limbs, W], uint32[limbs, H]: c * 2^frac_bits per column / row of the antialiased frame, two's complement,
+    limb-major.  With a ladder level, (cx3, cy3) = uint32[3, limbs, W], uint32[3, limbs, H]: the axes c, c + s, c - s with
+    s = (maxX - minX) / 2^level."""
+    limbs = limbs_for(frac_bits) if limbs is None else int(limbs)
+    w, h = view.width * view.antialiasing, view.height * view.antialiasing
+    n = 1 if level is None else 3
+    cx, cy = np.zeros((n, limbs, w), np.uint32), np.zeros((n, limbs, h), np.uint32)
+    if view._lib.fsh_view_exact_axes(view._h, w, h, int(frac_bits), -1 if level is None else int(level), limbs, cx.ctypes.data,
+                                     cy.ctypes.data) != 0:
+        raise ValueError("fsh_view_exact_axes: the view does not fit %d limbs at %d fractional bits" % (limbs, frac_bits))
+    return (cx[0], cy[0]) if level is None else (cx, cy)
+
+
+def _check(renderer, err, what):
+    if err:
+        raise RuntimeError("%s failed: %d (%s)" % (what, err, renderer.ConvertErrorToString(err)))
+
+
+def render(renderer, view, bailout=4, frac_bits=None, iter_bytes=4, inclusive=False):
+    """The view's exact frame into the renderer's iteration buffer (InitializeMemory with the view's antialiased size and
+    iter_bytes comes first), view.num_iterations the cap.  frac_bits defaults to view.precision_bits + 64.  Has the shape
+    autozoom.zoom wants for its `render` argument."""
+    F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
+    L = limbs_for(F)
+    cx, cy = axes(view, F, limbs=L)
+    _check(renderer, renderer.RenderExact(iter_bytes, F, L, cx, cy, bailout, inclusive, view.num_iterations), "fs_render_exact")
+
+
+def stable_mask(renderer, view, level, bailout=4, frac_bits=None):
+    """bool[H, W]: the pixels of the exact frame in the iteration buffer (exact.render of the same view, bailout and frac_bits,
+    strict) whose count is the same at c +- s and c +- is, s = the frame's width / 2^level."""
+    F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
+    L = limbs_for(F)
+    cx3, cy3 = axes(view, F, level=level, limbs=L)
+    err, mask = renderer.ExactStableMask(F, L, cx3, cy3, bailout, view.num_iterations)
+    _check(renderer, err, "fs_exact_stable_mask")
+    return mask.astype(bool)
+
+
+__all__ = ["GUARD_BITS", "MAX_FRAC_BITS", "limbs_for", "axes", "render", "stable_mask"]

@@ -558,6 +558,133 @@ extern "C" int fsh_view_bbox_str(const fsh_view *v, int which, char *buf, size_t
     return gmp_snprintf(buf, buflen, "%.Fe", p->v);
 }
 
+// ------------------------------------------------------------------ exact renderer axes (this project's addition)
+namespace {
+
+// "[-]d.ddde[+-]XX" or plain "[-]ddd.ddd" -> the exact rational it denotes
+bool decimal_to_mpq(const char *s, mpq_t out)
+{
+    std::string digits;
+    bool neg = false, point = false;
+    long frac = 0, exp10 = 0;
+    const char *p = s;
+    if (*p == '-' || *p == '+')
+        neg = *p++ == '-';
+    for (; *p; p++) {
+        if (*p >= '0' && *p <= '9') {
+            digits.push_back(*p);
+            frac += point ? 1 : 0;
+        } else if (*p == '.' && !point) {
+            point = true;
+        } else if (*p == 'e' || *p == 'E') {
+            char *end = nullptr;
+            exp10 = strtol(p + 1, &end, 10);
+            if (end == p + 1 || *end)
+                return false;
+            break;
+        } else {
+            return false;
+        }
+    }
+    if (digits.empty())
+        return false;
+    mpz_t ten;
+    mpz_init(ten);
+    mpz_set_str(mpq_numref(out), digits.c_str(), 10);
+    mpz_set_ui(mpq_denref(out), 1);
+    if (neg)
+        mpz_neg(mpq_numref(out), mpq_numref(out));
+    const long e = exp10 - frac;
+    mpz_ui_pow_ui(ten, 10, (unsigned long)(e < 0 ? -e : e));
+    if (e < 0)
+        mpz_set(mpq_denref(out), ten);
+    else
+        mpz_mul(mpq_numref(out), mpq_numref(out), ten);
+    mpz_clear(ten);
+    mpq_canonicalize(out);
+    return true;
+}
+
+// floor(q 2^F) as `limbs` two's-complement limbs at out[l * stride]; false when it does not fit
+bool put_fixed(const mpq_t q, uint32_t F, uint32_t limbs, uint32_t *out, size_t stride, mpz_t t, mpz_t lim)
+{
+    mpz_mul_2exp(t, mpq_numref(q), F);
+    mpz_fdiv_q(t, t, mpq_denref(q));
+    mpz_set_ui(lim, 1);
+    mpz_mul_2exp(lim, lim, 32 * limbs - 1);
+    if (mpz_cmp(t, lim) >= 0)
+        return false;
+    mpz_neg(lim, lim);
+    if (mpz_cmp(t, lim) < 0)
+        return false;
+    if (mpz_sgn(t) < 0) { // t + 2^(32 limbs)
+        mpz_mul_2exp(lim, lim, 1);
+        mpz_sub(t, t, lim);
+    }
+    for (uint32_t l = 0; l < limbs; l++) {
+        out[l * stride] = (uint32_t)mpz_get_ui(t);
+        mpz_fdiv_q_2exp(t, t, 32);
+    }
+    return true;
+}
+
+} // namespace
+
+extern "C" int fsh_view_exact_axes(const fsh_view *v, uint32_t w_aa, uint32_t h_aa, uint32_t frac_bits, int shift_level,
+                                   uint32_t limbs, uint32_t *cx3, uint32_t *cy3)
+{
+    if (!v || !w_aa || !h_aa || !limbs || !cx3 || !cy3)
+        return -1;
+    mpq_t b[4], span[2], q, c, sh;
+    mpz_t t, lim;
+    for (auto &x : b)
+        mpq_init(x);
+    mpq_inits(span[0], span[1], q, c, sh, nullptr);
+    mpz_inits(t, lim, nullptr);
+    bool ok = true;
+    for (int k = 0; k < 4 && ok; k++) {
+        char one[1];
+        const int n = fsh_view_bbox_str(v, k, one, sizeof one);
+        std::string s((size_t)(n > 0 ? n : 0) + 1, '\0');
+        ok = n > 0 && fsh_view_bbox_str(v, k, &s[0], s.size()) == n && decimal_to_mpq(s.c_str(), b[k]);
+    }
+    if (ok) {
+        mpq_sub(span[0], b[2], b[0]); // maxX - minX
+        mpq_sub(span[1], b[3], b[1]); // maxY - minY
+        mpq_set(sh, span[0]);
+        if (shift_level >= 0)
+            mpq_div_2exp(sh, sh, (mp_bitcnt_t)shift_level);
+        const int n_axes = shift_level >= 0 ? 3 : 1;
+        for (int axis = 0; axis < 2 && ok; axis++) {
+            const uint32_t n = axis == 0 ? w_aa : h_aa;
+            uint32_t *out = axis == 0 ? cx3 : cy3;
+            for (uint32_t i = 0; i < n && ok; i++) {
+                mpq_set_ui(q, i, n);
+                mpq_canonicalize(q);
+                mpq_mul(c, span[axis], q);
+                if (axis == 0)
+                    mpq_add(c, b[0], c);
+                else
+                    mpq_sub(c, b[3], c);
+                for (int a = 0; a < n_axes && ok; a++) {
+                    if (a == 0)
+                        mpq_set(q, c);
+                    else if (a == 1)
+                        mpq_add(q, c, sh);
+                    else
+                        mpq_sub(q, c, sh);
+                    ok = put_fixed(q, frac_bits, limbs, out + (size_t)a * limbs * n + i, n, t, lim);
+                }
+            }
+        }
+    }
+    for (auto &x : b)
+        mpq_clear(x);
+    mpq_clears(span[0], span[1], q, c, sh, nullptr);
+    mpz_clears(t, lim, nullptr);
+    return ok ? 0 : -1;
+}
+
 // Cpu64 / direct kernels: dx, dy, minX, maxY as doubles -- Fractal.cpp:2118-2119,2148-2151
 // (T(HighPrecision) for T=double is mpf_get_d, HighPrecision.h:497-501).
 extern "C" void fsh_view_coords_direct_f64(const fsh_view *v, uint32_t w_aa, uint32_t h_aa, double out[4])

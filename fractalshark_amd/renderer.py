@@ -165,6 +165,39 @@ class GPURenderer:
         """Test hook (fs_set_autozoom_gather_cap): frame rows the FilamentTip gather buffer holds, 0 = default."""
         return self._lib.fs_set_autozoom_gather_cap(self._h, int(rows))
 
+    def RenderExact(self, iter_bytes, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations):
+        """fs_render_exact: the exact fixed-point frame into the iteration buffer (include/fsmi355.h).  cx, cy = uint32[limbs, W] /
+        uint32[limbs, H] (exact.axes).  Synchronous."""
+        cx, cy = np.ascontiguousarray(cx, np.uint32), np.ascontiguousarray(cy, np.uint32)
+        if cx.shape != (limbs, self.GetWidth()) or cy.shape != (limbs, self.GetHeight()):
+            raise ValueError("cx, cy must be uint32[limbs, W] and uint32[limbs, H] of the initialised frame")
+        return self._lib.fs_render_exact(self._h, int(iter_bytes), int(frac_bits), int(limbs), cx.ctypes.data, cy.ctypes.data,
+                                         int(bailout), 1 if inclusive else 0, int(n_iterations))
+
+    def ExactStableMask(self, frac_bits, limbs, cx3, cy3, bailout, n_iterations):
+        """fs_exact_stable_mask: (error code, uint8[H, W]) -- 1 where the four frames shifted by s equal the exact frame in the
+        iteration buffer.  cx3, cy3 = uint32[3, limbs, W] / uint32[3, limbs, H]: the axes c, c + s, c - s.  Synchronous."""
+        cx3, cy3 = np.ascontiguousarray(cx3, np.uint32), np.ascontiguousarray(cy3, np.uint32)
+        w, h = self.GetWidth(), self.GetHeight()
+        if cx3.shape != (3, limbs, w) or cy3.shape != (3, limbs, h):
+            raise ValueError("cx3, cy3 must be uint32[3, limbs, W] and uint32[3, limbs, H] of the initialised frame")
+        px = (C.c_void_p * 3)(*[cx3[k].ctypes.data for k in range(3)])
+        py = (C.c_void_p * 3)(*[cy3[k].ctypes.data for k in range(3)])
+        mask = np.zeros((h, w), np.uint8)
+        err = self._lib.fs_exact_stable_mask(self._h, int(frac_bits), int(limbs), px, py, int(bailout), int(n_iterations),
+                                             mask.ctypes.data)
+        return err, mask
+
+    def SetExactSlice(self, steps, no_compaction=False):
+        """Test hook (fs_set_exact_slice): steps per sample per launch of the exact renderer, 0 = default; no_compaction: A/B."""
+        return self._lib.fs_set_exact_slice(self._h, int(steps), 1 if no_compaction else 0)
+
+    def exact_stats(self):
+        """fs_read_exact_stats of the last exact call: {lane_slots, lane_steps, launches, running_after_first_slice}."""
+        out = (C.c_uint64 * 4)()
+        self._lib.fs_read_exact_stats(self._h, out)
+        return dict(zip(("lane_slots", "lane_steps", "launches", "running_after_first_slice"), (int(v) for v in out)))
+
     def _feature_eval(self, entry, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
         from . import features
         din, dout, dreal = features.records(T == T_HDR64)

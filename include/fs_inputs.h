@@ -64,6 +64,15 @@ int fsh_orbit_save_im(const fsh_orbit *o, uint64_t num_iterations, int compressi
 fsh_orbit *fsh_orbit_load_im(const char *path, uint64_t *iteration_limit);
 /* which: 0=minX 1=minY 2=maxX 3=maxY; printf("%.Fe") of the squared bounding box. */
 int fsh_view_bbox_str(const fsh_view *v, int which, char *buf, size_t buflen);
+/* The axes of the exact renderer (fs_render_exact / fs_exact_stable_mask of fsmi355.h).  The four strings of fsh_view_bbox_str are
+ * read back as exact rationals -- they ARE the view as far as an exact count is concerned -- and
+ *   cx[x] = floor((minX + x (maxX - minX) / w_aa) 2^frac_bits),  cy[y] = floor((maxY - y (maxY - minY) / h_aa) 2^frac_bits)
+ * are written as two's-complement numbers of `limbs` 32-bit limbs, limb-major: cx3[l * w_aa + x], cy3[l * h_aa + y].
+ * shift_level >= 0: three axes each, back to back (limbs * w_aa resp. limbs * h_aa words apart): c, c + s and c - s with
+ * s = (maxX - minX) / 2^shift_level (the same length on both axes).  shift_level < 0: the first axis only.
+ * Returns 0; -1 when a string cannot be read, limbs or a size is zero, or a value does not fit `limbs` limbs with its sign. */
+int fsh_view_exact_axes(const fsh_view *v, uint32_t w_aa, uint32_t h_aa, uint32_t frac_bits, int shift_level, uint32_t limbs,
+                        uint32_t *cx3, uint32_t *cy3);
 
 /* out = {dx, dy, minX, maxY} as un-reduced HDRFloat (CpuHDR32 / CpuHDR64 direct kernels). */
 void fsh_view_coords_direct_hdr32(const fsh_view *v, uint32_t w_aa, uint32_t h_aa, fs_real_hdr32 out[4]);

@@ -297,6 +297,30 @@ uint32_t fs_render_scaled(fs_renderer *r, int type_tag, const void *coords, uint
 uint32_t fs_render_direct_lp(fs_renderer *r, int type_tag, const void *coords, uint64_t n_iterations,
                              int iteration_precision);
 
+/* The exact renderer (this project's addition; the render path of the reference's CpuHigh, CalcCpuHDR<IterType, HighPrecision,
+ * double>, Fractal.cpp:1200-1201, 2096-2206, at any depth and without a reference orbit).  Every sample is iterated in
+ * fixed point with frac_bits fractional bits on integers of `limbs` 32-bit limbs,
+ *     x' = floor((x^2 - y^2) / 2^F) + cx,   y' = floor(2 x y / 2^F) + cy,   escape when x^2 + y^2 > R 2^2F (>= when inclusive),
+ * with no rounding anywhere: the frame equals GMP integer iteration of the same recurrence on every pixel.
+ * cx, cy: the axes, c * 2^F as two's-complement numbers of `limbs` limbs, limb-major over the W x H of fs_init_memory
+ * (cx[l * W + x], cy[l * H + y]; fsh_view_exact_axes of fs_inputs.h makes them).  bailout = R, an integer.
+ * The frame is an ordinary one in the renderer's iteration buffer: with E the first n >= 1 with |z_n|^2 > R (z_1 = c), a pixel
+ * holds min(E - 1, n_iterations), and n_iterations when there is no escape within n_iterations + 1 -- the convention of every
+ * other path.  fs_render_current, the reductions and fs_autozoom_pick work on it unchanged.  Synchronous on the compute stream; the
+ * orbit and LA caches, recorded tile costs and orders and the kernel-time history are left as they were.
+ * FS_ERR_6: no fs_init_memory yet.  FS_ERR_UNSUPPORTED: row bands set (fs_set_row_bands); iter_bytes not 4 or 8; limbs outside
+ * 2 .. 24 or 32 * limbs < frac_bits + 10 (so frac_bits <= 758); bailout outside 1 .. 256; an axis value outside [-32, 32).
+ * hipErrorInvalidValue: iter_bytes is not the frame's, a NULL axis, an n_iterations the frame's IterType cannot hold. */
+uint32_t fs_render_exact(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx,
+                         const uint32_t *cy, uint32_t bailout, int inclusive, uint64_t n_iterations);
+/* Which pixels of the exact frame in the iteration buffer (the centre frame, rendered with the same frac_bits, bailout and
+ * n_iterations, strict bailout) keep their count when c moves by s: cx[3], cy[3] = the axes {c, c + s, c - s} (fsh_view_exact_axes
+ * with a shift level).  The four frames at c + s, c - s, c + is, c - is are rendered into scratch memory and compared with the
+ * centre frame on the device; host_mask[y * W + x] = 1 where all four equal it, else 0.  The iteration buffer is not written.
+ * Synchronous; errors as fs_render_exact. */
+uint32_t fs_exact_stable_mask(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *const cx[3],
+                              const uint32_t *const cy[3], uint32_t bailout, uint64_t n_iterations, uint8_t *host_mask);
+
 /* GPURenderer::ClearMemory<IterType> (GPU_Render.cu:212-225). */
 uint32_t fs_clear(fs_renderer *r);
 

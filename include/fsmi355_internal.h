@@ -99,6 +99,16 @@ uint32_t fs_set_feature_slice(fs_renderer *r, uint32_t steps);
  * 32.  When more candidates qualify than fit, the gather is repeated over bands of rows: a small cap exercises that path.
  * Changes no result. */
 uint32_t fs_set_autozoom_gather_cap(fs_renderer *r, uint32_t rows);
+/* Test and measurement hooks of the exact renderer (fs_render_exact, fs_exact_stable_mask).
+ * fs_set_exact_slice: steps per sample per launch; 0 = the default: 4096, fewer while the list of running samples is long enough to
+ * make such a launch last more than about 50 ms, never under 64.  A small slice makes a frame of hundreds of launches and
+ * exercises the sample state that is carried from one to the next.  no_compaction = 1 (A/B): the running samples keep their slots
+ * from slice to slice instead of being packed into full waves.  Neither changes a pixel.
+ * fs_read_exact_stats: what the last call did, summed over its frames: out[0] = lane slots its waves occupied in the step loop
+ * (64 x the steps of each wave's longest lane, per slice), [1] = steps its samples took, [2] = launches, [3] = samples still
+ * running after each frame's first slice. */
+uint32_t fs_set_exact_slice(fs_renderer *r, uint32_t steps, int no_compaction);
+uint32_t fs_read_exact_stats(const fs_renderer *r, uint64_t out[4]);
 uint32_t fs_enable_step_count(fs_renderer *r, int enable);
 uint32_t fs_read_step_count(fs_renderer *r, uint64_t counts[8]);
 /* The whole statistics buffer (measurement builds append per-wave trace records behind the 8 counters: library built

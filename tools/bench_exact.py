@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""The exact renderer (fs_render_exact) measured: the numbers of DESIGN.md 6.3.
+
+  pace      per limb count L: microseconds per step of a wave whose 64 samples never escape, from the difference of two frames of
+            8 waves (one per workgroup, so each has a compute unit's SIMD to itself) that differ in the cap only; and the chip-wide
+            rate of 32 x 32 -> 64 multiply-adds with every SIMD full (a 1024 x 1024 frame of never-escaping samples; a step is
+            2 L^2 + L multiply-adds: two squares of L (L + 1) / 2 each and one product of L^2)
+  frames    View 0 at 1024 x 768 (R 4), shallow_1e-28 at 1920 x 1080 (R 256) and View 5 at 1920 x 1080 (R 256; --view5, minutes),
+            each with the share of lane slots spent on finished lanes with and without the compaction, and against the GMP counter on 16
+            threads: the counter is timed on a lattice of the frame's samples and SCALED to the frame's sample count
+  c3        (with --view5) how many pixels of the HDRFloat<float> LAv2 frame of View 5 at 1920 x 1080 differ from the exact frame: a
+            recorded characterisation, not a test
+
+Times are host clocks around synchronous calls.  One JSON line per measurement.
+
+  python tools/bench_exact.py [--pace] [--frames] [--view5] [--limbs 2,4,7,8,11,12,16,20,23,24]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from fractalshark_amd import GPURenderer, LAV2_FULL, PARITY_CPU, T_HDR32, exact, inputs  # noqa: E402
+import _truth  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--pace", action="store_true")
+ap.add_argument("--frames", action="store_true")
+ap.add_argument("--view5", action="store_true")
+ap.add_argument("--limbs", default="2,4,7,8,11,12,16,20,23,24")
+args = ap.parse_args()
+if not (args.pace or args.frames or args.view5):
+    args.pace = args.frames = True
+
+
+def say(**kw):
+    print(json.dumps(kw), flush=True)
+
+
+def inside_axes(L, w, h, F):
+    """Axes of a w x h frame around c = -0.1 + 0.1i (inside the main cardioid: no sample ever escapes), spacing 2^-30."""
+    val = lambda q, i: (int(q * (1 << 40)) << (F - 40)) + (i << (F - 30))
+    limbs = lambda v: [(v >> (32 * l)) & 0xFFFFFFFF for l in range(L)]
+    cx = np.array([limbs(val(-0.1, i)) for i in range(w)], np.uint32).T.copy()
+    cy = np.array([limbs(val(0.1, i)) for i in range(h)], np.uint32).T.copy()
+    return cx, cy
+
+
+def timed_render(r, F, L, cx, cy, R, n):
+    t0 = time.perf_counter()
+    err = r.RenderExact(4, F, L, cx, cy, R, False, n)
+    dt = time.perf_counter() - t0
+    assert err == 0, err
+    return dt
+
+
+r = GPURenderer(0)
+
+if args.pace:
+    r.SetExactSlice(4096)  # (the default shortens the slices of a frame that fills the chip)
+    for L in [int(s) for s in args.limbs.split(",")]:
+        F = 32 * L - 10
+        # eight waves, one per workgroup
+        assert r.InitializeMemory(64, 8, 1, None, 0, 0, 0, False) == 0
+        cx, cy = inside_axes(L, 64, 8, F)
+        n1, n2 = 4096, 4096 * 9
+        timed_render(r, F, L, cx, cy, 4, n1)
+        t1 = min(timed_render(r, F, L, cx, cy, 4, n1) for _ in range(3))
+        t2 = min(timed_render(r, F, L, cx, cy, 4, n2) for _ in range(3))
+        us_step = (t2 - t1) / (n2 - n1) * 1e6
+        # every SIMD full
+        assert r.InitializeMemory(1024, 1024, 1, None, 0, 0, 0, False) == 0
+        cx, cy = inside_axes(L, 1024, 1024, F)
+        m1, m2 = 64, 64 + (512 if L <= 12 else 128)
+        timed_render(r, F, L, cx, cy, 4, m1)
+        u1 = min(timed_render(r, F, L, cx, cy, 4, m1) for _ in range(2))
+        u2 = min(timed_render(r, F, L, cx, cy, 4, m2) for _ in range(2))
+        lane_steps = (m2 - m1) * 1024 * 1024 / (u2 - u1)
+        say(what="pace", limbs=L, frac_bits=F, wave_us_per_step=round(us_step, 4), slice_of_4096_ms=round(us_step * 4096 / 1000, 2),
+            chip_lane_steps_per_s=round(lane_steps), chip_gmad_per_s=round(lane_steps * (2 * L * L + L) / 1e9, 1))
+
+
+r.SetExactSlice(0)
+
+
+def gmp_seconds(v, w, h, R, F, cap, cols, rows):
+    """The GMP counter (16 threads) on a cols x rows lattice of the frame, and that time scaled to all w * h samples."""
+    xs, ys = _truth.lattice(w, h, cols, rows)
+    t0 = time.perf_counter()
+    _truth.exact_counts(v.bbox(), w, h, xs, ys, cap + 1, R, F, shifts=[])
+    dt = time.perf_counter() - t0
+    return dt, len(xs), dt * w * h / len(xs)
+
+
+def frame(name, v, w, h, R, F, cap, lattice, both_modes=True):
+    v.num_iterations = cap
+    L = exact.limbs_for(F)
+    cx, cy = exact.axes(v, F, limbs=L)
+    assert r.InitializeMemory(w, h, 1, None, 0, 0, 0, False) == 0
+    out = {}
+    for mode in (("compaction", "no_compaction") if both_modes else ("compaction",)):
+        r.SetExactSlice(0, no_compaction=mode == "no_compaction")
+        timed_render(r, F, L, cx, cy, R, min(cap, 64))  # (memory and code warm)
+        dt = timed_render(r, F, L, cx, cy, R, cap)
+        st = r.exact_stats()
+        out[mode] = dict(seconds=round(dt, 4), launches=st["launches"], lane_steps=st["lane_steps"], lane_slots=st["lane_slots"],
+                         finished_lane_share=round(1 - st["lane_steps"] / max(1, st["lane_slots"]), 4))
+    r.SetExactSlice(0)
+    g_dt, g_n, g_scaled = gmp_seconds(v, w, h, R, F, cap, *lattice)
+    say(what="frame", name=name, width=w, height=h, bailout=R, frac_bits=F, limbs=L, cap=cap, **out,
+        gmp16_lattice_samples=g_n, gmp16_lattice_seconds=round(g_dt, 3), gmp16_scaled_to_frame_seconds=round(g_scaled, 1),
+        speedup_vs_scaled_gmp16=round(g_scaled / out["compaction"]["seconds"], 1))
+
+
+if args.frames:
+    c = _truth.Case("view0_1024x768")
+    frame("view0_1024x768", c.view(inputs), c.w, c.h, 4, c.raw["frac_bits"], c.cap, (64, 48))
+    c = _truth.Case("shallow_1e-28")
+    b = c.raw["bbox"]
+    v = inputs.View(b[0], b[1], b[2], b[3], 1920, 1080, num_iterations=c.cap)
+    frame("shallow_1e-28 at 1920x1080", v, 1920, 1080, 256, v.precision_bits + exact.GUARD_BITS, c.cap, (64, 36))
+
+if args.view5:
+    c = _truth.Case("view5_1920x1080")
+    v = c.view(inputs)
+    F = c.raw["frac_bits"]
+    frame("view5_1920x1080", v, c.w, c.h, 256, F, c.cap, (12, 8), both_modes=False)
+    ex = r.new_iter_buffer()
+    assert r.RenderCurrent(c.cap, ex) == 0 and r.SyncComputeStream() == 0
+    ob = inputs.Orbit(v)
+    la = inputs.LATable(ob)
+    assert r.InitializePerturb(1, ob, 0, None, la) == 0
+    co = [(float(k["m"]), int(k["e"])) for k in v.coords_perturb_hdr32(ob)]
+    assert r.RenderPerturbLAv2(None, None, None, *co, c.cap, T=T_HDR32, Mode=LAV2_FULL, parity=PARITY_CPU) == 0
+    got = r.new_iter_buffer()
+    assert r.RenderCurrent(c.cap, got) == 0 and r.SyncComputeStream() == 0
+    diff = got[:c.h, :c.w].astype(np.int64) - ex[:c.h, :c.w].astype(np.int64)
+    say(what="c3", name="view5_1920x1080 HDRFloat<float> LAv2 against the exact frame", pixels=int(diff.size),
+        differ=int((diff != 0).sum()), differ_by_more_than_one=int((np.abs(diff) > 1).sum()), largest=int(np.abs(diff).max()))
+
+r.close()
