@@ -129,6 +129,9 @@ def render_lib():
     _decl(lib, "fs_exact_stable_mask", u32, [vp, u32, u32, vp, vp, u32, u64, vp])
     _decl(lib, "fs_set_exact_slice", u32, [vp, u32, C.c_int])
     _decl(lib, "fs_read_exact_stats", u32, [vp, vp])
+    _decl(lib, "fs_exact_sample_counts", u32, [vp, u32, u32, vp, vp, u32, u32, C.c_int, u64, vp])
+    _decl(lib, "fs_render_exact_wide", u32, [vp, u32, u32, u32, vp, vp, u32, C.c_int, u64])
+    _decl(lib, "fs_exact_wide_state", u32, [vp, u32, u32, vp, vp, u32, u32, vp, vp])
     _decl(lib, "fs_render_bla", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_render_direct", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_upload_orbit_scaled", u32, [vp, C.c_int, u32, vp, vp, u64, u64])
@@ -208,6 +211,7 @@ RENDER_SYMBOLS = [
     "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_feature_eval", "fs_feature_eval_direct", "fs_set_feature_slice",
     "fs_autozoom_pick", "fs_set_autozoom_gather_cap",
     "fs_render_exact", "fs_exact_stable_mask", "fs_set_exact_slice", "fs_read_exact_stats",
+    "fs_exact_sample_counts", "fs_render_exact_wide", "fs_exact_wide_state",
     "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
     "fs_render_direct_lp", "fs_clear",

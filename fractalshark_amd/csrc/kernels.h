@@ -9,6 +9,7 @@
 
 #include "../../include/fs_layout.h"
 #include "exact_math.hpp"
+#include "exact_wide_math.hpp"
 #include "hdr_math.hpp"
 
 enum { FS_MODE_FULL = 0, FS_MODE_PO = 1, FS_MODE_LAO = 2 };
@@ -526,6 +527,34 @@ bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, hipStream_t s);
 // mask[y * W + x] = (first ? 1 : mask) & (centre == shifted) over two frames of the same pitch (elements)
 void fsk_exact_mask(const void *centre, const void *shifted, int iter_u64, uint8_t *mask, uint32_t W, uint32_t H, uint32_t pitch,
                     int first, hipStream_t s);
+
+// ---- wide exact renderer (kernels_exact_wide.hip): one slice, one wave per running sample
+struct FsExactWideArgs {
+    const uint32_t *cx, *cy; // limb-major: cx[l * nx + ix], cy[l * ny + iy]
+    uint32_t nx, ny;         // values per limb plane
+    uint32_t W;              // frame: ix = id % W, iy = id / W and the count goes to row iy, column ix.  0: samples, ix = iy = id
+    uint32_t out_pitch;      // frame: elements per row of `out`
+    uint32_t out_u64;
+    void *out;               // counts (frame: the iteration buffer; samples: uint64 per sample)
+    uint64_t cap;            // N
+    uint32_t limbs;          // L, 2 .. 64 M
+    fsx::Params P;
+    // running samples: limb planes of x, then of y (stride slots each), n and the sample's id
+    const uint32_t *src_xy;
+    const uint64_t *src_n;
+    const uint32_t *src_id;
+    uint32_t *dst_xy;
+    uint64_t *dst_n;
+    uint32_t *dst_id;
+    uint32_t stride;
+    uint32_t first;          // the samples start at z_1 = c and slot = id; the source list is not read
+    uint32_t state_only;     // fs_exact_wide_state: no count is written, every sample goes to dst slot = its source slot
+    uint32_t slice;          // steps at most
+    uint32_t *dst_count;     // += samples still running
+    unsigned long long *stats; // [0] += steps taken
+};
+// one workgroup of 64 per sample; false: the limb count needs more than 11 limbs per lane (nothing launched)
+bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, hipStream_t s);
 
 // multi-GPU tiler: out row y = in row index[y] (row_bytes a multiple of 16)
 void fsk_gather_rows(const void *in, void *out, const uint32_t *index, uint32_t row_bytes, uint32_t rows, hipStream_t s);

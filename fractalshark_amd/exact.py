@@ -12,6 +12,8 @@ import numpy as np
 GUARD_BITS = 64  # default frac_bits = the view's precision + this
 MIN_LIMBS, MAX_LIMBS = 2, 24  # instantiated limb counts (csrc/exact_math.hpp)
 MAX_FRAC_BITS = 32 * MAX_LIMBS - 10
+MAX_WIDE_LIMBS = 704  # one wave per sample, 11 limbs per lane at the most (csrc/exact_wide_math.hpp)
+MAX_WIDE_FRAC_BITS = 32 * MAX_WIDE_LIMBS - 10
 
 
 def limbs_for(frac_bits):
@@ -41,11 +43,45 @@ def _check(renderer, err, what):
 def render(renderer, view, bailout=4, frac_bits=None, iter_bytes=4, inclusive=False):
     """The view's exact frame into the renderer's iteration buffer (InitializeMemory with the view's antialiased size and
     iter_bytes comes first), view.num_iterations the cap.  frac_bits defaults to view.precision_bits + 64.  Has the shape
-    autozoom.zoom wants for its `render` argument."""
+    autozoom.zoom wants for its `render` argument.  Up to 24 limbs (758 bits) a lane holds a sample (fs_render_exact); beyond, a
+    wave does (fs_render_exact_wide), up to 704 limbs."""
     F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
     L = limbs_for(F)
     cx, cy = axes(view, F, limbs=L)
-    _check(renderer, renderer.RenderExact(iter_bytes, F, L, cx, cy, bailout, inclusive, view.num_iterations), "fs_render_exact")
+    if uses_wide(L):
+        _check(renderer, renderer.RenderExactWide(iter_bytes, F, L, cx, cy, bailout, inclusive, view.num_iterations),
+               "fs_render_exact_wide")
+    else:
+        _check(renderer, renderer.RenderExact(iter_bytes, F, L, cx, cy, bailout, inclusive, view.num_iterations), "fs_render_exact")
+
+
+def uses_wide(limbs):
+    """The dispatch rule of render: the wide kernel exactly where the narrow one has no instantiation."""
+    return int(limbs) > MAX_LIMBS
+
+
+def sample_counts(renderer, view, xs, ys, bailout=4, frac_bits=None, levels=(), inclusive=False):
+    """(values int64[n], stable bool[n, len(levels)]): min(E - 1, view.num_iterations) of the samples (xs[i], ys[i]) of the
+    view's antialiased frame, and per ladder level whether the value is the same at c +- s and c +- is, s = the frame's width /
+    2^level (the stability bits of the exact-count fixture).  One wave per sample at any limb count up to 704
+    (fs_exact_sample_counts); needs no InitializeMemory."""
+    F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
+    L = limbs_for(F)
+    xs, ys = np.asarray(xs, np.int64), np.asarray(ys, np.int64)
+
+    def run(ax, ay):
+        err, out = renderer.ExactSampleCounts(F, L, ax[:, xs], ay[:, ys], bailout, inclusive, view.num_iterations)
+        _check(renderer, err, "fs_exact_sample_counts")
+        return out.astype(np.int64)
+
+    cx, cy = axes(view, F, limbs=L)
+    values = run(cx, cy)
+    stable = np.ones((len(xs), len(levels)), bool)
+    for j, level in enumerate(levels):
+        cx3, cy3 = axes(view, F, level=level, limbs=L)
+        for ax, ay in ((cx3[1], cy3[0]), (cx3[2], cy3[0]), (cx3[0], cy3[1]), (cx3[0], cy3[2])):  # c + s, c - s, c + is, c - is
+            stable[:, j] &= run(ax, ay) == values
+    return values, stable
 
 
 def stable_mask(renderer, view, level, bailout=4, frac_bits=None):
@@ -59,4 +95,5 @@ def stable_mask(renderer, view, level, bailout=4, frac_bits=None):
     return mask.astype(bool)
 
 
-__all__ = ["GUARD_BITS", "MAX_FRAC_BITS", "limbs_for", "axes", "render", "stable_mask"]
+__all__ = ["GUARD_BITS", "MAX_FRAC_BITS", "MAX_WIDE_LIMBS", "MAX_WIDE_FRAC_BITS", "limbs_for", "axes", "render", "uses_wide",
+           "sample_counts", "stable_mask"]

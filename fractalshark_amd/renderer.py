@@ -174,6 +174,36 @@ class GPURenderer:
         return self._lib.fs_render_exact(self._h, int(iter_bytes), int(frac_bits), int(limbs), cx.ctypes.data, cy.ctypes.data,
                                          int(bailout), 1 if inclusive else 0, int(n_iterations))
 
+    def RenderExactWide(self, iter_bytes, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations):
+        """fs_render_exact_wide: RenderExact through the one-wave-per-sample kernel, limbs = 2 .. 704.  Synchronous."""
+        cx, cy = np.ascontiguousarray(cx, np.uint32), np.ascontiguousarray(cy, np.uint32)
+        if cx.shape != (limbs, self.GetWidth()) or cy.shape != (limbs, self.GetHeight()):
+            raise ValueError("cx, cy must be uint32[limbs, W] and uint32[limbs, H] of the initialised frame")
+        return self._lib.fs_render_exact_wide(self._h, int(iter_bytes), int(frac_bits), int(limbs), cx.ctypes.data, cy.ctypes.data,
+                                              int(bailout), 1 if inclusive else 0, int(n_iterations))
+
+    def ExactSampleCounts(self, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations):
+        """fs_exact_sample_counts: (error code, uint64[n]) -- min(E - 1, n_iterations) of n samples, cx, cy = uint32[limbs, n]
+        (limb-major per sample).  Needs no InitializeMemory.  Synchronous."""
+        cx, cy = np.ascontiguousarray(cx, np.uint32), np.ascontiguousarray(cy, np.uint32)
+        if cx.ndim != 2 or cx.shape[0] != limbs or cy.shape != cx.shape:
+            raise ValueError("cx, cy must both be uint32[limbs, n]")
+        out = np.zeros(cx.shape[1], np.uint64)
+        err = self._lib.fs_exact_sample_counts(self._h, int(frac_bits), int(limbs), cx.ctypes.data, cy.ctypes.data, cx.shape[1],
+                                               int(bailout), 1 if inclusive else 0, int(n_iterations), out.ctypes.data)
+        return err, out
+
+    def ExactWideState(self, frac_bits, limbs, cx, cy, steps):
+        """Test hook (fs_exact_wide_state): (error code, x, y) -- uint32[limbs, n] each: z after `steps` steps of the wide kernel
+        from z_1 = c, a z beyond |z|^2 > 256 kept as it is."""
+        cx, cy = np.ascontiguousarray(cx, np.uint32), np.ascontiguousarray(cy, np.uint32)
+        if cx.ndim != 2 or cx.shape[0] != limbs or cy.shape != cx.shape:
+            raise ValueError("cx, cy must both be uint32[limbs, n]")
+        x, y = np.zeros_like(cx), np.zeros_like(cy)
+        err = self._lib.fs_exact_wide_state(self._h, int(frac_bits), int(limbs), cx.ctypes.data, cy.ctypes.data, cx.shape[1],
+                                            int(steps), x.ctypes.data, y.ctypes.data)
+        return err, x, y
+
     def ExactStableMask(self, frac_bits, limbs, cx3, cy3, bailout, n_iterations):
         """fs_exact_stable_mask: (error code, uint8[H, W]) -- 1 where the four frames shifted by s equal the exact frame in the
         iteration buffer.  cx3, cy3 = uint32[3, limbs, W] / uint32[3, limbs, H]: the axes c, c + s, c - s.  Synchronous."""

@@ -320,6 +320,20 @@ uint32_t fs_render_exact(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits
  * Synchronous; errors as fs_render_exact. */
 uint32_t fs_exact_stable_mask(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *const cx[3],
                               const uint32_t *const cy[3], uint32_t bailout, uint64_t n_iterations, uint8_t *host_mask);
+/* The wide exact renderer: the same recurrence, counting and limb bound with one 64-lane wave per sample, each lane holding
+ * ceil(limbs / 64) limbs of every number, for limbs = 2 .. 704 (frac_bits <= 22518; DESIGN.md 6.3 "Wide").  A count equals
+ * fs_render_exact's wherever both accept the call.
+ * fs_exact_sample_counts: n_samples samples of their own, cx[l * n_samples + i] and cy[l * n_samples + i] (limb-major per SAMPLE);
+ * counts_out[i] = min(E - 1, n_iterations), host memory.  Synchronous.  Needs no frame and no fs_init_memory (the streams are made
+ * if they are missing); the iteration buffer, orbit and tables are left alone.  A lattice with its stability ladder is five calls
+ * per level.
+ * fs_render_exact_wide: the arguments of fs_render_exact and its frame, for limbs = 2 .. 704.
+ * Errors as fs_render_exact with 704 in place of 24 (fs_exact_sample_counts has no frame: no FS_ERR_6, no row bands, no iter_bytes);
+ * hipErrorInvalidValue also for more than 2^31 - 1 samples or pixels (one workgroup each). */
+uint32_t fs_exact_sample_counts(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                                uint32_t n_samples, uint32_t bailout, int inclusive, uint64_t n_iterations, uint64_t *counts_out);
+uint32_t fs_render_exact_wide(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx,
+                              const uint32_t *cy, uint32_t bailout, int inclusive, uint64_t n_iterations);
 
 /* GPURenderer::ClearMemory<IterType> (GPU_Render.cu:212-225). */
 uint32_t fs_clear(fs_renderer *r);

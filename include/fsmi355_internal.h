@@ -109,6 +109,16 @@ uint32_t fs_set_autozoom_gather_cap(fs_renderer *r, uint32_t rows);
  * running after each frame's first slice. */
 uint32_t fs_set_exact_slice(fs_renderer *r, uint32_t steps, int no_compaction);
 uint32_t fs_read_exact_stats(const fs_renderer *r, uint64_t out[4]);
+/* The wide path (fs_exact_sample_counts, fs_render_exact_wide) obeys fs_set_exact_slice too (its default: about 50 ms of a lone
+ * wave's steps at the limb count, divided by the number of times the list fills the chip's 1024 SIMDs, never under 16;
+ * no_compaction is ignored: a launch has exactly one wave per running sample) and reports out[1] = steps its samples took (one
+ * wave each, so out[0] = 64 x that), [2] = launches, [3] = samples still running after the first launch.
+ * fs_exact_wide_state: the state of the wide kernel after `steps` steps from z_1 = c, every limb of it: out_x[l * n_samples + i],
+ * out_y likewise (host memory, cx / cy as fs_exact_sample_counts).  No count stops a sample; the one thing that does is the bound
+ * the limb count is derived from: a z with |z|^2 > 256 * 2^2F is kept as it is (its successors need not fit the limbs).  An escape
+ * count is blind to wrong low limbs over a short run; the state shows a dropped carry at once.  Leaves fs_read_exact_stats alone. */
+uint32_t fs_exact_wide_state(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                             uint32_t n_samples, uint32_t steps, uint32_t *out_x, uint32_t *out_y);
 uint32_t fs_enable_step_count(fs_renderer *r, int enable);
 uint32_t fs_read_step_count(fs_renderer *r, uint64_t counts[8]);
 /* The whole statistics buffer (measurement builds append per-wave trace records behind the 8 counters: library built

@@ -11,9 +11,18 @@
   c3        (with --view5) how many pixels of the HDRFloat<float> LAv2 frame of View 5 at 1920 x 1080 differ from the exact frame: a
             recorded characterisation, not a test
 
+  wide      (--wide) the one-wave-per-sample kernel (fs_exact_sample_counts) per limb count of --wide-limbs: microseconds per step
+            of a lone wave (8 never-escaping samples, two caps apart, the difference) and the chip's pace with 1 024, 2 048 and
+            4 096 such samples, as steps per second and as multiply-adds per second: `executed` counts what the lanes issue
+            (3 products of ceil(L / M) rounds of M^2 in each of 64 lanes, M = ceil(L / 64)), `useful` the 2 L^2 + L of the narrow
+            kernel's count, the figure to put next to its 9.0e12
+  view11    (--view11) View 11's 200 fixture samples at the fixture's cap, (--view14) View 14's six at cap 1 800 000: equality with
+            the fixture's counts and the wall time next to the entry's generator_seconds.  One run each.
+
 Times are host clocks around synchronous calls.  One JSON line per measurement.
 
   python tools/bench_exact.py [--pace] [--frames] [--view5] [--limbs 2,4,7,8,11,12,16,20,23,24]
+                              [--wide] [--wide-limbs 25,64,80,128,160,320,683,704] [--view11] [--view14]
 """
 import argparse
 import json
@@ -34,8 +43,12 @@ ap.add_argument("--pace", action="store_true")
 ap.add_argument("--frames", action="store_true")
 ap.add_argument("--view5", action="store_true")
 ap.add_argument("--limbs", default="2,4,7,8,11,12,16,20,23,24")
+ap.add_argument("--wide", action="store_true")
+ap.add_argument("--wide-limbs", default="25,64,80,128,160,320,683,704")
+ap.add_argument("--view11", action="store_true")
+ap.add_argument("--view14", action="store_true")
 args = ap.parse_args()
-if not (args.pace or args.frames or args.view5):
+if not (args.pace or args.frames or args.view5 or args.wide or args.view11 or args.view14):
     args.pace = args.frames = True
 
 
@@ -87,6 +100,57 @@ if args.pace:
 
 
 r.SetExactSlice(0)
+
+
+def timed_counts(r, F, L, cx, cy, n):
+    t0 = time.perf_counter()
+    err, out = r.ExactSampleCounts(F, L, cx, cy, 4, False, n)
+    dt = time.perf_counter() - t0
+    assert err == 0 and (out == n).all(), err
+    return dt
+
+
+if args.wide:
+    r.SetExactSlice(1 << 20)  # (one launch per call: the caps below are far under it)
+    for L in [int(s) for s in args.wide_limbs.split(",")]:
+        F = 32 * L - 10
+        M = (L + 63) // 64
+        nb = (L + M - 1) // M
+        d = int(min(20000, max(300, 3e7 / (L * L))))
+        n1, n2 = d // 4, d // 4 + d
+        cx, cy = inside_axes(L, 8, 8, F)
+        timed_counts(r, F, L, cx, cy, n1)
+        t1 = min(timed_counts(r, F, L, cx, cy, n1) for _ in range(3))
+        t2 = min(timed_counts(r, F, L, cx, cy, n2) for _ in range(3))
+        us_step = (t2 - t1) / d * 1e6
+        row = dict(what="wide", limbs=L, frac_bits=F, limbs_per_lane=M, rounds=nb, wave_us_per_step=round(us_step, 3),
+                   steps_in_50_ms=int(50e3 / us_step))
+        for n in (1024, 2048, 4096):
+            cx, cy = inside_axes(L, n, n, F)
+            timed_counts(r, F, L, cx, cy, n1)
+            u1 = min(timed_counts(r, F, L, cx, cy, n1) for _ in range(2))
+            u2 = min(timed_counts(r, F, L, cx, cy, n2) for _ in range(2))
+            steps = n * d / (u2 - u1)
+            row["chip_%d" % n] = dict(steps_per_s=round(steps), executed_gmad_per_s=round(steps * 3 * 64 * nb * M * M / 1e9, 1),
+                                      useful_gmad_per_s=round(steps * (2 * L * L + L) / 1e9, 1))
+        say(**row)
+    r.SetExactSlice(0)
+
+for flag, name, cap in ((args.view11, "view11_64x36", None), (args.view14, "view14_15360x8640_attempt", 1800000)):
+    if not flag:
+        continue
+    c = _truth.Case(name)
+    v, F = c.view(inputs), c.raw["frac_bits"]
+    cap = c.cap if cap is None else cap
+    v.num_iterations = cap
+    t0 = time.perf_counter()
+    values, _ = exact.sample_counts(r, v, c.xs, c.ys, bailout=256, frac_bits=F)
+    dt = time.perf_counter() - t0
+    want = _truth.expect_minus_one(c.counts(256), cap)
+    st = r.exact_stats()
+    say(what="fixture samples", name=name, frac_bits=F, limbs=exact.limbs_for(F), samples=len(c.xs), cap=cap, seconds=round(dt, 2),
+        differ=int((values != want).sum()), steps=st["lane_steps"], launches=st["launches"],
+        generator_seconds=c.raw["generator_seconds"], speedup_vs_generator=round(c.raw["generator_seconds"] / dt, 1))
 
 
 def gmp_seconds(v, w, h, R, F, cap, cols, rows):
