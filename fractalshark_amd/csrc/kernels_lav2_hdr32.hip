@@ -95,6 +95,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
     uint32_t c_pass = 0, c_generic = 0; // careful passes of the wave / those that took the generic step
     uint32_t c_blk_free = 0, c_blk_tested = 0; // 4-step blocks of the scalar-cache scaled path without / with bound tests (per wave)
     uint32_t c_lane_steps = 0, c_lane_runs = 0; // (counting build) wave-steps / runs taken on the per-lane entry path of the scaled runs
+    // (counting build) the add-free (ND) form of FS_FAST_LOOP_FDU: wave-steps it carried, verdicts it failed (status 5), its accepted
+    // invocations that were replayed in the full form, and those whose replay ended differently (must stay 0)
+    uint32_t c_nd_steps = 0, c_nd_fail = 0, c_nd_replayed = 0, c_nd_mismatch = 0;
 #ifdef FS_PROFILE_CYCLES
     uint64_t cyc_loop = 0, cyc_run = 0, cyc_body = 0, cyc_t0 = 0, cyc_t1 = 0, cyc_t2 = 0;
     uint64_t cyc_asm = 0, cyc_tested = 0, cyc_hot = 0, cyc_t3 = 0, cyc_t4 = 0, cyc_t5 = 0, wall_loop = 0, wall_t0 = 0;
@@ -264,6 +267,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
             FS_CYC(wall_t0 = wall_clock64());
             uint32_t sc_skip = 0, sc_penalty = 0; // (wave-uniform) back-off of the scaled-run attempts, see below
             bool fl_per_trip = false; // (wave-uniform) the next run attempt uses the per-trip floor verdicts (FS_FAST_LOOP_FL)
+            uint32_t nd_skip = 0; // (wave-uniform) runs for which the add-free form of FS_FAST_LOOP_FDU is not asked for, see there
             while (running) {
                 // ---- run of "scaled" quiet steps.  HDRFloat addition and multiplication are the correctly rounded binary32
                 // operations on the represented values (an exponent gap >= 120 drops an addend that is far below half an
@@ -525,7 +529,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                         uint32_t c = 0;
                         bool failed;
                         FS_CYC(cyc_t2 = __builtin_readcyclecounter());
-                        bool fl_redo = false;
+                        bool fl_redo = false, nd_redo = false;
                         const uint32_t ref_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)ref);
                         if (__builtin_amdgcn_ballot_w64(ref != ref_u) == 0ull) {
                             // Every lane of the wave reads the same orbit entries (the usual case: neighbouring pixels
@@ -647,6 +651,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
 #endif
                             // (FS_FAST_LOOP_FDU) the largest scale shift of the running lanes
                             const int Esh_cap = wave_upper_bound_i32(Esh);
+                            // (FS_FAST_LOOP_FDU) the form of this run's untested bodies: add-free (ND) when dc 2^-E is at least
+                            // 2^26 below both parts of every running lane's entering state -- F_run, see the statement -- and
+                            // the wave is not backing off from a refused entry or a failed verdict
+                            int nd_form = 0;
+                            if (!fl_per_trip) {
+                                if (nd_skip != 0u) {
+                                    nd_skip--;
+                                } else {
+                                    const float f_run = __builtin_fmaxf(FS_FL_FLOOR, __builtin_amdgcn_ldexpf(fs_max_abs(dcs.x, dcs.y), 26));
+                                    const bool nd_ok = f_run < __builtin_inff() && mn0 * __builtin_amdgcn_ldexpf(1.0f, -kScaleShift) >= f_run;
+                                    if (__builtin_amdgcn_ballot_w64(!nd_ok) == 0ull)
+                                        nd_form = 1;
+                                    else
+                                        nd_skip = kNdBackoffEntry;
+                                }
+                            }
                             float mxS = mx0 * __builtin_amdgcn_ldexpf(1.0f, -kScaleShift);
                             int pwi = __builtin_amdgcn_readfirstlane(__float_as_int(e0.w));
                             // (all lanes sit at the same entry here: 2Z of the entry the state is at lives in scalar registers)
@@ -687,7 +707,46 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                             // (round 4's 16-step body of k_perturb_scalar measures 2 % slower here --
                                             // 47.8 - 48.1 against 46.6 - 47.0 ms at N = 1, 6.79 against 6.70 ms on the slowest of
                                             // eight emulated ranks: with seven waves per SIMD the round trip it halves is hidden)
-                                            FS_FAST_LOOP_FDU(FS_PF_NONE);
+                                            int nd_sel = __builtin_amdgcn_readfirstlane(nd_form); // (wave-uniform by construction)
+                                            if (kStats && nd_form != 0) {
+                                                // REPLAY (counting build only): an add-free invocation that was accepted runs again
+                                                // from the same start -- state, step count, max|w|, the entry's bound and 2Z -- in the
+                                                // full form; end state bits, step count, status and what the statement leaves for the
+                                                // tested block must agree.  The frame continues from the add-free results.
+                                                const f2 wv_s = wv, zS_s = zS;
+                                                const float mxS_s = mxS;
+                                                const int pwi_s = pwi;
+                                                const uint32_t off_s = off;
+                                                FS_FAST_LOOP_FDU(FS_PF_NONE);
+                                                const int st_n = __builtin_amdgcn_readfirstlane(st);
+                                                if (st_n != 5 && st_n != 3) {
+                                                    const f2 wv_n = wv, zS_n = zS;
+                                                    const float mxS_n = mxS;
+                                                    const int pwi_n = pwi;
+                                                    const uint32_t off_n = off;
+                                                    wv = wv_s, zS = zS_s, mxS = mxS_s, pwi = pwi_s, off = off_s;
+                                                    nd_sel = 0;
+                                                    FS_FAST_LOOP_FDU(FS_PF_NONE);
+                                                    const bool lane_diff = __float_as_int(wv.x) != __float_as_int(wv_n.x) ||
+                                                                           __float_as_int(wv.y) != __float_as_int(wv_n.y) ||
+                                                                           __float_as_int(mxS) != __float_as_int(mxS_n);
+                                                    const bool wave_diff =
+                                                        __builtin_amdgcn_readfirstlane(st) != st_n ||
+                                                        __builtin_amdgcn_readfirstlane((int)off) != __builtin_amdgcn_readfirstlane((int)off_n) ||
+                                                        __builtin_amdgcn_readfirstlane(pwi) != __builtin_amdgcn_readfirstlane(pwi_n) ||
+                                                        __builtin_amdgcn_readfirstlane(__float_as_int(zS.x)) !=
+                                                            __builtin_amdgcn_readfirstlane(__float_as_int(zS_n.x)) ||
+                                                        __builtin_amdgcn_readfirstlane(__float_as_int(zS.y)) !=
+                                                            __builtin_amdgcn_readfirstlane(__float_as_int(zS_n.y));
+                                                    c_nd_replayed++;
+                                                    if (wave_diff || __builtin_amdgcn_ballot_w64(lane_diff) != 0ull)
+                                                        c_nd_mismatch++;
+                                                    wv = wv_n, zS = zS_n, mxS = mxS_n, pwi = pwi_n, off = off_n;
+                                                    st = st_n;
+                                                }
+                                            } else {
+                                                FS_FAST_LOOP_FDU(FS_PF_NONE);
+                                            }
                                         }
                                         ebo = 0;
                                     } else
@@ -713,7 +772,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                         fl_redo = true;
                                         break;
                                     }
+                                    if (st == 5) {
+                                        // the add-free form's verdict failed (dc was not negligible against some state of this
+                                        // invocation): nothing has been committed either -- the same run again in the full form
+                                        fl_redo = nd_redo = true;
+                                        if (kStats)
+                                            c_nd_fail++;
+                                        break;
+                                    }
                                     cs = (uint32_t)__builtin_amdgcn_readfirstlane((int)off) >> 4;
+                                    if (kStats && nd_form != 0)
+                                        c_nd_steps += cs - c_in;
                                     pwi = __builtin_amdgcn_readfirstlane(pwi);
                                     if (kStats)
                                         c_blk_free += (cs - c_in) >> 2;
@@ -859,7 +928,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                 (const volatile __attribute__((address_space(3))) float *)s_dzp + (wave_in_block * 64u + lane_p) * 2u;
                             dzm = (f2){pz[0], pz[1]};
                             dze = E - kScaleShift;
-                            fl_per_trip = true;
+                            fl_per_trip = !nd_redo;
+                            if (nd_redo)
+                                nd_skip = kNdBackoffVerdict;
                             continue;
                         }
                         fl_per_trip = false;
@@ -1220,6 +1291,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
             const uint32_t ls = __shfl_down(c_lane_steps, off), lr = __shfl_down(c_lane_runs, off);
             c_lane_steps = ls > c_lane_steps ? ls : c_lane_steps;
             c_lane_runs = lr > c_lane_runs ? lr : c_lane_runs;
+            const uint32_t ns = __shfl_down(c_nd_steps, off), nf = __shfl_down(c_nd_fail, off);
+            c_nd_steps = ns > c_nd_steps ? ns : c_nd_steps;
+            c_nd_fail = nf > c_nd_fail ? nf : c_nd_fail;
+            const uint32_t nr = __shfl_down(c_nd_replayed, off), nm = __shfl_down(c_nd_mismatch, off);
+            c_nd_replayed = nr > c_nd_replayed ? nr : c_nd_replayed;
+            c_nd_mismatch = nm > c_nd_mismatch ? nm : c_nd_mismatch;
             const uint32_t bv = __shfl_down(c_blk_violation, off);
             c_blk_violation = bv > c_blk_violation ? bv : c_blk_violation;
             for (int i = 0; i < 4; i++) {
@@ -1247,6 +1324,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
             }
             atomicAdd((unsigned long long *)&A.stats[28], (unsigned long long)c_lane_steps);
             atomicAdd((unsigned long long *)&A.stats[29], (unsigned long long)c_lane_runs);
+            // the add-free forms of FS_FAST_LOOP_FDU (tools/add_free_probe.py).  31 is kept for a form without the dz add
+            atomicAdd((unsigned long long *)&A.stats[30], (unsigned long long)c_nd_steps);
+            atomicAdd((unsigned long long *)&A.stats[32], (unsigned long long)c_nd_fail);
+            atomicAdd((unsigned long long *)&A.stats[33], (unsigned long long)c_nd_mismatch);
+            atomicAdd((unsigned long long *)&A.stats[34], (unsigned long long)c_nd_replayed);
         }
     }
 }

@@ -288,49 +288,96 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
     "s_cmp_gt_i32 %[sdc], " BW "\n\t"                                                                               \
     "s_cselect_b32 %[t], -1, %[t]\n\t"
 #define FS_BT_V "v_cmp_lt_i32_e32 vcc, %[t], v60\n\t"
-#define FS_FAST_LOOP_FDU(PF)                                                                                        \
-    asm volatile(                                                                                                   \
-        "v_mov_b32_e32 v61, 0x7f800000\n\t" FS_BT_T("s67") FS_BT_V                                                  \
-        ".Lfu_loop_%=:\n\t" /* eight steps left?  the first block's verdict (taken where max|w| was made) */         \
+// ---- ADD-FREE form of the body (ND, "no dc"): the step without its last instruction.
+// A step ends with q = p + dc 2^-E (FS_PK_A).  On a deep view that sum is p, bit for bit: View 5's |dc| is near 2^-146 while
+// the |dz| this loop sees is tens of binades above it.  The ND form writes p straight into the next state pair (FS_PK_PN) and
+// issues four packed instructions per step instead of five.  When that is exact:
+//   fl(p + d) == p  whenever  |d| <= 2^-26 |p|:  d is then strictly below half an ulp of p, also where |p| is a power of two and
+//   the ulp below it is half the one above (2^-26 |p| = a quarter of the smaller ulp 2^-24 |p|), so round-to-nearest returns p.
+//   Per lane and run  F_run = max(2^-56, 2^26 max(|dcs.x|, |dcs.y|)),  dcs = dc 2^-E, the run's scaled dc (|dcs| < 2^7 by the
+//   start condition, so F_run is finite; a run whose F_run is not -- a NaN part -- is not eligible).
+//   In an ND run every state IS its p, so the floor accumulator v61 -- the smallest part of every state of the invocation -- already
+//   holds what has to be compared:  v61 >= F_run  certifies, for every step at once and in both parts, |dcs part| <= 2^-26 |p part|,
+//   i.e. that the full form's add would have returned p.  Induction over the invocation: the entering state is the full form's
+//   (whoever made it used the full form, or an ND invocation that passed this verdict), each ND state equals the full form's
+//   state bit for bit, hence so does the next.  Because the states are the same bits, everything argued above for the full
+//   form holds unchanged: the floor (F_run >= 2^-56 subsumes it), H, the bound tests, the block test on sdc / eshm.
+//   The verdict is taken on the way out of the statement (status 5 = failed) against F_run, which is made there from dcs (three
+//   instructions per invocation) instead of being held in a register across the loop.  A failed verdict commits nothing, as
+//   status 3 commits nothing: the caller repeats the run from its parked start state in the full form.  (A state below the
+//   floor 2^-56 itself is reported as status 3, as the full form reports it: that is the floor's business, not dc's, the run
+//   is repeated with the per-trip verdicts as before and no back-off follows.)
+//   Which form runs is decided once per run by the caller (%[nd], wave-uniform): every running lane's entering
+//   min(|w0.x|, |w0.y|) >= F_run, otherwise the run takes the full form without trying; after a refused entry or a failed
+//   verdict the wave does not ask again for kNdBackoffEntry / kNdBackoffVerdict runs, so a shallow view, whose dc is never
+//   negligible, pays one vote every kNdBackoffEntry runs.  The tested C++ blocks, the per-lane path, the hot runs, the careful
+//   step and FS_FAST_LOOP_FL always add dc.
+// Both forms live in ONE statement (a statement exit plus a run entry costs about 75 vector instructions); the full form is
+// the text of round 5, instruction for instruction.  STEP_PRE / STEP_POST are the end of a step: FS_PK_P then FS_PK_A (full),
+// nothing then FS_PK_PN (ND) -- split in two because the second block's branch sits between them.
+#define FS_PK_PN(NW) "v_pk_add_f32 " NW ", v[58:59], v[56:57] neg_lo:[0,1] neg_hi:[0,0]\n\t"
+#define FS_FDU_LOOP(L, PF, PRE, POST)                                                                               \
+        ".L" L "_loop_%=:\n\t" /* eight steps left?  the first block's verdict (taken where max|w| was made) */      \
         "s_cmp_gt_u32 %[off], %[lim8]\n\t"                                                                          \
-        "s_cbranch_scc1 .Lfu_out_%=\n\t"                                                                            \
-        "s_cbranch_vccnz .Lfu_out_%=\n\t" /* steps 1 .. 4 */                                                        \
+        "s_cbranch_scc1 .L" L "_out_%=\n\t"                                                                         \
+        "s_cbranch_vccnz .L" L "_out_%=\n\t" /* steps 1 .. 4 */                                                     \
         FS_PK_F(FS_R0, "s[64:65]")                                                                                  \
         "s_load_dwordx16 s[36:51], s[68:69], %[off]\n\t"                                                            \
         "s_load_dwordx16 s[52:67], s[68:69], %[off] offset:0x40\n\t"                                                \
-        FS_PK_MA(FS_R0) FS_PK_MB(FS_R0) FS_PK_P FS_PK_A(FS_R1)                                                      \
+        FS_PK_MA(FS_R0) FS_PK_MB(FS_R0) PRE POST(FS_R1)                                                             \
         "s_waitcnt lgkmcnt(0)\n\t" PF FS_BT_T("s51")                                                                \
-        FS_PK_F(FS_R1, "s[36:37]") FS_FL_ACC("v50", "v51") FS_PK_MA(FS_R1) FS_PK_MB(FS_R1) FS_PK_P FS_PK_A(FS_R2)   \
-        FS_PK_F(FS_R2, "s[40:41]") FS_FL_ACC("v52", "v53") FS_PK_MA(FS_R2) FS_PK_MB(FS_R2) FS_PK_P FS_PK_A(FS_R3)   \
-        FS_PK_F(FS_R3, "s[44:45]") FS_FL_ACC("v54", "v55") FS_PK_MA(FS_R3) FS_PK_MB(FS_R3) FS_PK_P FS_PK_A(FS_R0)   \
+        FS_PK_F(FS_R1, "s[36:37]") FS_FL_ACC("v50", "v51") FS_PK_MA(FS_R1) FS_PK_MB(FS_R1) PRE POST(FS_R2)          \
+        FS_PK_F(FS_R2, "s[40:41]") FS_FL_ACC("v52", "v53") FS_PK_MA(FS_R2) FS_PK_MB(FS_R2) PRE POST(FS_R3)          \
+        FS_PK_F(FS_R3, "s[44:45]") FS_FL_ACC("v54", "v55") FS_PK_MA(FS_R3) FS_PK_MB(FS_R3) PRE POST(FS_R0)          \
         /* step 5 + w4's floor part and max; the second block's verdict in step 6, before anything of block 2 is counted */ \
         FS_PK_F(FS_R0, "s[48:49]") FS_FL_ACC("v48", "v49") FS_PK_MA(FS_R0) FS_T_X("v48", "v49") FS_PK_MB(FS_R0)     \
-        FS_PK_P FS_PK_A(FS_R1)                                                                                      \
-        FS_PK_F(FS_R1, "s[52:53]") FS_BT_V FS_PK_MA(FS_R1) FS_PK_MB(FS_R1) FS_PK_P                                  \
-        "s_cbranch_vccnz .Lfu_blk_%=\n\t" FS_PK_A(FS_R2)                                                            \
+        PRE POST(FS_R1)                                                                                             \
+        FS_PK_F(FS_R1, "s[52:53]") FS_BT_V FS_PK_MA(FS_R1) FS_PK_MB(FS_R1) PRE                                      \
+        "s_cbranch_vccnz .L" L "_blk_%=\n\t" POST(FS_R2)                                                            \
         FS_PK_F(FS_R2, "s[56:57]") FS_FL_ACC("v50", "v51") FS_PK_MA(FS_R2) FS_FL_ACC("v52", "v53") FS_PK_MB(FS_R2)  \
-        FS_PK_P FS_PK_A(FS_R3)                                                                                      \
-        FS_PK_F(FS_R3, "s[60:61]") FS_FL_ACC("v54", "v55") FS_PK_MA(FS_R3) FS_PK_MB(FS_R3) FS_PK_P FS_PK_A(FS_R0)   \
+        PRE POST(FS_R3)                                                                                             \
+        FS_PK_F(FS_R3, "s[60:61]") FS_FL_ACC("v54", "v55") FS_PK_MA(FS_R3) FS_PK_MB(FS_R3) PRE POST(FS_R0)          \
         "s_add_u32 %[off], %[off], 0x80\n\t" FS_BT_T("s67")                                                         \
-        FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") FS_BT_V "s_branch .Lfu_loop_%=\n"                              \
-        ".Lfu_blk_%=:\n\t" /* the second block needs its bound tests (or H): the state is w4 in v[48:49] */         \
+        FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") FS_BT_V "s_branch .L" L "_loop_%=\n"                           \
+        ".L" L "_blk_%=:\n\t" /* the second block needs its bound tests (or H): the state is w4 in v[48:49] */       \
         "s_mov_b64 s[64:65], s[48:49]\n\t"                                                                          \
         "s_mov_b32 s67, s51\n\t"                                                                                    \
         "s_add_u32 %[off], %[off], 0x40\n"                                                                          \
-        ".Lfu_out_%=:\n\t" /* the verdict over every state of this invocation */                                    \
+        ".L" L "_out_%=:\n\t"
+#define FS_FAST_LOOP_FDU(PF)                                                                                        \
+    asm volatile(                                                                                                   \
+        "v_mov_b32_e32 v61, 0x7f800000\n\t" FS_BT_T("s67") FS_BT_V                                                  \
+        "s_cmp_lg_u32 %[nd], 0\n\t"                                                                                 \
+        "s_cbranch_scc1 .Lfn_loop_%=\n"                                                                             \
+        FS_FDU_LOOP("fu", PF, FS_PK_P, FS_PK_A) /* the verdict over every state of this invocation */               \
         "s_mov_b32 %[st], 0\n\t" FS_FL_C                                                                            \
         "s_cbranch_vccz .Lfu_end_%=\n\t"                                                                            \
+        "s_mov_b32 %[st], 3\n\t"                                                                                    \
+        "s_branch .Lfu_end_%=\n"                                                                                    \
+        FS_FDU_LOOP("fn", PF, "", FS_PK_PN) /* the ND verdict: F_run > the smallest part of any state */            \
+        "v_max_f32_e64 v62, |%[dcx]|, |%[dcy]|\n\t"                                                                 \
+        "s_mov_b32 %[st], 0\n\t"                                                                                    \
+        "v_ldexp_f32 v62, v62, 26\n\t"                                                                              \
+        "v_max_f32_e32 v62, %[flr], v62\n\t"                                                                        \
+        "v_cmp_gt_f32_e32 vcc, v62, v61\n\t"                                                                        \
+        "s_cbranch_vccz .Lfu_end_%=\n\t" /* failed: below the floor itself (3, as in the full form), or only below F_run (5) */ \
+        "s_mov_b32 %[st], 5\n\t" FS_FL_C                                                                            \
+        "s_cbranch_vccz .Lfu_end_%=\n\t"                                                                            \
         "s_mov_b32 %[st], 3\n"                                                                                      \
-        ".Lfu_end_%=:\n\t"                                                                                          \
+        ".Lfu_end_%=:\n\t"                                                                                        \
         "s_waitcnt lgkmcnt(0)"                                                                                      \
         : "+{v[48:49]}"(wv), "={v[50:51]}"(r1), "={v[52:53]}"(r2), "={v[54:55]}"(r3), "={v[56:57]}"(ts_),           \
-          "={v[58:59]}"(ta_), "+{v60}"(mxS), "={v61}"(tn_), [t] "=&s"(bt_t_), [st] "=&s"(st),                       \
+          "={v[58:59]}"(ta_), "+{v60}"(mxS), "={v61}"(tn_), "={v62}"(tl_), [t] "=&s"(bt_t_), [st] "=&s"(st),        \
           "+{s67}"(pwi), "+{s[64:65]}"(zS), [off] "+s"(off), [pf] "=&s"(pf_), [pg] "=&s"(pg_), [ph] "=&s"(ph_)      \
-        : [se] "v"(sE2), [dc] "v"(dcs), [eshm] "s"(Esh_cap), [sdc] "s"(sdc_bits), [lim8] "s"(lim8),                 \
-          "{s[68:69]}"(zpb), [flr] "s"(kFloorBits)                                                                  \
+        : [se] "v"(sE2), [dc] "v"(dcs), [dcx] "v"(dcs.x), [dcy] "v"(dcs.y), [eshm] "s"(Esh_cap),                    \
+          [sdc] "s"(sdc_bits), [lim8] "s"(lim8), [nd] "s"(nd_sel), "{s[68:69]}"(zpb), [flr] "s"(kFloorBits)         \
         : "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50",  \
           "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s66", "vcc",  \
           "scc")
+// Runs for which a wave does not ask for the ND form again: after an entry vote that refused it / after a failed verdict (which
+// costs the run's steps a second time).  Wave-uniform counters; which form a run takes changes no result.
+constexpr uint32_t kNdBackoffEntry = 8;
+constexpr uint32_t kNdBackoffVerdict = 32;
 
 // The untested body with the deferred verdict, SIXTEEN steps per body (round 4).  A wave that is alone on its SIMD -- the
 // never-escaping pixels that decide C2's frame time, the last waves of a rank of an N-GPU split -- pays one L2 round trip per
