@@ -61,9 +61,8 @@ def _write_stamp(target, digest):
 
 
 def _render_units():
-    """Translation units of libfsmi355.so: every csrc/*.hip plus the host side of the C ABI."""
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip"))) + [os.path.join(CSRC, "renderer.cpp"),
-                                                             os.path.join(CSRC, "group.cpp")]
+    """Translation units of libfsmi355.so: every csrc/*.hip plus the host side of the C ABI, every csrc/*.cpp."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip"))) + sorted(glob.glob(os.path.join(CSRC, "*.cpp")))
 
 
 def _render_headers():
@@ -104,7 +103,7 @@ def _unit_digest(src, hdr_digest, extra=()):
 
 
 def _compile(hipcc, src, obj, flags):
-    # renderer.cpp / group.cpp are host-only C++ that include HIP runtime headers: compiled by hipcc as HIP so
+    # csrc/*.cpp (renderer*.cpp, group.cpp) are host-only C++ that include HIP runtime headers: compiled by hipcc as HIP so
     # that <hip/hip_runtime.h> types (float4, hipStream_t) match the kernels' launchers
     lang = [] if src.endswith(".hip") else ["-x", "hip"]
     _run([hipcc, *flags, *_unit_flags(src), "-c", *lang, src, "-o", obj])

@@ -1,5 +1,5 @@
 // autozoom_math.hpp -- the FilamentTip score of fs_autozoom_pick, one text for the device (kernels_autozoom.hip: selects the
-// candidates) and the host (renderer.cpp: decides among them with libm).  AutoZoomer.cpp:338-361, operation by operation; built
+// candidates) and the host (renderer_analysis.cpp: decides among them with libm).  AutoZoomer.cpp:338-361, operation by operation; built
 // with -ffp-contract=off.  Everything but log() is IEEE arithmetic (+ - * / sqrt, correctly rounded on both sides), so the two
 // sides differ by what their log() functions differ.
 #pragma once

@@ -1,4 +1,4 @@
-// kernels.h -- argument blocks and launch entry points shared by renderer.cpp (host) and the kernel translation units (kernels*.hip).
+// kernels.h -- argument blocks and launch entry points shared by renderer*.cpp (host) and the kernel translation units (kernels*.hip).
 // Kernel arguments are plain PODs passed by value (well under the 4 KB kernarg limit), instead of the
 // reference's by-value copies of non-trivial classes (GPUPerturbSingleResults, GPU_LAReference incl. ATInfo,
 // GPU_BLAS -- SURVEY.md appendix B).
@@ -559,7 +559,7 @@ bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, hipStream_t 
 // multi-GPU tiler: out row y = in row index[y] (row_bytes a multiple of 16)
 void fsk_gather_rows(const void *in, void *out, const uint32_t *index, uint32_t row_bytes, uint32_t rows, hipStream_t s);
 
-// ---- LAv2 table construction on the device (kernels_la.hip; host orchestration: fs_build_la in renderer.cpp).
+// ---- LAv2 table construction on the device (kernels_la.hip; host orchestration: fs_build_la in renderer_la_build.cpp).
 // F = float | double.  Work arrays are raw device pointers (hreal<F> / LAInfo<F> of csrc/la_math.hpp).
 template <class F> void fsk_la_src_orbit(const void *zref, uint32_t n, void *chebv, hipStream_t s);
 template <class F> void fsk_la_src_stage(const void *P, uint32_t n, void *chebv, void *mm, uint32_t *steps, hipStream_t s);

@@ -753,7 +753,7 @@ __global__ void __launch_bounds__(256) k_perturb_bla_f64(FsBlaArgsF64 A)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host-callable launchers (called from renderer.cpp through kernels.h).
+// Host-callable launchers (called from renderer_inputs.cpp and renderer_launch.cpp through kernels.h).
 static dim3 frame_grid(const FsFrame &f) { return dim3((f.width + 63) / 64, (f.local_rows + 3) / 4, 1); }
 static dim3 tile_grid(const FsFrame &f) { return dim3((f.width + 31) / 32, (f.local_rows + 7) / 8, 1); } // tile_pixel()
 

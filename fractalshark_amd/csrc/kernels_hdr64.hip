@@ -170,7 +170,7 @@ __device__ __forceinline__ const fs_la_hdr64_u32 *la_at_off(const fs_la_hdr64_u3
 __device__ __forceinline__ double cheb64(const C64 a) { return max_abs64(a.re, a.im); }
 
 // records by a 32-bit BYTE offset from a wave-uniform base (one scalar base + one vector offset per load; the host only launches
-// this kernel when the orbit and the table stay below 4 GB, renderer.cpp)
+// this kernel when the orbit and the table stay below 4 GB, renderer_launch.cpp)
 __device__ __forceinline__ C64 z_at_off(const FsZ64 *__restrict__ z, uint32_t byte_off)
 {
     const FsZ64 *p = (const FsZ64 *)((const char *)z + byte_off);

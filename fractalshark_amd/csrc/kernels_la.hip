@@ -18,7 +18,7 @@
 //      doubling (log2 rounds over all states), ranked by an exclusive scan (chain order = index order);
 //   5. one lane per marked segment: fold its elements with the reference's own Step / Composite (csrc/la_math.hpp, the
 //      source the golden-pinned host builder compiles too) and write the record at its rank.
-// The host (renderer.cpp, fs_build_la) keeps only the scalar decisions of LAReference.cpp (period from the prologue, the
+// The host (renderer_la_build.cpp, fs_build_la) keeps only the scalar decisions of LAReference.cpp (period from the prologue, the
 // low-bound rules, when the stage loop stops) and reads a few words back per stage.  Result: the table of the reference's
 // single-threaded builder, bit for bit.  Its multi-threaded stage-0 variant (CreateLAFromOrbitMT, :215-770) scans the orbit
 // in pieces -- each piece a stretch of one of the chains x -> next(x) above, begun where a worker's two uncapped trackers
@@ -339,7 +339,7 @@ __global__ void k_la_records(const void *zref, const LAInfo<F> *P, const uint32_
 }
 
 // ... and from an explicit list of segments [b, e) of the orbit (the stitched chains of the multi-threaded stage 0: the host has
-// walked them, see build_la in renderer.cpp): record k = init(z[b]) stepped through z[b+1 .. e-1], StepLength e - b.
+// walked them, see build_la in renderer_la_build.cpp): record k = init(z[b]) stepped through z[b+1 .. e-1], StepLength e - b.
 template <class F>
 __global__ void k_la_records_list(const void *zref, const uint32_t *seg, uint32_t n, LAInfo<F> *out, LAInfo<F> *tail_out,
                                   uint32_t max_ref)

@@ -1335,7 +1335,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
 #undef FS_CYC
 
 // ------------------------------------------------------------------------------------------------
-// Host-callable launchers (called from renderer.cpp through kernels.h).
+// Host-callable launchers (called from renderer_launch.cpp through kernels.h).
 static dim3 tile_grid(const FsFrame &f) { return dim3((f.width + 31) / 32, (f.local_rows + 7) / 8, 1); } // tile_pixel()
 
 uint32_t fsk_lav2_hdr32_slots(const FsFrame &f)

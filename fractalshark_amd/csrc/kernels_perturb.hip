@@ -1425,7 +1425,7 @@ __global__ void __launch_bounds__(256) k_perturb_scalar(FsBlaArgsT<F> A)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host-callable launchers (called from renderer.cpp through kernels.h).
+// Host-callable launchers (called from renderer_launch.cpp through kernels.h).
 static dim3 tile_grid(const FsFrame &f) { return dim3((f.width + 31) / 32, (f.local_rows + 7) / 8, 1); } // tile_pixel()
 
 // Grid of the persistent (lane-refilling) launch: as many workgroups as the device holds at once, never more than one

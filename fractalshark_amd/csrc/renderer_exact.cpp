@@ -1,0 +1,432 @@
+#include "renderer_state.hpp"
+
+using namespace fsr;
+
+// ---- what the two exact paths (fs_render_exact: a lane per sample, fs_render_exact_wide: a wave per sample) share on the host.
+// The device block of one call: [counter, statistics | cx | cy | `lists` lists of running samples], a list being the limb planes of
+// x and y, then n, then the sample's id.
+struct ExactLayout {
+    static constexpr size_t head = 256;
+    size_t cx_bytes, cy_bytes, xy_bytes, n_bytes, id_bytes, list_bytes;
+    ExactLayout(uint32_t limbs, uint32_t nx, uint32_t ny, uint32_t n)
+    {
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+        cx_bytes = up((size_t)limbs * nx * 4), cy_bytes = up((size_t)limbs * ny * 4);
+        xy_bytes = up((size_t)2 * limbs * n * 4), n_bytes = up((size_t)n * 8), id_bytes = up((size_t)n * 4);
+        list_bytes = xy_bytes + n_bytes + id_bytes;
+    }
+    size_t bytes(int lists) const { return head + cx_bytes + cy_bytes + (size_t)lists * list_bytes; }
+    uint32_t *count(char *blk) const { return (uint32_t *)blk; }
+    unsigned long long *stats(char *blk) const { return (unsigned long long *)(blk + 16); }
+    uint32_t *cx(char *blk) const { return (uint32_t *)(blk + head); }
+    uint32_t *cy(char *blk) const { return (uint32_t *)(blk + head + cx_bytes); }
+    char *list(char *blk, int k) const { return blk + head + cx_bytes + cy_bytes + (size_t)k * list_bytes; }
+};
+
+// Slice after slice until one leaves no sample running.  launch(k) starts slice k on the stream (false: nothing was launched, the
+// limb count has no kernel); survivors(left) hears how many samples slice k left running before slice k + 1 is set up.  The host
+// reads that count after every slice, so the loop is synchronous.
+template <class Launch, class Survivors>
+static hipError_t exact_slice_loop(hipStream_t s, uint32_t *d_cnt, Launch launch, Survivors survivors, uint64_t &slices,
+                                   uint64_t &after_first)
+{
+    for (;;) {
+        uint32_t left = 0;
+        hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), s);
+        if (e != hipSuccess)
+            return e;
+        if (!launch(slices))
+            return hipErrorInvalidValue;
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(&left, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (e != hipSuccess)
+            return e;
+        if (slices++ == 0)
+            after_first = left;
+        if (left == 0)
+            return hipSuccess;
+        survivors(left);
+    }
+}
+
+extern "C" {
+
+// ---- fs_render_exact / fs_exact_stable_mask: the host side (kernels_exact.hip, exact_math.hpp).
+// Steps per lane per launch: at most 4096 -- one wave's pace with 24 limbs is 11.7 us per step, 48 ms a launch --
+// and fewer when the list is long enough to fill the chip several times over: the chip sustains 5.6e9 lane steps per second with 24
+// limbs and about (24 / L)^2 times that with L, so 1.5e11 / L^2 lane steps per launch keep a launch near 50 ms at any frame size and
+// limb count.  As the compaction shortens the list the slices grow back to 4096.  Never under 64: a launch is not worth less.
+static constexpr uint32_t kExactSlice = 4096, kExactSliceMin = 64;
+static uint32_t exact_default_slice(uint32_t limbs, uint32_t n_src)
+{
+    const uint64_t k = (uint64_t)(1.5e11 / ((double)limbs * limbs)) / (n_src ? n_src : 1u);
+    return (uint32_t)(k > kExactSlice ? kExactSlice : k < kExactSliceMin ? kExactSliceMin : k);
+}
+
+uint32_t fs_set_exact_slice(fs_renderer *r, uint32_t steps, int no_compaction)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    r->exact_slice = steps;
+    r->exact_no_compaction = no_compaction != 0;
+    return 0;
+}
+
+uint32_t fs_read_exact_stats(const fs_renderer *r, uint64_t out[4])
+{
+    if (!r || !out)
+        return hipErrorInvalidValue;
+    memcpy(out, r->exact_stats, sizeof r->exact_stats);
+    return 0;
+}
+
+// What both entry points refuse, in the order the header lists it.
+static uint32_t exact_begin(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, uint32_t bailout, uint64_t n_iterations)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (!r->memory_initialized() || !r->compute)
+        return FS_ERR_6;
+    if (r->local_rows != r->height)
+        return FS_ERR_UNSUPPORTED; // this renderer holds some rows of the frame only
+    if (limbs < fsx::kMinLimbs || limbs > fsx::kMaxLimbs || 32u * limbs < frac_bits + 10u || bailout < 1 ||
+        bailout > fsx::kMaxBailout)
+        return FS_ERR_UNSUPPORTED;
+    if ((n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8) || n_iterations == ~0ull ||
+        (uint64_t)r->width * r->height > 0xFFFFFFFFull)
+        return (uint32_t)hipErrorInvalidValue;
+    return 0;
+}
+
+// every value of a limb-major axis (n values of `limbs` limbs) in [-32 * 2^F, 32 * 2^F): bits F + 5 and up all equal the sign
+static bool exact_axis_in_range(const uint32_t *axis, uint32_t n, uint32_t limbs, uint32_t frac_bits)
+{
+    const uint32_t lo = frac_bits + fsx::kCBoundLog2;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t ext = 0u - (axis[(size_t)(limbs - 1) * n + i] >> 31);
+        for (uint32_t l = lo / 32; l < limbs; l++) {
+            const uint32_t mask = l == lo / 32 ? ~0u << (lo % 32) : ~0u;
+            if ((axis[(size_t)l * n + i] ^ ext) & mask)
+                return false;
+        }
+    }
+    return true;
+}
+
+// One exact frame into `out` (a buffer of the iteration buffer's geometry).  One device block per call: [counter, statistics | cx |
+// cy | two lists of running samples]; synchronous.
+static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                            uint32_t bailout, int inclusive, uint64_t n_iterations, void *out)
+{
+    const uint32_t W = r->width, H = r->height, npix = W * H;
+    const ExactLayout Y(limbs, W, H, npix);
+    const bool compact = !r->exact_no_compaction;
+    char *blk = nullptr;
+    hipStream_t s = r->compute;
+    FS_TRY(r_alloc(r, (void **)&blk, Y.bytes(compact ? 2 : 1), kFrame));
+    unsigned long long *d_stats = Y.stats(blk);
+    char *lists[2] = {Y.list(blk, 0), Y.list(blk, compact ? 1 : 0)};
+
+    FsExactArgs A{};
+    A.cx = Y.cx(blk), A.cy = Y.cy(blk);
+    A.W = W, A.H = H, A.rounded_width = r->w_block * 16u;
+    A.iter_u64 = r->iter_bytes == 8 ? 1u : 0u;
+    A.iters = out;
+    A.cap = n_iterations;
+    A.P = fsx::make_params(frac_bits, bailout, inclusive);
+    A.stride = npix;
+    A.n_src = npix;
+    A.first = 1;
+    A.compact = compact ? 1u : 0u;
+    A.dst_count = Y.count(blk);
+    A.stats = d_stats;
+
+    uint64_t slices = 0, after_first = 0;
+    hipError_t e = hipMemsetAsync(blk, 0, Y.head, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(Y.cx(blk), cx, (size_t)limbs * W * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(Y.cy(blk), cy, (size_t)limbs * H * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = exact_slice_loop(
+            s, A.dst_count,
+            [&](uint64_t k) {
+                char *src = lists[(k & 1) ^ 1], *dst = lists[k & 1];
+                A.src_xy = (const uint32_t *)src, A.src_n = (const uint64_t *)(src + Y.xy_bytes);
+                A.src_pix = (const uint32_t *)(src + Y.xy_bytes + Y.n_bytes);
+                A.dst_xy = (uint32_t *)dst, A.dst_n = (uint64_t *)(dst + Y.xy_bytes), A.dst_pix = (uint32_t *)(dst + Y.xy_bytes + Y.n_bytes);
+                A.slice = r->exact_slice ? r->exact_slice : exact_default_slice(limbs, A.n_src);
+                return fsk_exact_slice(A, limbs, s);
+            },
+            [&](uint32_t left) {
+                A.first = 0;
+                if (compact)
+                    A.n_src = left;
+            },
+            slices, after_first);
+    unsigned long long st[2] = {0, 0};
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(st, d_stats, sizeof st, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    r->exact_stats[0] += st[0], r->exact_stats[1] += st[1], r->exact_stats[2] += slices, r->exact_stats[3] += after_first;
+    (void)r_free(r, blk);
+    return (uint32_t)e;
+}
+
+uint32_t fs_render_exact(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                         uint32_t bailout, int inclusive, uint64_t n_iterations)
+{
+    if (uint32_t e = exact_begin(r, frac_bits, limbs, bailout, n_iterations))
+        return e;
+    if (iter_bytes != 4 && iter_bytes != 8)
+        return FS_ERR_UNSUPPORTED;
+    if (iter_bytes != r->iter_bytes || !cx || !cy)
+        return (uint32_t)hipErrorInvalidValue;
+    if (!exact_axis_in_range(cx, r->width, limbs, frac_bits) || !exact_axis_in_range(cy, r->height, limbs, frac_bits))
+        return FS_ERR_UNSUPPORTED;
+    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    return exact_frame(r, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations, r->iters());
+}
+
+uint32_t fs_exact_stable_mask(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *const cx[3], const uint32_t *const cy[3],
+                              uint32_t bailout, uint64_t n_iterations, uint8_t *host_mask)
+{
+    if (uint32_t e = exact_begin(r, frac_bits, limbs, bailout, n_iterations))
+        return e;
+    if (!cx || !cy || !host_mask)
+        return (uint32_t)hipErrorInvalidValue;
+    for (int k = 0; k < 3; k++) {
+        if (!cx[k] || !cy[k])
+            return (uint32_t)hipErrorInvalidValue;
+        if (!exact_axis_in_range(cx[k], r->width, limbs, frac_bits) || !exact_axis_in_range(cy[k], r->height, limbs, frac_bits))
+            return FS_ERR_UNSUPPORTED;
+    }
+    const uint32_t W = r->width, H = r->height, pitch = r->w_block * 16u;
+    const size_t frame_bytes = ((size_t)pitch * r->local_rows_padded * r->iter_bytes + 255) / 256 * 256;
+    char *blk = nullptr;
+    FS_TRY(r_alloc(r, (void **)&blk, frame_bytes + (size_t)W * H, kFrame));
+    uint8_t *d_mask = (uint8_t *)(blk + frame_bytes);
+    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    uint32_t rc = 0;
+    for (int d = 0; d < 4 && rc == 0; d++) { // c + s, c - s, c + is, c - is
+        rc = exact_frame(r, frac_bits, limbs, d < 2 ? cx[1 + d] : cx[0], d < 2 ? cy[0] : cy[d - 1], bailout, 0, n_iterations, blk);
+        if (rc == 0) {
+            fsk_exact_mask(r->iters(), blk, r->iter_bytes == 8, d_mask, W, H, pitch, d == 0, r->compute);
+            rc = (uint32_t)hipGetLastError();
+        }
+    }
+    if (rc == 0)
+        rc = (uint32_t)hipMemcpyAsync(host_mask, d_mask, (size_t)W * H, hipMemcpyDeviceToHost, r->compute);
+    if (rc == 0)
+        rc = (uint32_t)hipStreamSynchronize(r->compute);
+    (void)r_free(r, blk);
+    return rc;
+}
+
+// ---- fs_exact_sample_counts / fs_render_exact_wide / fs_exact_wide_state: the host side (kernels_exact_wide.hip).
+// Steps per launch.  A lone wave's step takes wide_step_ns(L): 1.5 us plus, for each of its ceil(L / M) rounds, 16.7 M^2 + 36 M + 133 ns
+// (M = limbs per lane) -- the fit of DESIGN.md 6.3 "Wide" to the measured pace, through M = 1, 2 and 11 and within 4 % at M = 3
+// and 5.  The chip runs 1024 waves -- one per SIMD -- at that pace and shares the SIMDs among more (at 11 limbs per lane exactly
+// so; at few limbs per lane it does better, and the launches come out shorter), so a list of n samples advances at
+// ceil(n / 1024) times the lone step time.  K = 50 ms over that, never under 16 steps.
+static constexpr uint32_t kWideMaxSamples = 0x7FFFFFFFu; // one workgroup per sample: the grid's x dimension
+static constexpr uint32_t kWideSliceMin = 16, kWideSliceMax = 1u << 20, kWideWavesAtOnce = 1024;
+static double wide_step_ns(uint32_t limbs)
+{
+    const uint32_t m = fsw::block_for(limbs);
+    const double M = (double)m, nb = (double)((limbs + m - 1) / m);
+    return 1500.0 + nb * (16.7 * M * M + 36.0 * M + 133.0);
+}
+static uint32_t wide_default_slice(uint32_t limbs, uint32_t n_src)
+{
+    const double passes = (double)((n_src + kWideWavesAtOnce - 1) / kWideWavesAtOnce);
+    const double k = 50e6 / (wide_step_ns(limbs) * (passes < 1 ? 1 : passes));
+    return k > kWideSliceMax ? kWideSliceMax : k < kWideSliceMin ? kWideSliceMin : (uint32_t)k;
+}
+
+// what every wide entry point refuses about the number format
+static uint32_t wide_check(uint32_t frac_bits, uint32_t limbs, uint32_t bailout)
+{
+    if (limbs < fsw::kMinLimbs || limbs > fsw::kMaxLimbs || 32ull * limbs < (uint64_t)frac_bits + 10u || bailout < 1 ||
+        bailout > fsx::kMaxBailout)
+        return FS_ERR_UNSUPPORTED;
+    return 0;
+}
+
+struct WideJob {
+    uint32_t frac_bits, limbs;
+    const uint32_t *cx, *cy;
+    uint32_t nx, ny;     // values per axis
+    uint32_t W;          // 0: samples (nx == ny == n)
+    uint32_t n;          // samples
+    uint32_t bailout;
+    int inclusive;
+    uint64_t cap;
+    void *out;           // device: counts
+    uint32_t out_u64, out_pitch;
+    uint32_t state_steps; // fs_exact_wide_state: steps to apply, and ...
+    uint32_t *state_x, *state_y; // ... host arrays [limbs][n] for the result
+    bool state_only;
+};
+
+// One device block per call: [counter, statistics | cx | cy | two lists of running samples]; synchronous.
+static uint32_t exact_wide_run(fs_renderer *r, const WideJob &J)
+{
+    const uint32_t L = J.limbs, n = J.n;
+    const ExactLayout Y(L, J.nx, J.ny, n);
+    char *blk = nullptr;
+    hipStream_t s = r->compute;
+    FS_TRY(r_alloc(r, (void **)&blk, Y.bytes(2), kFrame));
+    unsigned long long *d_stats = Y.stats(blk);
+
+    FsExactWideArgs A{};
+    A.cx = Y.cx(blk), A.cy = Y.cy(blk);
+    A.nx = J.nx, A.ny = J.ny, A.W = J.W;
+    A.out = J.out, A.out_u64 = J.out_u64, A.out_pitch = J.out_pitch;
+    A.cap = J.cap;
+    A.limbs = L;
+    // (the state call freezes a sample at the bound the limb count is derived for: |z|^2 > 256 2^2F)
+    A.P = J.state_only ? fsx::make_params(J.frac_bits, fsx::kMaxBailout, 0) : fsx::make_params(J.frac_bits, J.bailout, J.inclusive);
+    A.stride = n;
+    A.first = 1;
+    A.state_only = J.state_only ? 1u : 0u;
+    A.dst_count = Y.count(blk);
+    A.stats = d_stats;
+
+    uint32_t n_src = n;
+    uint64_t slices = 0, after_first = 0;
+    auto set_lists = [&](uint64_t k) {
+        char *src = Y.list(blk, (k & 1) ^ 1), *dst = Y.list(blk, k & 1);
+        A.src_xy = (const uint32_t *)src, A.src_n = (const uint64_t *)(src + Y.xy_bytes);
+        A.src_id = (const uint32_t *)(src + Y.xy_bytes + Y.n_bytes);
+        A.dst_xy = (uint32_t *)dst, A.dst_n = (uint64_t *)(dst + Y.xy_bytes), A.dst_id = (uint32_t *)(dst + Y.xy_bytes + Y.n_bytes);
+    };
+    hipError_t e = hipMemsetAsync(blk, 0, Y.head, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(Y.cx(blk), J.cx, (size_t)L * J.nx * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(Y.cy(blk), J.cy, (size_t)L * J.ny * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && J.state_only) {
+        // one launch of exactly state_steps steps; every sample is written to list 0 at its own slot
+        set_lists(0);
+        A.slice = J.state_steps;
+        e = fsk_exact_wide_slice(A, n, s) ? hipGetLastError() : hipErrorInvalidValue;
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(J.state_x, Y.list(blk, 0), (size_t)L * n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(J.state_y, Y.list(blk, 0) + (size_t)L * n * 4, (size_t)L * n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+    } else if (e == hipSuccess) {
+        e = exact_slice_loop(
+            s, A.dst_count,
+            [&](uint64_t k) {
+                set_lists(k);
+                A.slice = r->exact_slice ? r->exact_slice : wide_default_slice(L, n_src);
+                return fsk_exact_wide_slice(A, n_src, s);
+            },
+            [&](uint32_t left) {
+                A.first = 0;
+                n_src = left;
+            },
+            slices, after_first);
+    }
+    unsigned long long st = 0;
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(&st, d_stats, sizeof st, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    r->exact_stats[0] += 64ull * st, r->exact_stats[1] += st, r->exact_stats[2] += slices, r->exact_stats[3] += after_first;
+    (void)r_free(r, blk);
+    return (uint32_t)e;
+}
+
+uint32_t fs_exact_sample_counts(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                                uint32_t n_samples, uint32_t bailout, int inclusive, uint64_t n_iterations, uint64_t *counts_out)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (uint32_t e = wide_check(frac_bits, limbs, bailout))
+        return e;
+    if (n_iterations == ~0ull)
+        return (uint32_t)hipErrorInvalidValue;
+    if (n_samples == 0)
+        return 0;
+    if (!cx || !cy || !counts_out || n_samples > kWideMaxSamples)
+        return (uint32_t)hipErrorInvalidValue;
+    if (!exact_axis_in_range(cx, n_samples, limbs, frac_bits) || !exact_axis_in_range(cy, n_samples, limbs, frac_bits))
+        return FS_ERR_UNSUPPORTED;
+    if (uint32_t e = ensure_streams(r)) // no fs_init_memory needed
+        return e;
+    uint64_t *d_out = nullptr;
+    FS_TRY(r_alloc(r, (void **)&d_out, (size_t)n_samples * 8, kFrame));
+    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    WideJob J{};
+    J.frac_bits = frac_bits, J.limbs = limbs, J.cx = cx, J.cy = cy, J.nx = J.ny = J.n = n_samples, J.W = 0;
+    J.bailout = bailout, J.inclusive = inclusive, J.cap = n_iterations;
+    J.out = d_out, J.out_u64 = 1;
+    uint32_t rc = exact_wide_run(r, J);
+    if (rc == 0)
+        rc = (uint32_t)hipMemcpyAsync(counts_out, d_out, (size_t)n_samples * 8, hipMemcpyDeviceToHost, r->compute);
+    if (rc == 0)
+        rc = (uint32_t)hipStreamSynchronize(r->compute);
+    (void)r_free(r, d_out);
+    return rc;
+}
+
+uint32_t fs_render_exact_wide(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx,
+                              const uint32_t *cy, uint32_t bailout, int inclusive, uint64_t n_iterations)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (!r->memory_initialized() || !r->compute)
+        return FS_ERR_6;
+    if (r->local_rows != r->height)
+        return FS_ERR_UNSUPPORTED; // this renderer holds some rows of the frame only
+    if (uint32_t e = wide_check(frac_bits, limbs, bailout))
+        return e;
+    if (iter_bytes != 4 && iter_bytes != 8)
+        return FS_ERR_UNSUPPORTED;
+    if ((n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8) || n_iterations == ~0ull ||
+        (uint64_t)r->width * r->height > kWideMaxSamples || iter_bytes != r->iter_bytes || !cx || !cy)
+        return (uint32_t)hipErrorInvalidValue;
+    if (!exact_axis_in_range(cx, r->width, limbs, frac_bits) || !exact_axis_in_range(cy, r->height, limbs, frac_bits))
+        return FS_ERR_UNSUPPORTED;
+    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    WideJob J{};
+    J.frac_bits = frac_bits, J.limbs = limbs, J.cx = cx, J.cy = cy, J.nx = r->width, J.ny = r->height, J.W = r->width;
+    J.n = r->width * r->height;
+    J.bailout = bailout, J.inclusive = inclusive, J.cap = n_iterations;
+    J.out = r->iters(), J.out_u64 = r->iter_bytes == 8 ? 1u : 0u, J.out_pitch = r->w_block * 16u;
+    return exact_wide_run(r, J);
+}
+
+uint32_t fs_exact_wide_state(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                             uint32_t n_samples, uint32_t steps, uint32_t *out_x, uint32_t *out_y)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (uint32_t e = wide_check(frac_bits, limbs, 1))
+        return e;
+    if (n_samples == 0)
+        return 0;
+    if (!cx || !cy || !out_x || !out_y || n_samples > kWideMaxSamples)
+        return (uint32_t)hipErrorInvalidValue;
+    if (!exact_axis_in_range(cx, n_samples, limbs, frac_bits) || !exact_axis_in_range(cy, n_samples, limbs, frac_bits))
+        return FS_ERR_UNSUPPORTED;
+    if (uint32_t e = ensure_streams(r))
+        return e;
+    WideJob J{};
+    J.frac_bits = frac_bits, J.limbs = limbs, J.cx = cx, J.cy = cy, J.nx = J.ny = J.n = n_samples, J.W = 0;
+    J.state_only = true, J.state_steps = steps, J.state_x = out_x, J.state_y = out_y;
+    const uint64_t keep[4] = {r->exact_stats[0], r->exact_stats[1], r->exact_stats[2], r->exact_stats[3]};
+    const uint32_t rc = exact_wide_run(r, J);
+    memcpy(r->exact_stats, keep, sizeof keep);
+    return rc;
+}
+
+} // extern "C"

@@ -89,7 +89,7 @@ def gather_frame(local, gathered, frame_index, rank, world):
 
 def band_copy_plan(height, rank, world, band=8):
     """The direct host path (round 6): the copies that take `rank`'s local buffer (its bands back to back) to their rows of a
-    whole-frame host buffer, as fs_copy_bands_to_host (csrc/renderer.cpp) issues them -- in ROWS:
+    whole-frame host buffer, as fs_copy_bands_to_host (csrc/renderer_current.cpp) issues them -- in ROWS:
     {"dst_row", "dst_pitch_rows", "src_pitch_rows", "rows_per_band", "bands"} = ONE two-dimensional copy whose element is a whole
     band (bands that lie wholly inside the frame), and {"tail_dst_row", "tail_src_row", "tail_rows"} = the last band when the
     frame's edge cuts it (tail_rows = 0: none).  Pure host arithmetic (CPU tests; bench.py's ranks call the C function)."""

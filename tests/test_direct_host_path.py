@@ -1,5 +1,5 @@
 """CPU-only: the direct host path of the row-tiled frame (round 6) -- every rank copies its own bands straight to their rows of
-ONE whole-frame host buffer, no gather and no re-order (fs_copy_bands_to_host in csrc/renderer.cpp; bench.py --host-path direct).
+ONE whole-frame host buffer, no gather and no re-order (fs_copy_bands_to_host in csrc/renderer_current.cpp; bench.py --host-path direct).
 Here: the copy plan as pure arithmetic against the ownership function, and world_size 2 over gloo -- two rank PROCESSES fill one
 frame in POSIX shared memory, the CPU oracle standing in for the kernel, rank 0 reads it when both ranks' counters say so (the
 same shared-frame + counter protocol bench.py's ranks run on the GPU boxes)."""
