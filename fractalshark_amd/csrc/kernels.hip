@@ -88,10 +88,48 @@ __device__ __forceinline__ float scaled_block_bound(const float4 *__restrict__ z
     return ok ? best * (1.0f - 0x1p-10f) : -0.0f;
 }
 
+// NDZ body bound of entry j (third companion of the scaled runs, `znz`; FS_FAST_LOOP_FDU's bodies without the dz add, whose
+// comment in scaled_runs.hpp carries the argument): with G = max(max|dz|, max|dc|) at entry j within it, each of the eight steps
+// that leave the entries j .. j + 7 computes fma(w, 2^E, 2Z) == 2Z in both parts, and all eight arrivals pass their bound tests.
+// The smallest of
+//   2^-26 min(|2Z.re|, |2Z.im|) of entry j + m over the growth g_j .. g_(j+m-1), m = 0 .. 7  (fl(a + d) == a for |d| <= 2^-26 |a|),
+//   scaled_block_bound(j),  and  scaled_block_bound(j + 4) over g_j .. g_(j+3)  (the second block's test, taken ahead of time),
+// times (1 - 2^-10), with g_k = (4 M_k + 3.8)(1 + 2^-10) as in scaled_block_bound.  "Never" when either block bound is (which
+// covers j + 8 >= n: the last arrival has no bound then), when a part of a 2Z is zero or not safely normal (< 2^-100), or when the
+// result is below 2^-120: the loops compare bit patterns as integers, which orders normal numbers only.
+__device__ __forceinline__ float ndz_body_bound(const float4 *__restrict__ zref, uint64_t j, uint64_t n)
+{
+    if (j + 8 >= n)
+        return -0.0f;
+    const float b0 = scaled_block_bound(zref, j, n), b4 = scaled_block_bound(zref, j + 4, n);
+    if (__float_as_int(b0) == (int)0x80000000 || __float_as_int(b4) == (int)0x80000000)
+        return -0.0f;
+    float best = b0, grow = 1.0f;
+    bool ok = true;
+    for (uint32_t m = 0; m < 8; m++) {
+        const float4 v = zref[j + m];
+        const int e = __float_as_int(v.z);
+        // 2Z as the loop reads it (the second companion's .xy)
+        const float lo = fs_min_abs(__builtin_amdgcn_ldexpf(v.x, e + 1), __builtin_amdgcn_ldexpf(v.y, e + 1));
+        ok = ok && lo >= 0x1p-100f;
+        if (m == 4)
+            best = __builtin_fminf(best, b4 / grow);
+        best = __builtin_fminf(best, lo * 0x1p-26f / grow);
+        // growth of the step that leaves entry j + m (every M here is below 5.6: the block bounds are not "never")
+        const float mk = __builtin_amdgcn_ldexpf(fs_max_abs(v.x, v.y), e < -200 ? -200 : (e > 100 ? 100 : e));
+        grow *= (4.0f * mk + 3.8f) * (1.0f + 0x1p-10f);
+    }
+    best *= 1.0f - 0x1p-10f;
+    return ok && best >= 0x1p-120f ? best : -0.0f;
+}
+
 __global__ void k_make_quiet_orbit(const float4 *__restrict__ zref, float4 *__restrict__ zq, float2 *__restrict__ zs2,
-                                   float4 *__restrict__ zqb, uint64_t n)
+                                   float4 *__restrict__ zqb, float *__restrict__ znz, uint64_t n, uint64_t slack)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // (the slack behind the NDZ bounds is requested a body ahead and never used; it reads as "never" all the same)
+    if (i < slack)
+        znz[n + i] = -0.0f;
     if (i >= n)
         return;
     const float4 v = zref[i];
@@ -116,6 +154,7 @@ __global__ void k_make_quiet_orbit(const float4 *__restrict__ zref, float4 *__re
     zs2[i] = make_float2(__builtin_amdgcn_ldexpf(v.x, e + 1), __builtin_amdgcn_ldexpf(v.y, e + 1));
     zqb[i] = make_float4(scaled_block_bound(zref, i + 3, n), scaled_block_bound(zref, i + 7, n),
                          scaled_block_bound(zref, i + 11, n), scaled_block_bound(zref, i + 15, n));
+    znz[i] = ndz_body_bound(zref, i, n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -762,9 +801,11 @@ void fsk_prepare_orbit_hdr32(const fs_orbit_hdr32 *in, float4 *out, uint64_t n, 
     hipLaunchKernelGGL(k_prepare_orbit_hdr32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);
 }
 
-void fsk_make_quiet_orbit(const float4 *zref, float4 *zq, float2 *zs2, float4 *zqb, uint64_t n, hipStream_t s)
+void fsk_make_quiet_orbit(const float4 *zref, float4 *zq, float2 *zs2, float4 *zqb, float *znz, uint64_t n, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_make_quiet_orbit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, zref, zq, zs2, zqb, n);
+    // (n >= 32 or not: the first block alone has more threads than the 32 entries of slack)
+    hipLaunchKernelGGL(k_make_quiet_orbit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, zref, zq, zs2, zqb, znz, n,
+                       (uint64_t)32);
 }
 
 __global__ void k_decompress_orbit_hdr64(const fs_orbit_hdr64_rc *__restrict__ wp, uint64_t n_wp, uint64_t n_uncompressed,

@@ -39,6 +39,26 @@ void fsk_test_block_threshold(const int *bw, const int *eshm, const int *sdc, in
     hipLaunchKernelGGL(k_test_block_threshold, dim3(n), dim3(64), 0, s, bw, eshm, sdc, t_out, n);
 }
 
+// The same for the NDZ body threshold T2 (FS_BT_T2: the NDZ body bound in place of the block bound, Hz in place of H).
+__global__ void k_test_ndz_threshold(const int *__restrict__ bw, const int *__restrict__ eshm, const int *__restrict__ sdc,
+                                     int *__restrict__ t_out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x;
+    if (i >= n)
+        return;
+    const int b = __builtin_amdgcn_readfirstlane(bw[i]), e = __builtin_amdgcn_readfirstlane(eshm[i]),
+              d = __builtin_amdgcn_readfirstlane(sdc[i]);
+    int t;
+    asm volatile("s_mov_b32 s72, %[b]\n\t" FS_BT_T2("s72") : [t] "=&s"(t) : [b] "s"(b), [eshm] "s"(e), [sdc] "s"(d) : "s72", "scc");
+    if (threadIdx.x == 0)
+        t_out[i] = t;
+}
+
+void fsk_test_ndz_threshold(const int *bw, const int *eshm, const int *sdc, int *t_out, uint32_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_test_ndz_threshold, dim3(n), dim3(64), 0, s, bw, eshm, sdc, t_out, n);
+}
+
 template <int Mode, bool kStats, bool kScaled, bool kLds = false, bool kGpuStage = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) k_lav2_hdr32_fast(FsLav2Args32 A)
 {
@@ -98,6 +118,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
     // (counting build) the add-free (ND) form of FS_FAST_LOOP_FDU: wave-steps it carried, verdicts it failed (status 5), its accepted
     // invocations that were replayed in the full form, and those whose replay ended differently (must stay 0)
     uint32_t c_nd_steps = 0, c_nd_fail = 0, c_nd_replayed = 0, c_nd_mismatch = 0;
+    uint32_t c_ndz_steps = 0; // ... and the wave-steps among c_nd_steps that ran without the dz add as well (NDZ bodies)
 #ifdef FS_PROFILE_CYCLES
     uint64_t cyc_loop = 0, cyc_run = 0, cyc_body = 0, cyc_t0 = 0, cyc_t1 = 0, cyc_t2 = 0;
     uint64_t cyc_asm = 0, cyc_tested = 0, cyc_hot = 0, cyc_t3 = 0, cyc_t4 = 0, cyc_t5 = 0, wall_loop = 0, wall_t0 = 0;
@@ -677,6 +698,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                             const uint32_t rl = (uint32_t)__builtin_amdgcn_readfirstlane((int)run_len);
                             const uint32_t lim8 = (rl << 4) - 0x80u; // run lengths are 16 / 64 / 256 steps
                             const float4 *const zpb = zpu;
+                            // (FS_FAST_LOOP_FDU) the NDZ body bounds, from the entry the run starts at
+                            const float *const znp = A.znz + ref_u;
                             for (;;) {
 #ifdef FS_VERIFY_BLOCK_BOUND
                                 // VERIFICATION BUILD (tools/block_bound_check.py): every block runs the tested form, and a block
@@ -698,6 +721,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                     float tn_, tl_;
                                     uint64_t msk_;
                                     int st, ebo, pf_, pg_, ph_, bt_t_;
+                                    uint32_t nz_ = 0; // (counting build) wave-steps this invocation takes in NDZ bodies
                                     const uint32_t c_in = cs;
                                     uint32_t off = cs << 4;
                                     FS_CYC(cyc_t3 = __builtin_readcyclecounter());
@@ -717,7 +741,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                                 const float mxS_s = mxS;
                                                 const int pwi_s = pwi;
                                                 const uint32_t off_s = off;
-                                                FS_FAST_LOOP_FDU(FS_PF_NONE);
+                                                FS_FAST_LOOP_FDU(FS_PF_NONE, FS_NDZ_COUNT);
                                                 const int st_n = __builtin_amdgcn_readfirstlane(st);
                                                 if (st_n != 5 && st_n != 3) {
                                                     const f2 wv_n = wv, zS_n = zS;
@@ -726,7 +750,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                                     const uint32_t off_n = off;
                                                     wv = wv_s, zS = zS_s, mxS = mxS_s, pwi = pwi_s, off = off_s;
                                                     nd_sel = 0;
-                                                    FS_FAST_LOOP_FDU(FS_PF_NONE);
+                                                    const uint32_t nz_n = nz_; // (the full form takes no NDZ body)
+                                                    FS_FAST_LOOP_FDU(FS_PF_NONE, FS_NDZ_COUNT);
+                                                    nz_ = nz_n;
                                                     const bool lane_diff = __float_as_int(wv.x) != __float_as_int(wv_n.x) ||
                                                                            __float_as_int(wv.y) != __float_as_int(wv_n.y) ||
                                                                            __float_as_int(mxS) != __float_as_int(mxS_n);
@@ -745,7 +771,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                                     st = st_n;
                                                 }
                                             } else {
-                                                FS_FAST_LOOP_FDU(FS_PF_NONE);
+                                                FS_FAST_LOOP_FDU(FS_PF_NONE, "");
                                             }
                                         }
                                         ebo = 0;
@@ -781,8 +807,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                         break;
                                     }
                                     cs = (uint32_t)__builtin_amdgcn_readfirstlane((int)off) >> 4;
-                                    if (kStats && nd_form != 0)
+                                    if (kStats && nd_form != 0) {
                                         c_nd_steps += cs - c_in;
+                                        c_ndz_steps += (uint32_t)__builtin_amdgcn_readfirstlane((int)nz_);
+                                    }
                                     pwi = __builtin_amdgcn_readfirstlane(pwi);
                                     if (kStats)
                                         c_blk_free += (cs - c_in) >> 2;
@@ -1297,6 +1325,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
             const uint32_t nr = __shfl_down(c_nd_replayed, off), nm = __shfl_down(c_nd_mismatch, off);
             c_nd_replayed = nr > c_nd_replayed ? nr : c_nd_replayed;
             c_nd_mismatch = nm > c_nd_mismatch ? nm : c_nd_mismatch;
+            const uint32_t nzs = __shfl_down(c_ndz_steps, off);
+            c_ndz_steps = nzs > c_ndz_steps ? nzs : c_ndz_steps;
             const uint32_t bv = __shfl_down(c_blk_violation, off);
             c_blk_violation = bv > c_blk_violation ? bv : c_blk_violation;
             for (int i = 0; i < 4; i++) {
@@ -1324,11 +1354,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
             }
             atomicAdd((unsigned long long *)&A.stats[28], (unsigned long long)c_lane_steps);
             atomicAdd((unsigned long long *)&A.stats[29], (unsigned long long)c_lane_runs);
-            // the add-free forms of FS_FAST_LOOP_FDU (tools/add_free_probe.py).  31 is kept for a form without the dz add
+            // the add-free forms of FS_FAST_LOOP_FDU (tools/add_free_probe.py).  30 counts every add-free wave-step, 35 those of them
+            // without the dz add (NDZ); 31 stays unused and zero
             atomicAdd((unsigned long long *)&A.stats[30], (unsigned long long)c_nd_steps);
             atomicAdd((unsigned long long *)&A.stats[32], (unsigned long long)c_nd_fail);
             atomicAdd((unsigned long long *)&A.stats[33], (unsigned long long)c_nd_mismatch);
             atomicAdd((unsigned long long *)&A.stats[34], (unsigned long long)c_nd_replayed);
+            atomicAdd((unsigned long long *)&A.stats[35], (unsigned long long)c_ndz_steps);
         }
     }
 }

@@ -13,7 +13,7 @@ namespace {
 constexpr uint64_t kQuietSlack = 32;
 constexpr uint64_t quiet_orbit_units(uint64_t n)
 {
-    return 2 * (n + 2) + 16 + ((n + 2) + kQuietSlack + 1) / 2 + ((n + 2) + kQuietSlack);
+    return 2 * (n + 2) + 16 + ((n + 2) + kQuietSlack + 1) / 2 + ((n + 2) + kQuietSlack) + ((n + 2) + kQuietSlack + 3) / 4;
 }
 
 // zq: the tuned LAv2 loop's view of the prepared orbit (same length incl. the two spare entries)
@@ -25,6 +25,7 @@ hipError_t make_quiet_orbit(fs_renderer *r, uint64_t n)
     // ... followed by the compact form the 16-step body of the untested loop reads: 2Z alone (8 B per entry) and, per entry, the
     // block bounds of the entries 3, 7, 11 and 15 further on (16 B); 32 entries of slack each (the body after the last is
     // requested ahead, never used)
+    // ... and the NDZ body bounds of FS_FAST_LOOP_FDU (4 B per entry), with the same slack
     const uint64_t m = n + 2, slack = kQuietSlack;
     const uint64_t units = quiet_orbit_units(n);
     hipError_t err = r_alloc(r, (void **)&r->zq, units * sizeof(float4), kInput);
@@ -33,10 +34,11 @@ hipError_t make_quiet_orbit(fs_renderer *r, uint64_t n)
     r->zq_n = m;
     r->zs2 = (float2 *)(r->zq + 2 * m + 16);
     r->zqb = r->zq + 2 * m + 16 + (m + slack + 1) / 2;
+    r->znz = (float *)(r->zqb + (m + slack));
     err = hipMemsetAsync(r->zs2, 0, ((m + slack + 1) / 2 + (m + slack)) * sizeof(float4), r->compute);
     if (err != hipSuccess)
         return err;
-    fsk_make_quiet_orbit(r->zref, r->zq, r->zs2, r->zqb, m, r->compute);
+    fsk_make_quiet_orbit(r->zref, r->zq, r->zs2, r->zqb, r->znz, m, r->compute);
     return hipGetLastError();
 }
 

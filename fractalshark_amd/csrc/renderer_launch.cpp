@@ -273,6 +273,7 @@ template <class Args> static void set_orbit_hdr32(const fs_renderer *r, Args &A)
     A.zs = r->zq + r->zq_n;
     A.zs2 = r->zs2;
     A.zqb = r->zqb;
+    A.znz = r->znz;
 }
 
 // GPURenderer::RenderPerturbLAv2<uint64_t, ...> with a cap the 32-bit counters cannot hold: the literal kernel
@@ -832,8 +833,23 @@ uint32_t fs_enable_step_count(fs_renderer *r, int enable)
     return 0;
 }
 
+static uint32_t test_threshold(fs_renderer *r, const int32_t *bound_bits, const int32_t *scale_shift, const int32_t *dc_bits,
+                               int32_t *threshold_out, uint32_t n, bool ndz);
+
 uint32_t fs_test_block_threshold(fs_renderer *r, const int32_t *bound_bits, const int32_t *scale_shift, const int32_t *dc_bits,
                                  int32_t *threshold_out, uint32_t n)
+{
+    return test_threshold(r, bound_bits, scale_shift, dc_bits, threshold_out, n, false);
+}
+
+uint32_t fs_test_ndz_threshold(fs_renderer *r, const int32_t *bound_bits, const int32_t *scale_shift, const int32_t *dc_bits,
+                               int32_t *threshold_out, uint32_t n)
+{
+    return test_threshold(r, bound_bits, scale_shift, dc_bits, threshold_out, n, true);
+}
+
+static uint32_t test_threshold(fs_renderer *r, const int32_t *bound_bits, const int32_t *scale_shift, const int32_t *dc_bits,
+                               int32_t *threshold_out, uint32_t n, bool ndz)
 {
     if (!r || !bound_bits || !scale_shift || !dc_bits || !threshold_out)
         return (uint32_t)hipErrorInvalidValue;
@@ -848,7 +864,10 @@ uint32_t fs_test_block_threshold(fs_renderer *r, const int32_t *bound_bits, cons
     if (!rc)
         rc = (uint32_t)hipMemcpy(d + 2 * (size_t)n, dc_bits, n * sizeof(int), hipMemcpyHostToDevice);
     if (!rc) {
-        fsk_test_block_threshold(d, d + n, d + 2 * (size_t)n, d + 3 * (size_t)n, n, r->compute);
+        if (ndz)
+            fsk_test_ndz_threshold(d, d + n, d + 2 * (size_t)n, d + 3 * (size_t)n, n, r->compute);
+        else
+            fsk_test_block_threshold(d, d + n, d + 2 * (size_t)n, d + 3 * (size_t)n, n, r->compute);
         rc = (uint32_t)hipGetLastError();
     }
     if (!rc)

@@ -281,12 +281,15 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
 // subtracted: positive again under a scale shift below -2^30, i.e. for |dz| < 2^-152 -- tools/block_bound_check.py counted 24 150
 // such blocks among 3.6e9 on the deep views 11, 14 and 19, none on View 5.)  A wave whose lanes' scales are k binades
 // apart tests its lower lanes against a bound 2^k tighter than theirs: such a block takes the tested path, nothing else changes.
-#define FS_BT_T(BW)                                                                                                 \
+// (FS_BT_TH: the same five instructions for any cap HB on max|w| -- H = 2^14 where a four-step block starts, FS_BT_T; Hz = 2^-5
+// where an eight-step body of the form without the dz add starts, FS_BT_T2 below.)
+#define FS_BT_TH(BW, HB)                                                                                            \
     "s_sub_i32 %[t], " BW ", %[eshm]\n\t"                                                                           \
-    "s_cselect_b32 %[t], 0x46800000, %[t]\n\t"                                                                      \
-    "s_min_i32 %[t], %[t], 0x46800000\n\t"                                                                          \
+    "s_cselect_b32 %[t], " HB ", %[t]\n\t"                                                                          \
+    "s_min_i32 %[t], %[t], " HB "\n\t"                                                                              \
     "s_cmp_gt_i32 %[sdc], " BW "\n\t"                                                                               \
     "s_cselect_b32 %[t], -1, %[t]\n\t"
+#define FS_BT_T(BW) FS_BT_TH(BW, "0x46800000")
 #define FS_BT_V "v_cmp_lt_i32_e32 vcc, %[t], v60\n\t"
 // ---- ADD-FREE form of the body (ND, "no dc"): the step without its last instruction.
 // A step ends with q = p + dc 2^-E (FS_PK_A).  On a deep view that sum is p, bit for bit: View 5's |dc| is near 2^-146 while
@@ -316,14 +319,82 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
 // the text of round 5, instruction for instruction.  STEP_PRE / STEP_POST are the end of a step: FS_PK_P then FS_PK_A (full),
 // nothing then FS_PK_PN (ND) -- split in two because the second block's branch sits between them.
 #define FS_PK_PN(NW) "v_pk_add_f32 " NW ", v[58:59], v[56:57] neg_lo:[0,1] neg_hi:[0,0]\n\t"
-#define FS_FDU_LOOP(L, PF, PRE, POST)                                                                               \
+// ---- The form without the dz add either (NDZ): an ND step without its FIRST instruction.
+// A step starts with s = fma(w, 2^E, 2Z) (FS_PK_F).  Where |dz| is tens of binades below |Z| -- most steps of a deep view -- that
+// is 2Z, bit for bit, and the NDZ step multiplies w by the entry's scalar register pair directly: three packed instructions
+// (FS_PK_ZA, FS_PK_ZB, FS_PK_PN) and the state's v_min3.  Unlike ND's, its condition is known BEFORE the steps, from the orbit
+// alone, so it is a threshold test where a body starts and needs no verdict afterwards.
+//   The bound.  k_make_quiet_orbit stores per orbit entry j the NDZ BODY bound (third companion, `znz`, one float per entry): with
+//   G = max(max|dz|, max|dc|) in true scale at entry j and g_k the growth factor of scaled_block_bound, the smallest of
+//     (a) 2^-26 min(|2Z_(j+m).re|, |2Z_(j+m).im|) / (g_j .. g_(j+m-1)),  m = 0 .. 7 -- the eight entries the body's steps leave from,
+//     (b) scaled_block_bound(j),  (c) scaled_block_bound(j + 4) / (g_j .. g_(j+3)),
+//   times (1 - 2^-10); "never" when a term is, when a part of some 2Z is zero or below 2^-100, when the result is below 2^-120
+//   (the integer compare of bit patterns below needs a normal number) or when j + 8 is past the orbit.
+//   1. Induction.  fl(a + d) == a whenever |d| <= 2^-26 |a| (argued for ND above).  The fma rounds once, and the product w 2^E is
+//      exact inside it (a power of two; it IS dz in true scale, which need not be representable on its own).  (b) makes the first
+//      four arrivals pass their bound tests and keeps G <= 1.4, so max|dz| at entry j + m is at most G g_j .. g_(j+m-1) for m <= 4;
+//      (c) says that this value at m = 4 is within scaled_block_bound(j + 4), which carries the same statement through m = 5 .. 8
+//      (3. below).  Hence G <= bound implies by (a), at each of the eight entries and in BOTH parts, |dz part| <= max|dz| <=
+//      2^-26 |2Z part|: s == 2Z in every lane, and the NDZ state is the ND state bit for bit -- which is the full form's once the
+//      ND verdict passes, as before: NDZ states are ND states, counted, floored (v61) and certified against F_run like them.
+//   2. The wave-uniform threshold.  G <= bound is tested as the block test is, and is safe for every lane for the same reasons:
+//      bits(max|w|) <= bound - eshm implies bits(max|w|) + Esh <= bound in each lane because eshm is the LARGEST Esh of the
+//      running lanes, and sdc, the wave's largest max|dc|, stands for the lanes' max|dc|.  T2 = min(bound - eshm, bits(Hz)), -1
+//      when sdc > bound: FS_BT_T's five instructions with another cap (FS_BT_TH).  Because bound <= scaled_block_bound(j) and
+//      Hz <= H, T2 <= T always: a body that passes T2 would have passed the block test.
+//      Hz = 2^-5.  H asks for max|w| < 2^29 at every state a step leaves from; a body has no test inside, so its entering state
+//      has to vouch for the seven states after it.  In true scale G grows by at most g <= (4 * 5.6 + 3.8)(1 + 2^-10) < 26.23 a
+//      step, dc included, i.e. max(max|w|, max|dcs|) grows by that in the run's scale, and 26.23^7 < 2^33: the seven states stay
+//      below 2^33 max(2^-5, max|dcs|) = 2^28 -- an ND run's max|dcs| is below 2^-49 (its entry vote: 2^26 max|dcs| <= a part of a
+//      state whose max is below 2^-23).  The eighth arrival (< 2^33) is the next decision's business: it fails Hz and H alike and
+//      the statement ends in front of it.  A run starts with max|w| < 2^-23 and View 5 gains 0.007 binades a step: Hz never binds.
+//   3. No test inside the body.  The full and ND bodies test w4 against the second block's T half way.  Here (c) did that ahead
+//      of time: max(max|dz_4|, max|dc|) <= G g_j .. g_(j+3) <= scaled_block_bound(j + 4), the very condition that test checks
+//      (with H replaced by 2.), so the arrivals 5 .. 8 pass their bound tests, and G <= 1.4 holds where each step starts.
+//   The decision is taken where a body ends, for the next body, in the ND and the NDZ loop alike: max|w| against T2 first; when no
+//   lane exceeds it the next body is NDZ, otherwise today's compare against T follows and the ND loop goes on or ends.  An NDZ body
+//   is 24 packed + 8 v_min3 + 1 v_max + 1 v_cmp (4.25 per step, ND: 5.5); an ND body after a refused T2 pays one compare more.
+//   The bound of the next body's entry (s72) is loaded with the body's entries, from s[70:71] + off / 4; the statement reads the
+//   bound of the entry it starts at itself (ND side only), so nothing about NDZ is live outside it.  The full form, the tested
+//   blocks, the per-lane path, FS_FAST_LOOP_FL, the hot runs and the careful step never take it.
+#define FS_NDZ_HZ "0x3d000000" /* bits(2^-5) */
+#define FS_BT_T2(BW) FS_BT_TH(BW, FS_NDZ_HZ)
+#define FS_PK_ZA(W, Z) "v_pk_mul_f32 v[58:59], " W ", " Z " op_sel_hi:[0,1]\n\t"
+#define FS_PK_ZB(W, Z) "v_pk_mul_f32 v[56:57], " W ", " Z " op_sel:[1,1] op_sel_hi:[1,0]\n\t"
+#define FS_NDZ_STEP(W, WA, WB, Z, NW) FS_PK_ZA(W, Z) FS_FL_ACC(WA, WB) FS_PK_ZB(W, Z) FS_PK_PN(NW)
+// the next body's NDZ bound, requested with the body's entries (%[t] is free between a body's verdict and its next FS_BT_T)
+#define FS_NDZ_LOAD                                                                                                 \
+    "s_lshr_b32 %[t], %[off], 2\n\t"                                                                                \
+    "s_load_dword s72, s[70:71], %[t] offset:0x20\n\t"
+// where a body ends: today's (full form) / the NDZ decision first (ND and NDZ loops)
+#define FS_FDU_TAIL(L) FS_BT_T("s67") FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") FS_BT_V "s_branch .L" L "_loop_%=\n"
+#define FS_NDZ_TAIL                                                                                                 \
+    FS_BT_T2("s72") FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") FS_BT_V                                            \
+    "s_cbranch_vccz .Lfz_loop_%=\n\t" FS_BT_T("s67") FS_BT_V "s_branch .Lfn_loop_%=\n"
+// the NDZ loop (CNT: the counting build's step counter, or nothing).  On the way out (fewer than eight steps left) it joins the
+// ND loop's exit: the state in v[48:49], max|w| in v60, s[64:65] / s67 of the entry the state is at, as the ND loop leaves them.
+#define FS_NDZ_LOOP(PF, CNT)                                                                                        \
+        ".Lfz_loop_%=:\n\t"                                                                                         \
+        "s_cmp_gt_u32 %[off], %[lim8]\n\t"                                                                          \
+        "s_cbranch_scc1 .Lfn_out_%=\n\t"                                                                            \
+        FS_PK_ZA(FS_R0, "s[64:65]") FS_PK_ZB(FS_R0, "s[64:65]")                                                     \
+        "s_load_dwordx16 s[36:51], s[68:69], %[off]\n\t"                                                            \
+        "s_load_dwordx16 s[52:67], s[68:69], %[off] offset:0x40\n\t"                                                \
+        FS_NDZ_LOAD FS_PK_PN(FS_R1) CNT                                                                             \
+        "s_waitcnt lgkmcnt(0)\n\t" PF                                                                               \
+        FS_NDZ_STEP(FS_R1, "v50", "v51", "s[36:37]", FS_R2) FS_NDZ_STEP(FS_R2, "v52", "v53", "s[40:41]", FS_R3)     \
+        FS_NDZ_STEP(FS_R3, "v54", "v55", "s[44:45]", FS_R0) FS_NDZ_STEP(FS_R0, "v48", "v49", "s[48:49]", FS_R1)     \
+        FS_NDZ_STEP(FS_R1, "v50", "v51", "s[52:53]", FS_R2) FS_NDZ_STEP(FS_R2, "v52", "v53", "s[56:57]", FS_R3)     \
+        FS_NDZ_STEP(FS_R3, "v54", "v55", "s[60:61]", FS_R0)                                                         \
+        "s_add_u32 %[off], %[off], 0x80\n\t" FS_NDZ_TAIL
+#define FS_FDU_LOOP(L, PF, PRE, POST, XLOAD, TAIL)                                                                  \
         ".L" L "_loop_%=:\n\t" /* eight steps left?  the first block's verdict (taken where max|w| was made) */      \
         "s_cmp_gt_u32 %[off], %[lim8]\n\t"                                                                          \
         "s_cbranch_scc1 .L" L "_out_%=\n\t"                                                                         \
         "s_cbranch_vccnz .L" L "_out_%=\n\t" /* steps 1 .. 4 */                                                     \
         FS_PK_F(FS_R0, "s[64:65]")                                                                                  \
         "s_load_dwordx16 s[36:51], s[68:69], %[off]\n\t"                                                            \
-        "s_load_dwordx16 s[52:67], s[68:69], %[off] offset:0x40\n\t"                                                \
+        "s_load_dwordx16 s[52:67], s[68:69], %[off] offset:0x40\n\t" XLOAD                                          \
         FS_PK_MA(FS_R0) FS_PK_MB(FS_R0) PRE POST(FS_R1)                                                             \
         "s_waitcnt lgkmcnt(0)\n\t" PF FS_BT_T("s51")                                                                \
         FS_PK_F(FS_R1, "s[36:37]") FS_FL_ACC("v50", "v51") FS_PK_MA(FS_R1) FS_PK_MB(FS_R1) PRE POST(FS_R2)          \
@@ -337,24 +408,31 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
         FS_PK_F(FS_R2, "s[56:57]") FS_FL_ACC("v50", "v51") FS_PK_MA(FS_R2) FS_FL_ACC("v52", "v53") FS_PK_MB(FS_R2)  \
         PRE POST(FS_R3)                                                                                             \
         FS_PK_F(FS_R3, "s[60:61]") FS_FL_ACC("v54", "v55") FS_PK_MA(FS_R3) FS_PK_MB(FS_R3) PRE POST(FS_R0)          \
-        "s_add_u32 %[off], %[off], 0x80\n\t" FS_BT_T("s67")                                                         \
-        FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") FS_BT_V "s_branch .L" L "_loop_%=\n"                           \
+        "s_add_u32 %[off], %[off], 0x80\n\t" TAIL                                                                   \
         ".L" L "_blk_%=:\n\t" /* the second block needs its bound tests (or H): the state is w4 in v[48:49] */       \
         "s_mov_b64 s[64:65], s[48:49]\n\t"                                                                          \
         "s_mov_b32 s67, s51\n\t"                                                                                    \
         "s_add_u32 %[off], %[off], 0x40\n"                                                                          \
         ".L" L "_out_%=:\n\t"
-#define FS_FAST_LOOP_FDU(PF)                                                                                        \
+#define FS_NDZ_COUNT "s_add_u32 %[nz], %[nz], 8\n\t" /* (counting build) wave-steps taken in NDZ bodies */
+#define FS_FAST_LOOP_FDU(PF, CNT)                                                                                   \
     asm volatile(                                                                                                   \
         "v_mov_b32_e32 v61, 0x7f800000\n\t" FS_BT_T("s67") FS_BT_V                                                  \
         "s_cmp_lg_u32 %[nd], 0\n\t"                                                                                 \
-        "s_cbranch_scc1 .Lfn_loop_%=\n"                                                                             \
-        FS_FDU_LOOP("fu", PF, FS_PK_P, FS_PK_A) /* the verdict over every state of this invocation */               \
+        "s_cbranch_scc1 .Lfz_entry_%=\n"                                                                            \
+        FS_FDU_LOOP("fu", PF, FS_PK_P, FS_PK_A, "", FS_FDU_TAIL("fu")) /* the verdict over every state of this invocation */ \
         "s_mov_b32 %[st], 0\n\t" FS_FL_C                                                                            \
         "s_cbranch_vccz .Lfu_end_%=\n\t"                                                                            \
         "s_mov_b32 %[st], 3\n\t"                                                                                    \
         "s_branch .Lfu_end_%=\n"                                                                                    \
-        FS_FDU_LOOP("fn", PF, "", FS_PK_PN) /* the ND verdict: F_run > the smallest part of any state */            \
+        ".Lfz_entry_%=:\n\t" /* ND side: the NDZ bound of the entry the state is at, then the decision as where a body ends */ \
+        "s_lshr_b32 %[t], %[off], 2\n\t"                                                                            \
+        "s_load_dword s72, s[70:71], %[t]\n\t"                                                                      \
+        "s_waitcnt lgkmcnt(0)\n\t" FS_BT_T2("s72") FS_BT_V                                                          \
+        "s_cbranch_vccz .Lfz_loop_%=\n\t" FS_BT_T("s67") FS_BT_V                                                    \
+        "s_branch .Lfn_loop_%=\n"                                                                                   \
+        FS_NDZ_LOOP(PF, CNT)                                                                                        \
+        FS_FDU_LOOP("fn", PF, "", FS_PK_PN, FS_NDZ_LOAD, FS_NDZ_TAIL) /* the ND verdict: F_run > the smallest part of any state */ \
         "v_max_f32_e64 v62, |%[dcx]|, |%[dcy]|\n\t"                                                                 \
         "s_mov_b32 %[st], 0\n\t"                                                                                    \
         "v_ldexp_f32 v62, v62, 26\n\t"                                                                              \
@@ -368,12 +446,14 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
         "s_waitcnt lgkmcnt(0)"                                                                                      \
         : "+{v[48:49]}"(wv), "={v[50:51]}"(r1), "={v[52:53]}"(r2), "={v[54:55]}"(r3), "={v[56:57]}"(ts_),           \
           "={v[58:59]}"(ta_), "+{v60}"(mxS), "={v61}"(tn_), "={v62}"(tl_), [t] "=&s"(bt_t_), [st] "=&s"(st),        \
-          "+{s67}"(pwi), "+{s[64:65]}"(zS), [off] "+s"(off), [pf] "=&s"(pf_), [pg] "=&s"(pg_), [ph] "=&s"(ph_)      \
+          "+{s67}"(pwi), "+{s[64:65]}"(zS), [off] "+s"(off), [pf] "=&s"(pf_), [pg] "=&s"(pg_), [ph] "=&s"(ph_),     \
+          [nz] "+s"(nz_)                                                                                            \
         : [se] "v"(sE2), [dc] "v"(dcs), [dcx] "v"(dcs.x), [dcy] "v"(dcs.y), [eshm] "s"(Esh_cap),                    \
-          [sdc] "s"(sdc_bits), [lim8] "s"(lim8), [nd] "s"(nd_sel), "{s[68:69]}"(zpb), [flr] "s"(kFloorBits)         \
+          [sdc] "s"(sdc_bits), [lim8] "s"(lim8), [nd] "s"(nd_sel), "{s[68:69]}"(zpb), "{s[70:71]}"(znp),            \
+          [flr] "s"(kFloorBits)                                                                                     \
         : "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50",  \
-          "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s66", "vcc",  \
-          "scc")
+          "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s66", "s72",  \
+          "vcc", "scc")
 // Runs for which a wave does not ask for the ND form again: after an entry vote that refused it / after a failed verdict (which
 // costs the run's steps a second time).  Wave-uniform counters; which form a run takes changes no result.
 constexpr uint32_t kNdBackoffEntry = 8;

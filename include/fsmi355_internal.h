@@ -130,6 +130,10 @@ uint32_t fs_read_stats_raw(fs_renderer *r, uint64_t *out, uint64_t max_words);
  * min(bound_bits - scale_shift, 0x46800000) without wrap-around.  Host arrays.  tests/test_gpu_block_threshold.py. */
 uint32_t fs_test_block_threshold(fs_renderer *r, const int32_t *bound_bits, const int32_t *scale_shift, const int32_t *dc_bits,
                                  int32_t *threshold_out, uint32_t n);
+/* The same for the threshold of that loop's bodies without the dz add (NDZ; bound_bits = the NDZ body bound): -1 when dc_bits >
+ * bound_bits, else min(bound_bits - scale_shift, 0x3D000000) without wrap-around.  tests/test_gpu_lav2_ndz.py. */
+uint32_t fs_test_ndz_threshold(fs_renderer *r, const int32_t *bound_bits, const int32_t *scale_shift, const int32_t *dc_bits,
+                               int32_t *threshold_out, uint32_t n);
 /* Average duration (HIP events on the compute stream, `repeats` back-to-back launches, no D2H) of the two RenderCurrent
  * kernels over the current iteration buffer: ms_out[0] = antialias + palette, ms_out[1] = min / max / sum.  Needs a
  * palette (fs_init_memory) and the whole frame on this renderer.  tools/bench_render_current.py turns them into GB/s. */

@@ -1,6 +1,6 @@
 """How much of the hand-scheduled body of the tuned LAv2 kernel (FS_FAST_LOOP_FDU, csrc/scaled_runs.hpp) runs in its add-free form,
-by workload: the statement's wave-steps, the share the ND form carried, the ND verdicts that failed (each repeats its run in the
-full form), and the counting instantiation's replay of every accepted add-free invocation in the full form (mismatches must be 0).
+by workload: the statement's wave-steps, the share the ND form carried (word 30, NDZ bodies included) and the share that ran
+without the dz add as well (NDZ, word 35), the ND verdicts that failed (each repeats its run in the full form), and the counting instantiation's replay of every accepted add-free invocation in the full form (mismatches must be 0).
 Usage: python tools/add_free_probe.py [view width height [cpu|cpu_gpustage]] ...   (default: View 5 at 64x36 and at 3840x2160)"""
 import ctypes as C
 import json
@@ -39,8 +39,10 @@ for view, w, h, parity in jobs:
                       "perturb_lane_steps": st["perturb_steps"],
                       "statement_wave_steps": statement,
                       "nd_wave_steps": raw[30], "nd_share_of_statement": round(raw[30] / max(1, statement), 4),
-                      "ndz_wave_steps": raw[31],
+                      "ndz_wave_steps": raw[35], "ndz_share_of_statement": round(raw[35] / max(1, statement), 4),
+                      "ndz_share_of_nd": round(raw[35] / max(1, raw[30]), 4),
                       "nd_verdicts_failed": raw[32],
                       "invocations_replayed": raw[34], "replay_mismatches": raw[33],
-                      "predicted_valu_instructions_saved": raw[30] + 2 * raw[31]}), flush=True)
+                      "predicted_valu_instructions_saved_by_nd": raw[30],
+                      "predicted_valu_instructions_saved_by_ndz": 1.25 * raw[35]}), flush=True)
 r.close()
