@@ -107,7 +107,7 @@ template <class F> struct FsLav2ArgsT {
     const float4 *zs;                 // ... and its scaled runs: {2Z.re, 2Z.im, 2^-5 max|Z| | -1, -} in true scale
     const float2 *zs2;                // the same 2Z alone, 8 B per entry, and
     const float4 *zqb;                // the block bounds of entries i + 3, + 7, + 11, + 15: what a 16-step body of the untested loop reads
-    const float *znz;                 // the NDZ body bound of entry i (FS_FAST_LOOP_FDU's bodies without the dz add)
+    const float2 *znz;                // the NDZ body bounds of entry i, {on max|dz|, on max|dc|} (FS_FAST_LOOP_FDU's bodies without the dz add)
     const typename FsDev<F>::LA *las;
     const fs_la_stage_u32 *stages;
     uint64_t *stats;
@@ -199,7 +199,7 @@ template <class F> struct FsBlaArgsT {
     const float4 *zs;                            // ... and the scaled runs' companion (see FsLav2ArgsT)
     const float2 *zs2;                           // ... in the compact form of the 16-step body (see FsLav2ArgsT)
     const float4 *zqb;
-    const float *znz;
+    const float2 *znz;
     const typename FsDev<F>::BLA *const *levels; // device array of device pointers, indexed by level
     uint64_t *stats;
     uint32_t *queue; // frame-wide pixel counter of the persistent (lane-refilling) launch, zeroed before each launch
@@ -385,7 +385,7 @@ void fsk_feature_direct_init(const void *in, FsFeatDirectLane<F> *st, void *out,
 template <class F>
 void fsk_feature_direct_step(FsFeatDirectLane<F> *st, void *out, uint64_t n, int find, int iter_u64, fs::hreal<F> R,
                              uint32_t slice, uint32_t *unfinished, hipStream_t s);
-void fsk_make_quiet_orbit(const float4 *zref, float4 *zq, float2 *zs2, float4 *zqb, float *znz, uint64_t n, hipStream_t s);
+void fsk_make_quiet_orbit(const float4 *zref, float4 *zq, float2 *zs2, float4 *zqb, float2 *znz, uint64_t n, hipStream_t s);
 // Launch order for "long tiles first": order[0 .. n_slots) = the tiles whose probe count (their own centre's or a
 // neighbour's) reached `threshold`, in tile order, then the others, then 0xFFFFFFFF; order[n_slots] = the number of long
 // tiles.  probe: tiles_y rows of tiles_x counts.

@@ -88,48 +88,70 @@ __device__ __forceinline__ float scaled_block_bound(const float4 *__restrict__ z
     return ok ? best * (1.0f - 0x1p-10f) : -0.0f;
 }
 
-// NDZ body bound of entry j (third companion of the scaled runs, `znz`; FS_FAST_LOOP_FDU's bodies without the dz add, whose
-// comment in scaled_runs.hpp carries the argument): with G = max(max|dz|, max|dc|) at entry j within it, each of the eight steps
+// NDZ body bounds of entry j (third companion of the scaled runs, `znz`; FS_FAST_LOOP_FDU's bodies without the dz add, whose
+// comment in scaled_runs.hpp carries the argument): with D = max|dz| <= .x and C = max|dc| <= .y at entry j, each of the eight steps
 // that leave the entries j .. j + 7 computes fma(w, 2^E, 2Z) == 2Z in both parts, and all eight arrivals pass their bound tests.
-// The smallest of
-//   2^-26 min(|2Z.re|, |2Z.im|) of entry j + m over the growth g_j .. g_(j+m-1), m = 0 .. 7  (fl(a + d) == a for |d| <= 2^-26 |a|),
-//   scaled_block_bound(j),  and  scaled_block_bound(j + 4) over g_j .. g_(j+3)  (the second block's test, taken ahead of time),
-// times (1 - 2^-10), with g_k = (4 M_k + 3.8)(1 + 2^-10) as in scaled_block_bound.  "Never" when either block bound is (which
-// covers j + 8 >= n: the last arrival has no bound then), when a part of a 2Z is zero or not safely normal (< 2^-100), or when the
-// result is below 2^-120: the loops compare bit patterns as integers, which orders normal numbers only.
-__device__ __forceinline__ float ndz_body_bound(const float4 *__restrict__ zref, uint64_t j, uint64_t n)
+// dc has a term of its own.  With lo = min(|2Z.re|, |2Z.im|), 2Z as the loop reads it (the second companion's .xy), and the growth an
+// NDZ step really has, s_k = (|2Z_k.re| + |2Z_k.im|)(1 + 2^-10):
+//   A_0 = 1, B_0 = 0,  A_(m+1) = s_(j+m) A_m,  B_(m+1) = s_(j+m) B_m + 1      (A_m = the product of the s, B_m = the sum over i of the
+//                                                                              products of the s after step i)
+//   .x = min over m = 0 .. 7 of 2^-27 lo_(j+m) / A_m,   .y = min over m = 1 .. 7 of 2^-27 lo_(j+m) / B_m,
+//   each also within half of scaled_bound(Z_(j+8)) over A_8 / B_8 (the eighth arrival's own bound test), times (1 - 2^-10).
+// Induction over the body's steps, hypothesis at m:  max|dz_m| <= A_m D + B_m C <= 2^-26 lo_(j+m)  (both halves <= 2^-27 lo).
+//   => s = fl(2Z + dz_m) == 2Z in both parts (|dz part| <= 2^-26 |2Z part|; fl(a + d) == a for |d| <= 2^-26 |a|), so
+//      dz_(m+1) = dz_m 2Z + dc as written, |re| = |dz.re 2Z.re - dz.im 2Z.im + dc.re| <= (|2Z.re| + |2Z.im|) |dz_m|_inf + |dc|_inf, the
+//      imaginary part alike; the two products and the two sums round 2^-24 relative each, which 1 + 2^-10 covers:
+//      max|dz_(m+1)| <= s (A_m D + B_m C) + C = A_(m+1) D + B_(m+1) C
+//   => the hypothesis at m + 1 by the terms m + 1 of .x and .y, for m + 1 <= 7
+//   => arrival m + 1 passes its bound test: max|dz_(m+1)| <= 2^-26 lo <= 2^-25 zmax <= 2^-2 zmax, its scaled_bound, because entry
+//      j + m + 1 is usable (lo <= 2 zmax); the eighth arrival by the halves of scaled_bound(Z_(j+8)).
+// (Round 8 kept ONE bound on max(max|dz|, max|dc|) and divided by scaled_block_bound's g_k = 4 M_k + 3.8, valid for any G <= 1.4:
+// 2^18 .. 2^21 over seven typical steps.  One bound with the growth s + 1 -- dc riding on dz's term -- gave 2^9 .. 2^13 and took NDZ
+// from 52.0 % to 71.4 % of the statement's wave-steps on the C3 frame; its counting launch found 1.65e8 more wave-steps for the two
+// terms, 0.95 % of the launch's vector instructions at 1.25 each, above the 0.8 % that was set for building them.)
+// Neither bound is within scaled_block_bound(j) or (j + 4) by construction, and needs not be: an NDZ body has no test inside and the
+// induction vouches for its arrivals.  "Never" (both): one of the entries j + 1 .. j + 8 without a usable bound or an M >= 5.6 among
+// j .. j + 7 (either block bound says so; this covers j + 8 >= n), a part of a 2Z zero or not safely normal (< 2^-100), or a result
+// below 2^-120 or not finite: the loops compare bit patterns as integers, which orders normal numbers only.
+__device__ __forceinline__ float2 ndz_body_bound(const float4 *__restrict__ zref, uint64_t j, uint64_t n)
 {
+    const float2 never = make_float2(-0.0f, -0.0f);
     if (j + 8 >= n)
-        return -0.0f;
+        return never;
     const float b0 = scaled_block_bound(zref, j, n), b4 = scaled_block_bound(zref, j + 4, n);
     if (__float_as_int(b0) == (int)0x80000000 || __float_as_int(b4) == (int)0x80000000)
-        return -0.0f;
-    float best = b0, grow = 1.0f;
+        return never;
+    float bd = 0x1p60f, bc = 0x1p60f, a = 1.0f, b = 0.0f;
     bool ok = true;
     for (uint32_t m = 0; m < 8; m++) {
         const float4 v = zref[j + m];
         const int e = __float_as_int(v.z);
         // 2Z as the loop reads it (the second companion's .xy)
-        const float lo = fs_min_abs(__builtin_amdgcn_ldexpf(v.x, e + 1), __builtin_amdgcn_ldexpf(v.y, e + 1));
+        const float zr = __builtin_fabsf(__builtin_amdgcn_ldexpf(v.x, e + 1)), zi = __builtin_fabsf(__builtin_amdgcn_ldexpf(v.y, e + 1));
+        const float lo = __builtin_fminf(zr, zi);
         ok = ok && lo >= 0x1p-100f;
-        if (m == 4)
-            best = __builtin_fminf(best, b4 / grow);
-        best = __builtin_fminf(best, lo * 0x1p-26f / grow);
-        // growth of the step that leaves entry j + m (every M here is below 5.6: the block bounds are not "never")
-        const float mk = __builtin_amdgcn_ldexpf(fs_max_abs(v.x, v.y), e < -200 ? -200 : (e > 100 ? 100 : e));
-        grow *= (4.0f * mk + 3.8f) * (1.0f + 0x1p-10f);
+        bd = __builtin_fminf(bd, lo * 0x1p-27f / a);
+        if (m != 0)
+            bc = __builtin_fminf(bc, lo * 0x1p-27f / b);
+        // growth of the step that leaves entry j + m (every part here is below 11.2: the block bounds are not "never")
+        const float s = (zr + zi) * (1.0f + 0x1p-10f);
+        b = s * b + 1.0f;
+        a *= s;
     }
-    best *= 1.0f - 0x1p-10f;
-    return ok && best >= 0x1p-120f ? best : -0.0f;
+    const float sb = scaled_bound(zref[j + 8]) * 0.5f;
+    bd = __builtin_fminf(bd, sb / a) * (1.0f - 0x1p-10f);
+    bc = __builtin_fminf(bc, sb / b) * (1.0f - 0x1p-10f);
+    ok = ok && bd >= 0x1p-120f && bd < 0x1p60f && bc >= 0x1p-120f && bc < 0x1p60f;
+    return ok ? make_float2(bd, bc) : never;
 }
 
 __global__ void k_make_quiet_orbit(const float4 *__restrict__ zref, float4 *__restrict__ zq, float2 *__restrict__ zs2,
-                                   float4 *__restrict__ zqb, float *__restrict__ znz, uint64_t n, uint64_t slack)
+                                   float4 *__restrict__ zqb, float2 *__restrict__ znz, uint64_t n, uint64_t slack)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     // (the slack behind the NDZ bounds is requested a body ahead and never used; it reads as "never" all the same)
     if (i < slack)
-        znz[n + i] = -0.0f;
+        znz[n + i] = make_float2(-0.0f, -0.0f);
     if (i >= n)
         return;
     const float4 v = zref[i];
@@ -801,7 +823,7 @@ void fsk_prepare_orbit_hdr32(const fs_orbit_hdr32 *in, float4 *out, uint64_t n, 
     hipLaunchKernelGGL(k_prepare_orbit_hdr32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);
 }
 
-void fsk_make_quiet_orbit(const float4 *zref, float4 *zq, float2 *zs2, float4 *zqb, float *znz, uint64_t n, hipStream_t s)
+void fsk_make_quiet_orbit(const float4 *zref, float4 *zq, float2 *zs2, float4 *zqb, float2 *znz, uint64_t n, hipStream_t s)
 {
     // (n >= 32 or not: the first block alone has more threads than the 32 entries of slack)
     hipLaunchKernelGGL(k_make_quiet_orbit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, zref, zq, zs2, zqb, znz, n,

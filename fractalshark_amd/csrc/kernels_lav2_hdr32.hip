@@ -39,7 +39,8 @@ void fsk_test_block_threshold(const int *bw, const int *eshm, const int *sdc, in
     hipLaunchKernelGGL(k_test_block_threshold, dim3(n), dim3(64), 0, s, bw, eshm, sdc, t_out, n);
 }
 
-// The same for the NDZ body threshold T2 (FS_BT_T2: the NDZ body bound in place of the block bound, Hz in place of H).
+// The same for the NDZ body threshold T2 (FS_BT_T2: the NDZ body bound in place of the block bound, Hz in place of H; the one bound
+// given stands for both of its terms, on max|dz| and on max|dc|).
 __global__ void k_test_ndz_threshold(const int *__restrict__ bw, const int *__restrict__ eshm, const int *__restrict__ sdc,
                                      int *__restrict__ t_out, uint32_t n)
 {
@@ -49,7 +50,7 @@ __global__ void k_test_ndz_threshold(const int *__restrict__ bw, const int *__re
     const int b = __builtin_amdgcn_readfirstlane(bw[i]), e = __builtin_amdgcn_readfirstlane(eshm[i]),
               d = __builtin_amdgcn_readfirstlane(sdc[i]);
     int t;
-    asm volatile("s_mov_b32 s72, %[b]\n\t" FS_BT_T2("s72") : [t] "=&s"(t) : [b] "s"(b), [eshm] "s"(e), [sdc] "s"(d) : "s72", "scc");
+    asm volatile("s_mov_b32 s72, %[b]\n\t" FS_BT_T2("s72", "s72") : [t] "=&s"(t) : [b] "s"(b), [eshm] "s"(e), [sdc] "s"(d) : "s72", "scc");
     if (threadIdx.x == 0)
         t_out[i] = t;
 }
@@ -119,6 +120,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
     // invocations that were replayed in the full form, and those whose replay ended differently (must stay 0)
     uint32_t c_nd_steps = 0, c_nd_fail = 0, c_nd_replayed = 0, c_nd_mismatch = 0;
     uint32_t c_ndz_steps = 0; // ... and the wave-steps among c_nd_steps that ran without the dz add as well (NDZ bodies)
+    // ... the statement's full-form wave-steps of runs that did not ask for the add-free form because the wave was backing off, and
+    // those among them whose entry vote would have passed
+    uint32_t c_bo_steps = 0, c_bo_ok_steps = 0;
+    // ... and what dc's own term of the NDZ body bounds buys: wave-steps of add-free bodies whose NDZ threshold accepts them and
+    // whose one-term threshold (ndz_one_term_bound, the bound before the two terms) would have refused them
+    uint32_t c_s2_steps = 0;
 #ifdef FS_PROFILE_CYCLES
     uint64_t cyc_loop = 0, cyc_run = 0, cyc_body = 0, cyc_t0 = 0, cyc_t1 = 0, cyc_t2 = 0;
     uint64_t cyc_asm = 0, cyc_tested = 0, cyc_hot = 0, cyc_t3 = 0, cyc_t4 = 0, cyc_t5 = 0, wall_loop = 0, wall_t0 = 0;
@@ -288,7 +295,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
             FS_CYC(wall_t0 = wall_clock64());
             uint32_t sc_skip = 0, sc_penalty = 0; // (wave-uniform) back-off of the scaled-run attempts, see below
             bool fl_per_trip = false; // (wave-uniform) the next run attempt uses the per-trip floor verdicts (FS_FAST_LOOP_FL)
-            uint32_t nd_skip = 0; // (wave-uniform) runs for which the add-free form of FS_FAST_LOOP_FDU is not asked for, see there
+            // (wave-uniform) the add-free back-off of FS_FAST_LOOP_FDU in ONE scalar (the kernel keeps more scalars alive than it has
+            // registers for; a second one measured 0.8 % on the frame with the LA stages tested, whose runs are a few steps long):
+            // bits 8 .. = runs for which the add-free form is not asked for, bits 0 .. 7 = the penalty the next refused entry vote or
+            // failed verdict sets them to (kNdBackoffEntry)
+            uint32_t nd_bo = 0;
+            bool c_nd_redo_run = false; // (counting build) the next run repeats one whose add-free verdict failed
             while (running) {
                 // ---- run of "scaled" quiet steps.  HDRFloat addition and multiplication are the correctly rounded binary32
                 // operations on the represented values (an exponent gap >= 120 drops an addend that is far below half an
@@ -676,16 +688,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                             // 2^26 below both parts of every running lane's entering state -- F_run, see the statement -- and
                             // the wave is not backing off from a refused entry or a failed verdict
                             int nd_form = 0;
+                            bool bo_run = false, bo_ok = false; // (counting build) a backed-off run / whose vote would have passed
                             if (!fl_per_trip) {
-                                if (nd_skip != 0u) {
-                                    nd_skip--;
+                                if (nd_bo >= 0x100u) {
+                                    nd_bo -= 0x100u;
+                                    if (kStats) {
+                                        const float f_run = __builtin_fmaxf(FS_FL_FLOOR, __builtin_amdgcn_ldexpf(fs_max_abs(dcs.x, dcs.y), 26));
+                                        const bool nd_ok = f_run < __builtin_inff() && mn0 * __builtin_amdgcn_ldexpf(1.0f, -kScaleShift) >= f_run;
+                                        bo_run = !c_nd_redo_run; // (the repeated run has to take the full form whatever the policy)
+                                        c_nd_redo_run = false;
+                                        bo_ok = __builtin_amdgcn_ballot_w64(!nd_ok) == 0ull;
+                                    }
                                 } else {
                                     const float f_run = __builtin_fmaxf(FS_FL_FLOOR, __builtin_amdgcn_ldexpf(fs_max_abs(dcs.x, dcs.y), 26));
                                     const bool nd_ok = f_run < __builtin_inff() && mn0 * __builtin_amdgcn_ldexpf(1.0f, -kScaleShift) >= f_run;
-                                    if (__builtin_amdgcn_ballot_w64(!nd_ok) == 0ull)
+                                    if (__builtin_amdgcn_ballot_w64(!nd_ok) == 0ull) {
                                         nd_form = 1;
-                                    else
-                                        nd_skip = kNdBackoffEntry;
+                                    } else {
+                                        nd_bo = nd_backoff_refused(nd_bo, kNdBackoffEntry);
+                                    }
                                 }
                             }
                             float mxS = mx0 * __builtin_amdgcn_ldexpf(1.0f, -kScaleShift);
@@ -699,7 +720,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                             const uint32_t lim8 = (rl << 4) - 0x80u; // run lengths are 16 / 64 / 256 steps
                             const float4 *const zpb = zpu;
                             // (FS_FAST_LOOP_FDU) the NDZ body bounds, from the entry the run starts at
-                            const float *const znp = A.znz + ref_u;
+                            const float2 *const znp = A.znz + ref_u;
                             for (;;) {
 #ifdef FS_VERIFY_BLOCK_BOUND
                                 // VERIFICATION BUILD (tools/block_bound_check.py): every block runs the tested form, and a block
@@ -737,6 +758,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                                 // from the same start -- state, step count, max|w|, the entry's bound and 2Z -- in the
                                                 // full form; end state bits, step count, status and what the statement leaves for the
                                                 // tested block must agree.  The frame continues from the add-free results.
+                                                // An NDZ body may run where the full form's half-way block test would stop it (its bound
+                                                // vouches for its eight arrivals itself, see FS_FAST_LOOP_FDU), so the full form is taken
+                                                // to the add-free invocation's end in two invocations: the first with its block tests
+                                                // waived (a scale shift and a max|dc| no bound can refuse: T = H wherever a bound exists)
+                                                // and bodies that start at least eight steps before that end; the second as it is, which
+                                                // must stop where the add-free form stopped -- at once, or after the four steps of a body
+                                                // that a half-way test ended.  Its floor verdict has to pass in both.
+                                                // What the replay therefore no longer shows is that the full form's OWN block tests would
+                                                // have let it through an NDZ body: it shows that the states are the full form's bit for
+                                                // bit (s == 2Z held), and that the arrivals pass their bound tests rests on the induction
+                                                // beside ndz_body_bound, which tests/test_gpu_lav2_ndz_tight.py steps through entry by entry.
+                                                // The first part goes ONE BODY per invocation (lim8 = the body's own start), because the
+                                                // state where each body starts is what word 38 needs: where the NDZ threshold accepts the
+                                                // body (restated from FS_BT_T2 as the verification build restates FS_BT_T: max|w| against
+                                                // the D bound, max|dc| against the C bound), the one-term threshold this kernel had before
+                                                // is evaluated beside it, and the body's eight wave-steps are counted if that one refuses.
                                                 const f2 wv_s = wv, zS_s = zS;
                                                 const float mxS_s = mxS;
                                                 const int pwi_s = pwi;
@@ -751,8 +788,45 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                                     wv = wv_s, zS = zS_s, mxS = mxS_s, pwi = pwi_s, off = off_s;
                                                     nd_sel = 0;
                                                     const uint32_t nz_n = nz_; // (the full form takes no NDZ body)
-                                                    FS_FAST_LOOP_FDU(FS_PF_NONE, FS_NDZ_COUNT);
+                                                    int st_w = 0;
+                                                    const int esh_r = Esh_cap, sdc_r = sdc_bits; // (the run's own, for the estimate)
+                                                    while (st_w == 0 && off + 0x80u <= off_n) {
+                                                        const uint32_t off_b = off;
+                                                        const uint32_t je = ref_u + (off >> 4); // the entry the state is at
+                                                        const float2 b2 = A.znz[je];
+                                                        const int b_d = __float_as_int(b2.x), b_c = __float_as_int(b2.y);
+                                                        if (b_d != (int)0x80000000) {
+                                                            const int imx = __float_as_int(mxS);
+                                                            const long long d_2 = (long long)b_d - (long long)esh_r;
+                                                            const int t_2 = sdc_r > b_c ? -1 : (d_2 > 0x3d000000ll ? 0x3d000000 : (int)d_2);
+                                                            if (__builtin_amdgcn_ballot_w64(imx > t_2) == 0ull) {
+                                                                const float b1 = ndz_one_term_bound(zs + je);
+                                                                const int b_1 = b1 >= 0x1p-120f ? __float_as_int(b1) : (int)0x80000000;
+                                                                const long long d_1 = (long long)b_1 - (long long)esh_r;
+                                                                const int t_1 = sdc_r > b_1 ? -1 : (d_1 > 0x3d000000ll ? 0x3d000000 : (int)d_1);
+                                                                if (__builtin_amdgcn_ballot_w64(imx > t_1) != 0ull)
+                                                                    c_s2_steps += 8u;
+                                                            }
+                                                        }
+                                                        {
+                                                            const int Esh_cap = -0x7fffffff, sdc_bits = -0x7fffffff - 1; // (shadow the run's)
+                                                            const uint32_t lim8 = off_b;
+                                                            FS_FAST_LOOP_FDU(FS_PF_NONE, FS_NDZ_COUNT);
+                                                        }
+                                                        st_w = __builtin_amdgcn_readfirstlane(st);
+                                                        pwi = __builtin_amdgcn_readfirstlane(pwi);
+                                                        off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
+                                                        zS = (f2){__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(zS.x))),
+                                                                  __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(zS.y)))};
+                                                        if (off != off_b + 0x80u)
+                                                            break; // (a body the waived form does not take whole: the comparison below reports it)
+                                                    }
+                                                    if (st_w == 0) {
+                                                        FS_FAST_LOOP_FDU(FS_PF_NONE, FS_NDZ_COUNT);
+                                                    }
                                                     nz_ = nz_n;
+                                                    if (st_w != 0)
+                                                        st = st_w;
                                                     const bool lane_diff = __float_as_int(wv.x) != __float_as_int(wv_n.x) ||
                                                                            __float_as_int(wv.y) != __float_as_int(wv_n.y) ||
                                                                            __float_as_int(mxS) != __float_as_int(mxS_n);
@@ -807,9 +881,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                                         break;
                                     }
                                     cs = (uint32_t)__builtin_amdgcn_readfirstlane((int)off) >> 4;
+                                    // an add-free invocation with steps has passed its verdict: the wave asks again at once
+                                    // after the next refusal
+                                    if (__builtin_expect(nd_bo != 0u, 0)) {
+                                        if (nd_form != 0 && cs != c_in)
+                                            nd_bo = 0u; // (no run is being sat out while the add-free form runs)
+                                    }
                                     if (kStats && nd_form != 0) {
                                         c_nd_steps += cs - c_in;
                                         c_ndz_steps += (uint32_t)__builtin_amdgcn_readfirstlane((int)nz_);
+                                    }
+                                    if (kStats && bo_run) {
+                                        c_bo_steps += cs - c_in;
+                                        if (bo_ok)
+                                            c_bo_ok_steps += cs - c_in;
                                     }
                                     pwi = __builtin_amdgcn_readfirstlane(pwi);
                                     if (kStats)
@@ -957,8 +1042,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
                             dzm = (f2){pz[0], pz[1]};
                             dze = E - kScaleShift;
                             fl_per_trip = !nd_redo;
-                            if (nd_redo)
-                                nd_skip = kNdBackoffVerdict;
+                            if (nd_redo) {
+                                // (the repeated run itself is the first of the runs that do not ask)
+                                nd_bo = nd_backoff_refused(nd_bo, kNdBackoffVerdict) + 0x100u;
+                                if (kStats)
+                                    c_nd_redo_run = true;
+                            }
                             continue;
                         }
                         fl_per_trip = false;
@@ -1327,6 +1416,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
             c_nd_mismatch = nm > c_nd_mismatch ? nm : c_nd_mismatch;
             const uint32_t nzs = __shfl_down(c_ndz_steps, off);
             c_ndz_steps = nzs > c_ndz_steps ? nzs : c_ndz_steps;
+            const uint32_t s2s = __shfl_down(c_s2_steps, off);
+            c_s2_steps = s2s > c_s2_steps ? s2s : c_s2_steps;
+            const uint32_t bos = __shfl_down(c_bo_steps, off), bok = __shfl_down(c_bo_ok_steps, off);
+            c_bo_steps = bos > c_bo_steps ? bos : c_bo_steps;
+            c_bo_ok_steps = bok > c_bo_ok_steps ? bok : c_bo_ok_steps;
             const uint32_t bv = __shfl_down(c_blk_violation, off);
             c_blk_violation = bv > c_blk_violation ? bv : c_blk_violation;
             for (int i = 0; i < 4; i++) {
@@ -1361,6 +1455,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
             atomicAdd((unsigned long long *)&A.stats[33], (unsigned long long)c_nd_mismatch);
             atomicAdd((unsigned long long *)&A.stats[34], (unsigned long long)c_nd_replayed);
             atomicAdd((unsigned long long *)&A.stats[35], (unsigned long long)c_ndz_steps);
+            // 36 = the statement's full-form wave-steps taken while the wave was backing off, 37 = those whose entry vote would have passed
+            atomicAdd((unsigned long long *)&A.stats[36], (unsigned long long)c_bo_steps);
+            atomicAdd((unsigned long long *)&A.stats[37], (unsigned long long)c_bo_ok_steps);
+            // 38 = add-free wave-steps in bodies the NDZ threshold accepts and the one-term threshold (dc riding on dz's term) would refuse
+            atomicAdd((unsigned long long *)&A.stats[38], (unsigned long long)c_s2_steps);
         }
     }
 }

@@ -13,7 +13,7 @@ namespace {
 constexpr uint64_t kQuietSlack = 32;
 constexpr uint64_t quiet_orbit_units(uint64_t n)
 {
-    return 2 * (n + 2) + 16 + ((n + 2) + kQuietSlack + 1) / 2 + ((n + 2) + kQuietSlack) + ((n + 2) + kQuietSlack + 3) / 4;
+    return 2 * (n + 2) + 16 + ((n + 2) + kQuietSlack + 1) / 2 + ((n + 2) + kQuietSlack) + ((n + 2) + kQuietSlack + 1) / 2;
 }
 
 // zq: the tuned LAv2 loop's view of the prepared orbit (same length incl. the two spare entries)
@@ -25,7 +25,7 @@ hipError_t make_quiet_orbit(fs_renderer *r, uint64_t n)
     // ... followed by the compact form the 16-step body of the untested loop reads: 2Z alone (8 B per entry) and, per entry, the
     // block bounds of the entries 3, 7, 11 and 15 further on (16 B); 32 entries of slack each (the body after the last is
     // requested ahead, never used)
-    // ... and the NDZ body bounds of FS_FAST_LOOP_FDU (4 B per entry), with the same slack
+    // ... and the NDZ body bounds of FS_FAST_LOOP_FDU (two floats per entry), with the same slack
     const uint64_t m = n + 2, slack = kQuietSlack;
     const uint64_t units = quiet_orbit_units(n);
     hipError_t err = r_alloc(r, (void **)&r->zq, units * sizeof(float4), kInput);
@@ -34,7 +34,7 @@ hipError_t make_quiet_orbit(fs_renderer *r, uint64_t n)
     r->zq_n = m;
     r->zs2 = (float2 *)(r->zq + 2 * m + 16);
     r->zqb = r->zq + 2 * m + 16 + (m + slack + 1) / 2;
-    r->znz = (float *)(r->zqb + (m + slack));
+    r->znz = (float2 *)(r->zqb + (m + slack));
     err = hipMemsetAsync(r->zs2, 0, ((m + slack + 1) / 2 + (m + slack)) * sizeof(float4), r->compute);
     if (err != hipSuccess)
         return err;
@@ -740,6 +740,22 @@ uint64_t fs_bla_level_size(const fs_renderer *r, int32_t level)
 {
     return level >= 0 && (size_t)level < r->bla_level_sizes.size() ? r->bla_level_sizes[(size_t)level] : 0;
 }
+uint32_t fs_read_ndz_bounds(fs_renderer *r, float *bounds_out, float *entries_out, uint64_t max_entries, uint64_t *n_out)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (!r->zq || !r->znz || !r->zq_n)
+        return FS_ERR_6;
+    const uint64_t n = r->zq_n < max_entries ? r->zq_n : max_entries;
+    if (bounds_out && n)
+        FS_TRY(hipMemcpyAsync(bounds_out, r->znz, n * sizeof(float2), hipMemcpyDeviceToHost, r->compute));
+    if (entries_out && n)
+        FS_TRY(hipMemcpyAsync(entries_out, r->zq + r->zq_n, n * sizeof(float4), hipMemcpyDeviceToHost, r->compute));
+    if (n_out)
+        *n_out = r->zq_n;
+    return (uint32_t)hipStreamSynchronize(r->compute);
+}
+
 uint32_t fs_read_bla_level(fs_renderer *r, int32_t level, void *out, uint64_t max_records)
 {
     if (uint32_t e = use_device(r))

@@ -131,7 +131,7 @@ struct fs_renderer {
     uint64_t zq_n = 0;
     float2 *zs2 = nullptr; // (inside the zq block) compact companions of the 16-step body
     float4 *zqb = nullptr;
-    float *znz = nullptr; // (inside the zq block) NDZ body bounds of the tuned LAv2 loop
+    float2 *znz = nullptr; // (inside the zq block) NDZ body bounds of the tuned LAv2 loop
     FsZ64 *zref64 = nullptr;
     fs_orbit_f64 *orbit_f64 = nullptr; // plain double orbit (FS_T_F64), used as uploaded
     void *orbit_plain = nullptr;       // plain float / CudaDblflt orbit (FS_T_F32 / FS_T_2X32), used as uploaded

@@ -283,12 +283,13 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
 // apart tests its lower lanes against a bound 2^k tighter than theirs: such a block takes the tested path, nothing else changes.
 // (FS_BT_TH: the same five instructions for any cap HB on max|w| -- H = 2^14 where a four-step block starts, FS_BT_T; Hz = 2^-5
 // where an eight-step body of the form without the dz add starts, FS_BT_T2 below.)
-#define FS_BT_TH(BW, HB)                                                                                            \
+#define FS_BT_THC(BW, BC, HB)                                                                                       \
     "s_sub_i32 %[t], " BW ", %[eshm]\n\t"                                                                           \
     "s_cselect_b32 %[t], " HB ", %[t]\n\t"                                                                          \
     "s_min_i32 %[t], %[t], " HB "\n\t"                                                                              \
-    "s_cmp_gt_i32 %[sdc], " BW "\n\t"                                                                               \
+    "s_cmp_gt_i32 %[sdc], " BC "\n\t"                                                                               \
     "s_cselect_b32 %[t], -1, %[t]\n\t"
+#define FS_BT_TH(BW, HB) FS_BT_THC(BW, BW, HB)
 #define FS_BT_T(BW) FS_BT_TH(BW, "0x46800000")
 #define FS_BT_V "v_cmp_lt_i32_e32 vcc, %[t], v60\n\t"
 // ---- ADD-FREE form of the body (ND, "no dc"): the step without its last instruction.
@@ -311,9 +312,9 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
 //   floor 2^-56 itself is reported as status 3, as the full form reports it: that is the floor's business, not dc's, the run
 //   is repeated with the per-trip verdicts as before and no back-off follows.)
 //   Which form runs is decided once per run by the caller (%[nd], wave-uniform): every running lane's entering
-//   min(|w0.x|, |w0.y|) >= F_run, otherwise the run takes the full form without trying; after a refused entry or a failed
-//   verdict the wave does not ask again for kNdBackoffEntry / kNdBackoffVerdict runs, so a shallow view, whose dc is never
-//   negligible, pays one vote every kNdBackoffEntry runs.  The tested C++ blocks, the per-lane path, the hot runs, the careful
+//   min(|w0.x|, |w0.y|) >= F_run, otherwise the run takes the full form without trying; after refused entries or failed
+//   verdicts in a row the wave sits out 0, 1, 2, 4, .. runs, up to kNdBackoffEntry / kNdBackoffVerdict (see there), so a shallow
+//   view, whose dc is never negligible, pays one vote every kNdBackoffEntry runs.  The tested C++ blocks, the per-lane path, the hot runs, the careful
 //   step and FS_FAST_LOOP_FL always add dc.
 // Both forms live in ONE statement (a statement exit plus a run entry costs about 75 vector instructions); the full form is
 // the text of round 5, instruction for instruction.  STEP_PRE / STEP_POST are the end of a step: FS_PK_P then FS_PK_A (full),
@@ -324,52 +325,67 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
 // is 2Z, bit for bit, and the NDZ step multiplies w by the entry's scalar register pair directly: three packed instructions
 // (FS_PK_ZA, FS_PK_ZB, FS_PK_PN) and the state's v_min3.  Unlike ND's, its condition is known BEFORE the steps, from the orbit
 // alone, so it is a threshold test where a body starts and needs no verdict afterwards.
-//   The bound.  k_make_quiet_orbit stores per orbit entry j the NDZ BODY bound (third companion, `znz`, one float per entry): with
-//   G = max(max|dz|, max|dc|) in true scale at entry j and g_k the growth factor of scaled_block_bound, the smallest of
-//     (a) 2^-26 min(|2Z_(j+m).re|, |2Z_(j+m).im|) / (g_j .. g_(j+m-1)),  m = 0 .. 7 -- the eight entries the body's steps leave from,
-//     (b) scaled_block_bound(j),  (c) scaled_block_bound(j + 4) / (g_j .. g_(j+3)),
-//   times (1 - 2^-10); "never" when a term is, when a part of some 2Z is zero or below 2^-100, when the result is below 2^-120
-//   (the integer compare of bit patterns below needs a normal number) or when j + 8 is past the orbit.
+//   The bounds.  k_make_quiet_orbit stores per orbit entry j the two NDZ BODY bounds (third companion, `znz`, a float2 per entry): on
+//   D = max|dz| and on C = max|dc| in true scale at entry j.  With lo_k = min(|2Z_k.re|, |2Z_k.im|), the growth an NDZ step really has,
+//   s_k = (|2Z_k.re| + |2Z_k.im|)(1 + 2^-10) (2Z as this loop reads it), A_0 = 1, B_0 = 0, A_(m+1) = s_(j+m) A_m, B_(m+1) = s_(j+m) B_m + 1:
+//     .x = min over m = 0 .. 7 of 2^-27 lo_(j+m) / A_m,   .y = min over m = 1 .. 7 of 2^-27 lo_(j+m) / B_m,
+//     each also within half of scaled_bound(Z_(j+8)) over A_8 / B_8 -- the eighth arrival's own bound test --, times (1 - 2^-10);
+//   both "never" when one of the entries j + 1 .. j + 8 has no usable bound or an entry j .. j + 7 has M >= 5.6 (scaled_block_bound(j)
+//   or (j + 4) is "never"), when a part of some 2Z is zero or below 2^-100, when a result is below 2^-120 (the integer compare of bit
+//   patterns below needs a normal number) or when j + 8 is past the orbit.  (Round 8 kept one bound on max(D, C) and divided by
+//   scaled_block_bound's g_k = 4 M_k + 3.8, valid for any G <= 1.4: 2^18 .. 2^21 over seven typical steps, so a body was refused until dz
+//   was 2^-40 and more below Z where 2^-26 is what exactness needs.  One bound with the growth s + 1 came first and its counting launch
+//   said what dc's own term would add: ndz_body_bound in kernels.hip has the figures.)
 //   1. Induction.  fl(a + d) == a whenever |d| <= 2^-26 |a| (argued for ND above).  The fma rounds once, and the product w 2^E is
-//      exact inside it (a power of two; it IS dz in true scale, which need not be representable on its own).  (b) makes the first
-//      four arrivals pass their bound tests and keeps G <= 1.4, so max|dz| at entry j + m is at most G g_j .. g_(j+m-1) for m <= 4;
-//      (c) says that this value at m = 4 is within scaled_block_bound(j + 4), which carries the same statement through m = 5 .. 8
-//      (3. below).  Hence G <= bound implies by (a), at each of the eight entries and in BOTH parts, |dz part| <= max|dz| <=
-//      2^-26 |2Z part|: s == 2Z in every lane, and the NDZ state is the ND state bit for bit -- which is the full form's once the
-//      ND verdict passes, as before: NDZ states are ND states, counted, floored (v61) and certified against F_run like them.
-//   2. The wave-uniform threshold.  G <= bound is tested as the block test is, and is safe for every lane for the same reasons:
-//      bits(max|w|) <= bound - eshm implies bits(max|w|) + Esh <= bound in each lane because eshm is the LARGEST Esh of the
-//      running lanes, and sdc, the wave's largest max|dc|, stands for the lanes' max|dc|.  T2 = min(bound - eshm, bits(Hz)), -1
-//      when sdc > bound: FS_BT_T's five instructions with another cap (FS_BT_TH).  Because bound <= scaled_block_bound(j) and
-//      Hz <= H, T2 <= T always: a body that passes T2 would have passed the block test.
+//      exact inside it (a power of two; it IS dz in true scale, which need not be representable on its own).  Hypothesis at step m
+//      (m = 0: D <= .x <= 2^-27 lo_j):  max|dz_m| <= A_m D + B_m C <= 2^-26 lo_(j+m), each half within 2^-27 lo_(j+m).
+//        => |dz part| <= 2^-26 |2Z part| in BOTH parts of every lane: s == 2Z, and the NDZ state is the ND state bit for bit -- which
+//           is the full form's once the ND verdict passes, as before: NDZ states are ND states, counted, floored (v61) and
+//           certified against F_run like them;
+//        => dz_(m+1) = dz_m 2Z + dc with |re| <= |dz.re| |2Z.re| + |dz.im| |2Z.im| + |dc.re| <= (|2Z.re| + |2Z.im|) max|dz_m| + C, the
+//           imaginary part alike; the products and sums round 2^-24 relative each, 1 + 2^-10 covers them:
+//           max|dz_(m+1)| <= s (A_m D + B_m C) + C = A_(m+1) D + B_(m+1) C;
+//        => the hypothesis at m + 1 by the terms m + 1 of .x and .y (m + 1 <= 7);
+//        => arrival m + 1 passes its bound test: 2^-26 lo <= 2^-25 zmax <= 2^-2 zmax = scaled_bound of a usable entry (lo <= 2 zmax);
+//           the eighth arrival by the halves of scaled_bound(Z_(j+8)).
+//   2. The wave-uniform threshold.  D <= .x is tested as the block test is, and is safe for every lane for the same reasons:
+//      bits(max|w|) <= .x - eshm implies bits(max|w|) + Esh <= .x in each lane because eshm is the LARGEST Esh of the running lanes,
+//      and sdc, the wave's largest max|dc|, stands for the lanes' max|dc| against .y.  T2 = min(.x - eshm, bits(Hz)), -1 when
+//      sdc > .y: FS_BT_T's five instructions with another cap and the second bound in the compare (FS_BT_THC).
+//      T2 against T.  Round 8's bound was within scaled_block_bound(j) and (j + 4), so a body that passed T2 would have passed the block
+//      tests.  These bounds are not, and need not be: FS_NDZ_TAIL and .Lfz_entry compute T afresh when T2 refuses; the NDZ body has no
+//      test inside, 1. vouches for its eight arrivals directly; where the NDZ loop leaves through .Lfn_out the caller takes a
+//      TESTED block (or ends the run), which tests every arrival itself; the counting build's c_blk_free counts the blocks the
+//      statement took, tested or vouched for.  What did lean on it is the counting build's REPLAY: the full form has to reach
+//      the add-free invocation's end to be compared with it, see there (block tests waived up to the last body, then as usual).
 //      Hz = 2^-5.  H asks for max|w| < 2^29 at every state a step leaves from; a body has no test inside, so its entering state
 //      has to vouch for the seven states after it.  In true scale G grows by at most g <= (4 * 5.6 + 3.8)(1 + 2^-10) < 26.23 a
-//      step, dc included, i.e. max(max|w|, max|dcs|) grows by that in the run's scale, and 26.23^7 < 2^33: the seven states stay
+//      step (h <= (22.4 + 1)(1 + 2^-10) is below that), dc included, i.e. max(max|w|, max|dcs|) grows by that in the run's scale,
+//      and 26.23^7 < 2^33: the seven states stay
 //      below 2^33 max(2^-5, max|dcs|) = 2^28 -- an ND run's max|dcs| is below 2^-49 (its entry vote: 2^26 max|dcs| <= a part of a
 //      state whose max is below 2^-23).  The eighth arrival (< 2^33) is the next decision's business: it fails Hz and H alike and
 //      the statement ends in front of it.  A run starts with max|w| < 2^-23 and View 5 gains 0.007 binades a step: Hz never binds.
-//   3. No test inside the body.  The full and ND bodies test w4 against the second block's T half way.  Here (c) did that ahead
-//      of time: max(max|dz_4|, max|dc|) <= G g_j .. g_(j+3) <= scaled_block_bound(j + 4), the very condition that test checks
-//      (with H replaced by 2.), so the arrivals 5 .. 8 pass their bound tests, and G <= 1.4 holds where each step starts.
+//   3. No test inside the body.  The full and ND bodies test w4 against the second block's T half way; the NDZ body needs none:
+//      1. covers all eight arrivals from the state the body starts with.
 //   The decision is taken where a body ends, for the next body, in the ND and the NDZ loop alike: max|w| against T2 first; when no
 //   lane exceeds it the next body is NDZ, otherwise today's compare against T follows and the ND loop goes on or ends.  An NDZ body
 //   is 24 packed + 8 v_min3 + 1 v_max + 1 v_cmp (4.25 per step, ND: 5.5); an ND body after a refused T2 pays one compare more.
-//   The bound of the next body's entry (s72) is loaded with the body's entries, from s[70:71] + off / 4; the statement reads the
+//   The bounds of the next body's entry (s[72:73]) are loaded with the body's entries, from s[70:71] + off / 2; the statement reads the
 //   bound of the entry it starts at itself (ND side only), so nothing about NDZ is live outside it.  The full form, the tested
 //   blocks, the per-lane path, FS_FAST_LOOP_FL, the hot runs and the careful step never take it.
 #define FS_NDZ_HZ "0x3d000000" /* bits(2^-5) */
-#define FS_BT_T2(BW) FS_BT_TH(BW, FS_NDZ_HZ)
+#define FS_BT_T2(BD, BC) FS_BT_THC(BD, BC, FS_NDZ_HZ) /* max|w| against the D bound, max|dc| against the C bound */
 #define FS_PK_ZA(W, Z) "v_pk_mul_f32 v[58:59], " W ", " Z " op_sel_hi:[0,1]\n\t"
 #define FS_PK_ZB(W, Z) "v_pk_mul_f32 v[56:57], " W ", " Z " op_sel:[1,1] op_sel_hi:[1,0]\n\t"
 #define FS_NDZ_STEP(W, WA, WB, Z, NW) FS_PK_ZA(W, Z) FS_FL_ACC(WA, WB) FS_PK_ZB(W, Z) FS_PK_PN(NW)
 // the next body's NDZ bound, requested with the body's entries (%[t] is free between a body's verdict and its next FS_BT_T)
 #define FS_NDZ_LOAD                                                                                                 \
-    "s_lshr_b32 %[t], %[off], 2\n\t"                                                                                \
-    "s_load_dword s72, s[70:71], %[t] offset:0x20\n\t"
+    "s_lshr_b32 %[t], %[off], 1\n\t"                                                                                \
+    "s_load_dwordx2 s[72:73], s[70:71], %[t] offset:0x40\n\t"
 // where a body ends: today's (full form) / the NDZ decision first (ND and NDZ loops)
 #define FS_FDU_TAIL(L) FS_BT_T("s67") FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") FS_BT_V "s_branch .L" L "_loop_%=\n"
 #define FS_NDZ_TAIL                                                                                                 \
-    FS_BT_T2("s72") FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") FS_BT_V                                            \
+    FS_BT_T2("s72", "s73") FS_T_X("v48", "v49") FS_FL_ACC("v48", "v49") FS_BT_V                                            \
     "s_cbranch_vccz .Lfz_loop_%=\n\t" FS_BT_T("s67") FS_BT_V "s_branch .Lfn_loop_%=\n"
 // the NDZ loop (CNT: the counting build's step counter, or nothing).  On the way out (fewer than eight steps left) it joins the
 // ND loop's exit: the state in v[48:49], max|w| in v60, s[64:65] / s67 of the entry the state is at, as the ND loop leaves them.
@@ -426,9 +442,9 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
         "s_mov_b32 %[st], 3\n\t"                                                                                    \
         "s_branch .Lfu_end_%=\n"                                                                                    \
         ".Lfz_entry_%=:\n\t" /* ND side: the NDZ bound of the entry the state is at, then the decision as where a body ends */ \
-        "s_lshr_b32 %[t], %[off], 2\n\t"                                                                            \
-        "s_load_dword s72, s[70:71], %[t]\n\t"                                                                      \
-        "s_waitcnt lgkmcnt(0)\n\t" FS_BT_T2("s72") FS_BT_V                                                          \
+        "s_lshr_b32 %[t], %[off], 1\n\t"                                                                            \
+        "s_load_dwordx2 s[72:73], s[70:71], %[t]\n\t"                                                               \
+        "s_waitcnt lgkmcnt(0)\n\t" FS_BT_T2("s72", "s73") FS_BT_V                                                          \
         "s_cbranch_vccz .Lfz_loop_%=\n\t" FS_BT_T("s67") FS_BT_V                                                    \
         "s_branch .Lfn_loop_%=\n"                                                                                   \
         FS_NDZ_LOOP(PF, CNT)                                                                                        \
@@ -453,11 +469,41 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
           [flr] "s"(kFloorBits)                                                                                     \
         : "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50",  \
           "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s66", "s72",  \
-          "vcc", "scc")
-// Runs for which a wave does not ask for the ND form again: after an entry vote that refused it / after a failed verdict (which
-// costs the run's steps a second time).  Wave-uniform counters; which form a run takes changes no result.
+          "s73", "vcc", "scc")
+// Runs for which a wave does not ask for the ND form again after an entry vote that refused it / after a failed verdict (which
+// costs the run's steps a second time): a wave-uniform penalty that follows what happened.  It starts at 0 -- the wave asks again
+// at the very next run: a verdict fails where the orbit passes a near-zero entry and dz 2Z drops to dc's size, the repeated run
+// has passed that place and the next one is usually eligible again --, each further refusal or failure in a row doubles it
+// (1, 2, 4, ..), capped at kNdBackoffEntry runs after a refused vote and kNdBackoffVerdict after a failed verdict, and an add-free
+// invocation that takes steps and passes its verdict resets it.  A shallow view, whose dc is never negligible, still converges to
+// one vote every kNdBackoffEntry runs, and a failed verdict cannot repeat at full cost run after run.  (Round 7's constants sat
+// out 8 / 32 runs after the FIRST refusal / failure.)  Which form a run takes changes no result.
 constexpr uint32_t kNdBackoffEntry = 8;
 constexpr uint32_t kNdBackoffVerdict = 32;
+// The back-off state after a refusal: runs to sit out (bits 8 ..; none is left when this is called) = the penalty so far (bits
+// 0 .. 7), capped at `cap`; the penalty itself goes 0, 1, 2, 4, .. kNdBackoffVerdict.  (The runs sit in the upper bits so that
+// "is a run being sat out" is one compare against a constant, as it was with a counter of its own.)
+__device__ __forceinline__ uint32_t nd_backoff_refused(uint32_t bo, uint32_t cap)
+{
+    const uint32_t pen = bo & 0xffu;
+    const uint32_t next = pen == 0u ? 1u : (pen < kNdBackoffVerdict ? pen * 2u : pen);
+    return ((pen < cap ? pen : cap) << 8) | next;
+}
+
+// (counting build) The ONE-term NDZ body bound this kernel had before dc got a term of its own -- G = max(max|dz|, max|dc|) against
+// the smallest 2^-26 lo_(j+m) over the growth (|2Z.re| + |2Z.im| + 1)(1 + 2^-10) per step, and the eighth arrival's own bound over it --
+// for the statistics word that says what the second term buys (38).  `e` = the second companion from the entry the body starts at
+// ({2Z.re, 2Z.im, the entry's own bound, -}), whose two-term bounds are not "never" (so e[0 .. 8] are usable).
+__device__ __forceinline__ float ndz_one_term_bound(const float4 *__restrict__ e)
+{
+    float best = 0x1p60f, grow = 1.0f;
+    for (uint32_t m = 0; m < 8; m++) {
+        const float zr = __builtin_fabsf(e[m].x), zi = __builtin_fabsf(e[m].y);
+        best = __builtin_fminf(best, __builtin_fminf(zr, zi) * 0x1p-26f / grow);
+        grow *= (zr + zi + 1.0f) * (1.0f + 0x1p-10f);
+    }
+    return __builtin_fminf(best, e[8].z / grow) * (1.0f - 0x1p-10f);
+}
 
 // The untested body with the deferred verdict, SIXTEEN steps per body (round 4).  A wave that is alone on its SIMD -- the
 // never-escaping pixels that decide C2's frame time, the last waves of a rank of an N-GPU split -- pays one L2 round trip per

@@ -1540,6 +1540,28 @@ extern "C" uint64_t fsh_orbit_scale_entries(fsh_orbit *o, const uint64_t *idx, c
         apply(o->f);
     return changed;
 }
+extern "C" uint64_t fsh_orbit_scale_parts(fsh_orbit *o, const uint64_t *idx, const int32_t *exp2_re, const int32_t *exp2_im, uint64_t n)
+{
+    uint64_t changed = 0;
+    auto apply = [&](auto &ob) {
+        if (ob.compressed)
+            return;
+        for (uint64_t k = 0; k < n; k++) {
+            if (idx[k] >= ob.x.size())
+                continue;
+            ob.x[idx[k]].e += exp2_re[k];
+            ob.y[idx[k]].e += exp2_im[k];
+            changed++;
+        }
+        ob.packed32.clear();
+        ob.packed64.clear();
+    };
+    if (o->is64)
+        apply(o->d);
+    else
+        apply(o->f);
+    return changed;
+}
 extern "C" uint64_t fsh_orbit_period(const fsh_orbit *o) { return o->is64 ? o->d.period : o->f.period; }
 
 extern "C" const fs_orbit_hdr32 *fsh_orbit_data_hdr32(fsh_orbit *o)

@@ -232,6 +232,13 @@ class Orbit:
         assert idx.shape == ex.shape
         return int(self._lib.fsh_orbit_scale_entries(self._h, idx.ctypes.data, ex.ctypes.data, idx.size))
 
+    def scale_parts(self, indices, exp2_re, exp2_im):
+        """Test hook (fsh_orbit_scale_parts): as scale_entries with an exponent per part -- near-axis entries where a test wants them."""
+        idx = np.ascontiguousarray(indices, np.uint64)
+        er, ei = np.ascontiguousarray(exp2_re, np.int32), np.ascontiguousarray(exp2_im, np.int32)
+        assert idx.shape == er.shape == ei.shape
+        return int(self._lib.fsh_orbit_scale_parts(self._h, idx.ctypes.data, er.ctypes.data, ei.ctypes.data, idx.size))
+
     @property
     def data_ptr(self):
         return self._lib.fsh_orbit_data_hdr64(self._h) if self.is64 else self._lib.fsh_orbit_data_hdr32(self._h)

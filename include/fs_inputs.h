@@ -104,6 +104,9 @@ uint64_t fsh_orbit_count(const fsh_orbit *o);  /* GetCountOrbitEntries(), includ
 /* Test hook: entries idx[k] of an uncompressed orbit scaled by 2^exp2[k] (period boundaries where a test of the LA builders
  * wants them; the result is not the orbit of any view).  Returns the number of entries changed. */
 uint64_t fsh_orbit_scale_entries(fsh_orbit *o, const uint64_t *idx, const int32_t *exp2, uint64_t n);
+/* The same with an exponent per part: the real part of entry idx[k] scaled by 2^exp2_re[k], the imaginary part by 2^exp2_im[k]
+ * (near-axis entries, one part far below the other, where a test of the tuned loops' orbit companions wants them). */
+uint64_t fsh_orbit_scale_parts(fsh_orbit *o, const uint64_t *idx, const int32_t *exp2_re, const int32_t *exp2_im, uint64_t n);
 uint64_t fsh_orbit_period(const fsh_orbit *o); /* GetPeriodMaybeZero() */
 const fs_orbit_hdr32 *fsh_orbit_data_hdr32(fsh_orbit *o);
 const fs_orbit_hdr64 *fsh_orbit_data_hdr64(fsh_orbit *o);

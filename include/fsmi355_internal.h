@@ -130,10 +130,15 @@ uint32_t fs_read_stats_raw(fs_renderer *r, uint64_t *out, uint64_t max_words);
  * min(bound_bits - scale_shift, 0x46800000) without wrap-around.  Host arrays.  tests/test_gpu_block_threshold.py. */
 uint32_t fs_test_block_threshold(fs_renderer *r, const int32_t *bound_bits, const int32_t *scale_shift, const int32_t *dc_bits,
                                  int32_t *threshold_out, uint32_t n);
-/* The same for the threshold of that loop's bodies without the dz add (NDZ; bound_bits = the NDZ body bound): -1 when dc_bits >
+/* The same for the threshold of that loop's bodies without the dz add (NDZ; bound_bits = the NDZ body bound, taken for both of its terms): -1 when dc_bits >
  * bound_bits, else min(bound_bits - scale_shift, 0x3D000000) without wrap-around.  tests/test_gpu_lav2_ndz.py. */
 uint32_t fs_test_ndz_threshold(fs_renderer *r, const int32_t *bound_bits, const int32_t *scale_shift, const int32_t *dc_bits,
                                int32_t *threshold_out, uint32_t n);
+/* Read-back of what k_make_quiet_orbit made of the current HDRFloat<float> orbit for that loop (after fs_upload_orbit):
+ * bounds_out[2 j], [2 j + 1] = the NDZ body bounds of entry j on max|dz| and on max|dc| (-0.0 = "never", both then), entries_out[4 j ..] = the second companion {2Z.re, 2Z.im, the entry's own bound, its
+ * block bound} as the loop reads them; either may be NULL.  At most max_entries entries; *n_out = entries the orbit has (its two spare
+ * entries included).  Synchronises the compute stream.  tests/test_gpu_lav2_ndz_tight.py holds the bounds against their definition. */
+uint32_t fs_read_ndz_bounds(fs_renderer *r, float *bounds_out, float *entries_out, uint64_t max_entries, uint64_t *n_out);
 /* Average duration (HIP events on the compute stream, `repeats` back-to-back launches, no D2H) of the two RenderCurrent
  * kernels over the current iteration buffer: ms_out[0] = antialias + palette, ms_out[1] = min / max / sum.  Needs a
  * palette (fs_init_memory) and the whole frame on this renderer.  tools/bench_render_current.py turns them into GB/s. */

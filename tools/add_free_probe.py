@@ -1,6 +1,10 @@
 """How much of the hand-scheduled body of the tuned LAv2 kernel (FS_FAST_LOOP_FDU, csrc/scaled_runs.hpp) runs in its add-free form,
 by workload: the statement's wave-steps, the share the ND form carried (word 30, NDZ bodies included) and the share that ran
-without the dz add as well (NDZ, word 35), the ND verdicts that failed (each repeats its run in the full form), and the counting instantiation's replay of every accepted add-free invocation in the full form (mismatches must be 0).
+without the dz add as well (NDZ, word 35), the ND verdicts that failed (each repeats its run in the full form), the full-form wave-steps
+taken while a wave was backing off from a refused entry vote or a failed verdict (word 36) and those among them whose entry vote would
+have passed (word 37: what the back-off policy leaves on the table), the NDZ wave-steps in bodies that the one-term bound
+(dc riding on dz's term, the bound before dc got a term of its own) would have refused (word 38: what the second term buys), and the counting instantiation's replay of every accepted add-free
+invocation in the full form (mismatches must be 0).
 Usage: python tools/add_free_probe.py [view width height [cpu|cpu_gpustage]] ...   (default: View 5 at 64x36 and at 3840x2160)"""
 import ctypes as C
 import json
@@ -42,6 +46,10 @@ for view, w, h, parity in jobs:
                       "ndz_wave_steps": raw[35], "ndz_share_of_statement": round(raw[35] / max(1, statement), 4),
                       "ndz_share_of_nd": round(raw[35] / max(1, raw[30]), 4),
                       "nd_verdicts_failed": raw[32],
+                      "full_form_wave_steps": statement - raw[30],
+                      "backed_off_full_form_wave_steps": raw[36], "backed_off_with_passing_vote": raw[37],
+                      "ndz_wave_steps_owed_to_the_dc_term": raw[38],
+                      "predicted_valu_instructions_saved_by_the_dc_term": 1.25 * raw[38],
                       "invocations_replayed": raw[34], "replay_mismatches": raw[33],
                       "predicted_valu_instructions_saved_by_nd": raw[30],
                       "predicted_valu_instructions_saved_by_ndz": 1.25 * raw[35]}), flush=True)
