@@ -68,7 +68,24 @@ class AutozoomResult(C.Structure):
                 ("score", C.c_double), ("sum_sq", C.c_double), ("sum_sq_x", C.c_double), ("sum_sq_y", C.c_double)]
 
 
+class AuditOffender(C.Structure):
+    """fs_audit_offender (include/fs_layout.h)."""
+    _fields_ = [("sample", u32), ("stable_bits", u32), ("frame_value", u64), ("exact_value", u64)]
+
+
+AUDIT_MAX_LEVELS, AUDIT_MAX_OFFENDERS = 8, 16
+
+
+class AuditResult(C.Structure):
+    """fs_audit_result (include/fs_layout.h)."""
+    _fields_ = [("n_samples", u32), ("n_levels", u32), ("n_equal", u32), ("n_differ", u32), ("n_capped", u32), ("n_offenders", u32),
+                ("stable", u32 * AUDIT_MAX_LEVELS), ("stable_differ", u32 * AUDIT_MAX_LEVELS),
+                ("stable_capped", u32 * AUDIT_MAX_LEVELS), ("max_abs_diff", u64 * AUDIT_MAX_LEVELS),
+                ("offenders", AuditOffender * AUDIT_MAX_OFFENDERS)]
+
+
 assert C.sizeof(AutozoomResult) == 200
+assert C.sizeof(AuditOffender) == 24 and C.sizeof(AuditResult) == 568
 assert C.sizeof(AtHdr32) == 116 and C.sizeof(AtHdr64) == 232 and C.sizeof(At2x32) == 184
 
 DONE_CB = C.CFUNCTYPE(None, vp)
@@ -132,6 +149,7 @@ def render_lib():
     _decl(lib, "fs_exact_sample_counts", u32, [vp, u32, u32, vp, vp, u32, u32, C.c_int, u64, vp])
     _decl(lib, "fs_render_exact_wide", u32, [vp, u32, u32, u32, vp, vp, u32, C.c_int, u64])
     _decl(lib, "fs_exact_wide_state", u32, [vp, u32, u32, vp, vp, u32, u32, vp, vp])
+    _decl(lib, "fs_exact_audit", u32, [vp, vp, u32, u32, vp, vp, u32, u32, vp, vp, u32, C.c_int, u64, C.POINTER(AuditResult), vp, vp, vp])
     _decl(lib, "fs_render_bla", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_render_direct", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_upload_orbit_scaled", u32, [vp, C.c_int, u32, vp, vp, u64, u64])
@@ -213,7 +231,7 @@ RENDER_SYMBOLS = [
     "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_feature_eval", "fs_feature_eval_direct", "fs_set_feature_slice",
     "fs_autozoom_pick", "fs_set_autozoom_gather_cap",
     "fs_render_exact", "fs_exact_stable_mask", "fs_set_exact_slice", "fs_read_exact_stats",
-    "fs_exact_sample_counts", "fs_render_exact_wide", "fs_exact_wide_state",
+    "fs_exact_sample_counts", "fs_render_exact_wide", "fs_exact_wide_state", "fs_exact_audit",
     "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
     "fs_render_direct_lp", "fs_clear",

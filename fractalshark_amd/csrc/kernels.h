@@ -524,8 +524,9 @@ struct FsExactArgs {
     uint32_t *dst_count;     // += samples still running
     unsigned long long *stats; // [0] += lane slots occupied in the step loop, [1] += steps taken
 };
+// samples: the list is W == H runs of their own, run e at cx[l * W + e], cy[l * W + e], and iters = uint64 counts[W] (fs_exact_audit)
 // false: `limbs` is not an instantiated limb count (nothing launched)
-bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, hipStream_t s);
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, hipStream_t s);
 // mask[y * W + x] = (first ? 1 : mask) & (centre == shifted) over two frames of the same pitch (elements)
 void fsk_exact_mask(const void *centre, const void *shifted, int iter_u64, uint8_t *mask, uint32_t W, uint32_t H, uint32_t pitch,
                     int first, hipStream_t s);
@@ -557,6 +558,22 @@ struct FsExactWideArgs {
 };
 // one workgroup of 64 per sample; false: the limb count needs more than 11 limbs per lane (nothing launched)
 bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, hipStream_t s);
+
+// ---- fs_exact_audit (kernels_exact_audit.hip, exact_audit_math.hpp): the frame at the samples against their runs' counts.
+// counts[k * n_samples + i] = run k of sample i (run 0 = c, run 1 + 4 j + d = level j's four shifts).  One workgroup of one wave
+// walks the samples in index order; per sample it also leaves exact, frame and stable_bits in the three arrays.
+struct FsAuditArgs {
+    const void *iters;
+    uint32_t iter_u64, pitch; // pitch in elements
+    const uint32_t *xs, *ys;
+    const uint64_t *counts;
+    uint32_t n_samples, n_levels;
+    uint64_t cap;
+    fs_audit_result *out;
+    uint64_t *exact, *frame;
+    uint32_t *stable;
+};
+void fsk_exact_audit(const FsAuditArgs &A, hipStream_t s);
 
 // multi-GPU tiler: out row y = in row index[y] (row_bytes a multiple of 16)
 void fsk_gather_rows(const void *in, void *out, const uint32_t *index, uint32_t row_bytes, uint32_t rows, hipStream_t s);

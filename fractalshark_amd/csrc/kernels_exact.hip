@@ -10,13 +10,17 @@
 //
 // Counting: n is the index of the z the lane holds (z_1 = c).  The test comes first: an escape at n leaves n - 1; a z_{N+1} that
 // has not escaped leaves N.  That is min(E - 1, N) of every other path.
+//
+// Sample mode (S = true; fs_exact_audit): the list is n runs of their own instead of a frame's pixels -- run e reads cx[l * n + e]
+// and cy[l * n + e] (A.W = A.H = n, the addressing of the wide kernel's W == 0) and leaves its count as uint64 in counts[e]
+// (A.iters).  Step loop, slices, compaction and statistics are the frame mode's, which compiles to what it was without the flag.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
 
 namespace {
 
-template <int L> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
+template <int L, bool S> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
 {
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     bool alive = i < A.n_src;
@@ -30,7 +34,7 @@ template <int L> __global__ void __launch_bounds__(64) k_exact_slice(const FsExa
     }
     if (__ballot(alive) == 0)
         return;
-    const uint32_t col = pix % A.W, row = pix / A.W;
+    const uint32_t col = S ? pix : pix % A.W, row = S ? pix : pix / A.W;
     uint32_t x[L], y[L], cx[L], cy[L];
 #pragma unroll
     for (int l = 0; l < L; l++) {
@@ -49,7 +53,7 @@ template <int L> __global__ void __launch_bounds__(64) k_exact_slice(const FsExa
         }
     }
 
-    const size_t out_idx = (size_t)row * A.rounded_width + col;
+    const size_t out_idx = S ? (size_t)pix : (size_t)row * A.rounded_width + col;
     uint32_t my_steps = 0, wave_steps = 0;
     for (uint32_t k = 0; k < A.slice; k++) {
         if (__ballot(alive) == 0)
@@ -60,7 +64,7 @@ template <int L> __global__ void __launch_bounds__(64) k_exact_slice(const FsExa
             const bool escaped = fsx::step<L>(x, y, cx, cy, A.P);
             if (escaped || n == A.cap + 1) {
                 const uint64_t v = escaped ? n - 1 : A.cap;
-                if (A.iter_u64)
+                if (S || A.iter_u64)
                     ((uint64_t *)A.iters)[out_idx] = v;
                 else
                     ((uint32_t *)A.iters)[out_idx] = (uint32_t)v;
@@ -121,13 +125,16 @@ __global__ void __launch_bounds__(256) k_exact_mask(const T *__restrict__ centre
 
 } // namespace
 
-bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, hipStream_t s)
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, hipStream_t s)
 {
     const dim3 grid((A.n_src + 63u) / 64u), block(64);
     switch (limbs) {
 #define FS_EXACT_CASE(L)                                                                                                \
     case L:                                                                                                             \
-        hipLaunchKernelGGL(k_exact_slice<L>, grid, block, 0, s, A);                                                     \
+        if (samples)                                                                                                    \
+            hipLaunchKernelGGL((k_exact_slice<L, true>), grid, block, 0, s, A);                                         \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_exact_slice<L, false>), grid, block, 0, s, A);                                        \
         return true;
         FS_EXACT_FOR_EACH_L(FS_EXACT_CASE)
 #undef FS_EXACT_CASE

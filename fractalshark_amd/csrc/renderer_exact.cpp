@@ -117,11 +117,13 @@ static bool exact_axis_in_range(const uint32_t *axis, uint32_t n, uint32_t limbs
 }
 
 // One exact frame into `out` (a buffer of the iteration buffer's geometry).  One device block per call: [counter, statistics | cx |
-// cy | two lists of running samples]; synchronous.
+// cy | two lists of running samples]; synchronous.  n_runs != 0 (fs_exact_audit): a list of n_runs runs of their own instead of a
+// frame, cx and cy holding n_runs values each and `out` uint64 counts[n_runs] on the device (the kernel's sample mode).
 static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
-                            uint32_t bailout, int inclusive, uint64_t n_iterations, void *out)
+                            uint32_t bailout, int inclusive, uint64_t n_iterations, void *out, uint32_t n_runs = 0)
 {
-    const uint32_t W = r->width, H = r->height, npix = W * H;
+    const bool samples = n_runs != 0;
+    const uint32_t W = samples ? n_runs : r->width, H = samples ? n_runs : r->height, npix = samples ? n_runs : W * H;
     const ExactLayout Y(limbs, W, H, npix);
     const bool compact = !r->exact_no_compaction;
     char *blk = nullptr;
@@ -132,8 +134,8 @@ static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, 
 
     FsExactArgs A{};
     A.cx = Y.cx(blk), A.cy = Y.cy(blk);
-    A.W = W, A.H = H, A.rounded_width = r->w_block * 16u;
-    A.iter_u64 = r->iter_bytes == 8 ? 1u : 0u;
+    A.W = W, A.H = H, A.rounded_width = samples ? 0u : r->w_block * 16u;
+    A.iter_u64 = samples || r->iter_bytes == 8 ? 1u : 0u;
     A.iters = out;
     A.cap = n_iterations;
     A.P = fsx::make_params(frac_bits, bailout, inclusive);
@@ -159,7 +161,7 @@ static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, 
                 A.src_pix = (const uint32_t *)(src + Y.xy_bytes + Y.n_bytes);
                 A.dst_xy = (uint32_t *)dst, A.dst_n = (uint64_t *)(dst + Y.xy_bytes), A.dst_pix = (uint32_t *)(dst + Y.xy_bytes + Y.n_bytes);
                 A.slice = r->exact_slice ? r->exact_slice : exact_default_slice(limbs, A.n_src);
-                return fsk_exact_slice(A, limbs, s);
+                return fsk_exact_slice(A, limbs, samples, s);
             },
             [&](uint32_t left) {
                 A.first = 0;
@@ -427,6 +429,97 @@ uint32_t fs_exact_wide_state(fs_renderer *r, uint32_t frac_bits, uint32_t limbs,
     const uint32_t rc = exact_wide_run(r, J);
     memcpy(r->exact_stats, keep, sizeof keep);
     return rc;
+}
+
+// ---- fs_exact_audit: the host side (kernels_exact.hip's sample mode or kernels_exact_wide.hip, then kernels_exact_audit.hip).
+// The runs of a call are one list: run k of sample i is entry k * n_samples + i, so limb plane l of the list is the caller's
+// cx_runs[k][l][..] for k = 0, 1, ... side by side.  One device block per call: [record | xs | ys | counts | exact | frame |
+// stable_bits]; the slices' own block comes and goes inside exact_frame / exact_wide_run.
+uint32_t fs_exact_audit(fs_renderer *r, const void *device_iters, uint32_t frac_bits, uint32_t limbs, const uint32_t *xs,
+                        const uint32_t *ys, uint32_t n_samples, uint32_t n_levels, const uint32_t *cx_runs, const uint32_t *cy_runs,
+                        uint32_t bailout, int inclusive, uint64_t n_iterations, fs_audit_result *out, uint64_t *exact_out,
+                        uint64_t *frame_out, uint32_t *stable_out)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (!r->memory_initialized() || !r->compute)
+        return FS_ERR_6;
+    if (r->local_rows != r->height)
+        return FS_ERR_UNSUPPORTED; // this renderer holds some rows of the frame only
+    if (uint32_t e = wide_check(frac_bits, limbs, bailout))
+        return e;
+    if (n_levels > FS_AUDIT_MAX_LEVELS)
+        return FS_ERR_UNSUPPORTED;
+    if (!out || (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8) || n_iterations == ~0ull)
+        return (uint32_t)hipErrorInvalidValue;
+    memset(out, 0, sizeof *out);
+    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    if (n_samples == 0)
+        return 0;
+    const uint32_t runs_per_sample = 1u + 4u * n_levels;
+    const uint64_t n_runs64 = (uint64_t)n_samples * runs_per_sample;
+    if (!xs || !ys || !cx_runs || !cy_runs || n_runs64 > kWideMaxSamples)
+        return (uint32_t)hipErrorInvalidValue;
+    for (uint32_t i = 0; i < n_samples; i++)
+        if (xs[i] >= r->width || ys[i] >= r->height)
+            return (uint32_t)hipErrorInvalidValue;
+    const uint32_t n_runs = (uint32_t)n_runs64;
+    // limb plane l of the list: run k's plane l behind run k - 1's
+    std::vector<uint32_t> cx((size_t)limbs * n_runs), cy((size_t)limbs * n_runs);
+    for (uint32_t k = 0; k < runs_per_sample; k++)
+        for (uint32_t l = 0; l < limbs; l++) {
+            const size_t src = ((size_t)k * limbs + l) * n_samples, dst = (size_t)l * n_runs + (size_t)k * n_samples;
+            memcpy(&cx[dst], cx_runs + src, (size_t)n_samples * 4);
+            memcpy(&cy[dst], cy_runs + src, (size_t)n_samples * 4);
+        }
+    if (!exact_axis_in_range(cx.data(), n_runs, limbs, frac_bits) || !exact_axis_in_range(cy.data(), n_runs, limbs, frac_bits))
+        return FS_ERR_UNSUPPORTED;
+
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t rec_bytes = up(sizeof(fs_audit_result)), xy_bytes = up((size_t)n_samples * 4), cnt_bytes = up((size_t)n_runs * 8),
+                 v_bytes = up((size_t)n_samples * 8);
+    char *blk = nullptr;
+    hipStream_t s = r->compute;
+    FS_TRY(r_alloc(r, (void **)&blk, rec_bytes + 3 * xy_bytes + cnt_bytes + 2 * v_bytes, kFrame));
+    FsAuditArgs A{};
+    A.iters = device_iters ? device_iters : r->iters();
+    A.iter_u64 = r->iter_bytes == 8 ? 1u : 0u, A.pitch = r->w_block * 16u;
+    A.out = (fs_audit_result *)blk;
+    A.xs = (const uint32_t *)(blk + rec_bytes), A.ys = (const uint32_t *)(blk + rec_bytes + xy_bytes);
+    A.counts = (const uint64_t *)(blk + rec_bytes + 2 * xy_bytes);
+    A.exact = (uint64_t *)(blk + rec_bytes + 2 * xy_bytes + cnt_bytes), A.frame = A.exact + v_bytes / 8;
+    A.stable = (uint32_t *)(blk + rec_bytes + 2 * xy_bytes + cnt_bytes + 2 * v_bytes);
+    A.n_samples = n_samples, A.n_levels = n_levels, A.cap = n_iterations;
+
+    uint32_t rc = (uint32_t)hipMemcpyAsync((void *)A.xs, xs, (size_t)n_samples * 4, hipMemcpyHostToDevice, s);
+    if (rc == 0)
+        rc = (uint32_t)hipMemcpyAsync((void *)A.ys, ys, (size_t)n_samples * 4, hipMemcpyHostToDevice, s);
+    if (rc == 0) {
+        if (limbs <= fsx::kMaxLimbs) {
+            rc = exact_frame(r, frac_bits, limbs, cx.data(), cy.data(), bailout, inclusive, n_iterations, (void *)A.counts, n_runs);
+        } else {
+            WideJob J{};
+            J.frac_bits = frac_bits, J.limbs = limbs, J.cx = cx.data(), J.cy = cy.data(), J.nx = J.ny = J.n = n_runs, J.W = 0;
+            J.bailout = bailout, J.inclusive = inclusive, J.cap = n_iterations;
+            J.out = (void *)A.counts, J.out_u64 = 1;
+            rc = exact_wide_run(r, J);
+        }
+    }
+    if (rc == 0) {
+        fsk_exact_audit(A, s);
+        rc = (uint32_t)hipGetLastError();
+    }
+    if (rc == 0)
+        rc = (uint32_t)hipMemcpyAsync(out, A.out, sizeof *out, hipMemcpyDeviceToHost, s);
+    if (rc == 0 && exact_out)
+        rc = (uint32_t)hipMemcpyAsync(exact_out, A.exact, (size_t)n_samples * 8, hipMemcpyDeviceToHost, s);
+    if (rc == 0 && frame_out)
+        rc = (uint32_t)hipMemcpyAsync(frame_out, A.frame, (size_t)n_samples * 8, hipMemcpyDeviceToHost, s);
+    if (rc == 0 && stable_out)
+        rc = (uint32_t)hipMemcpyAsync(stable_out, A.stable, (size_t)n_samples * 4, hipMemcpyDeviceToHost, s);
+    const uint32_t rs = (uint32_t)hipStreamSynchronize(s); // (also when something failed: the copies above read the caller's arrays)
+    (void)r_free(r, blk);
+    return rc ? rc : rs;
 }
 
 } // extern "C"

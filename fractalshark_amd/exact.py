@@ -6,6 +6,10 @@ csrc/kernels_exact.hip): x' = floor((x^2 - y^2) / 2^F) + cx, y' = floor(2xy / 2^
 equals GMP integer iteration of that recurrence on every pixel, and is an ordinary frame in the renderer's iteration buffer:
 min(E - 1, N) like every other path.  The axes come from the view's bounding-box strings read as exact rationals
 (fsh_view_exact_axes).
+
+audit() asks the library which sample pixels of a frame ANOTHER kernel rendered differ from those counts, and at which stability
+levels the frame is clean (fs_exact_audit: the runs of all samples and ladder positions as one list on the device, the frame read
+next to them, one small record back).
 """
 import numpy as np
 
@@ -84,6 +88,83 @@ def sample_counts(renderer, view, xs, ys, bailout=4, frac_bits=None, levels=(), 
     return values, stable
 
 
+def lattice(view, cols, rows):
+    """(xs, ys) = uint32[n] each: `cols` x `rows` samples spread evenly over the view's antialiased frame, the first and the last
+    row and column included, row-major (rounded positions that coincide are taken once)."""
+    w, h = view.width * view.antialiasing, view.height * view.antialiasing
+    ax = np.unique(np.round(np.linspace(0, w - 1, cols)).astype(np.int64))
+    ay = np.unique(np.round(np.linspace(0, h - 1, rows)).astype(np.int64))
+    gx, gy = np.meshgrid(ax, ay)
+    return gx.ravel().astype(np.uint32), gy.ravel().astype(np.uint32)
+
+
+MIN_STABLE_SAMPLES, MIN_STABLE_SHARE = 100, 0.2  # the floors a stable set must meet to carry a verdict (DESIGN.md 2.2)
+
+
+class AuditReport:
+    """What fs_exact_audit says about a frame.  The record's fields: n_samples, n_levels, n_equal, n_differ, n_capped,
+    n_offenders, and per level, in the order of `levels`, stable_count (the record's stable[]), stable_differ, stable_capped and
+    max_abs_diff; `record` is the _capi.AuditResult itself.  Per sample: values (the exact counts, int64[n]), frame_values
+    (int64[n]) and stable (bool[n, len(levels)]).  offenders: the first (at most 16) differing samples in sample order, as dicts
+    {sample, x, y, frame_value, exact_value, stable: [bool per level]}."""
+
+    def __init__(self, levels, n_samples, stable_count, stable_differ, stable_capped=None, max_abs_diff=None, n_equal=0, n_differ=0,
+                 n_capped=0, offenders=(), values=None, frame_values=None, stable=None, record=None):
+        k = len(levels)
+        ints = lambda a: [int(v) for v in (a if a is not None else [0] * k)]
+        self.levels, self.n_samples, self.n_levels = tuple(int(lv) for lv in levels), int(n_samples), k
+        self.stable_count, self.stable_differ = ints(stable_count), ints(stable_differ)
+        self.stable_capped, self.max_abs_diff = ints(stable_capped), ints(max_abs_diff)
+        self.n_equal, self.n_differ, self.n_capped = int(n_equal), int(n_differ), int(n_capped)
+        self.offenders = list(offenders)
+        self.n_offenders = len(self.offenders)
+        self.values, self.frame_values, self.stable, self.record = values, frame_values, stable, record
+
+    def finest_clean_level(self, min_samples=MIN_STABLE_SAMPLES, min_share=MIN_STABLE_SHARE):
+        """The finest level (the largest k of s = width / 2^k) at which the frame misses on no stable sample and whose stable set
+        holds at least min_samples samples and min_share of all samples; None when there is none."""
+        clean = [lv for lv, n, bad in zip(self.levels, self.stable_count, self.stable_differ)
+                 if bad == 0 and n >= min_samples and n >= min_share * self.n_samples]
+        return max(clean) if clean else None
+
+    def as_dict(self):
+        """The record as plain Python values (what tools/audit_frame.py prints)."""
+        return {"levels": list(self.levels), "n_samples": self.n_samples, "n_equal": self.n_equal, "n_differ": self.n_differ,
+                "n_capped": self.n_capped, "stable": self.stable_count, "stable_differ": self.stable_differ,
+                "stable_capped": self.stable_capped, "max_abs_diff": self.max_abs_diff}
+
+
+def audit(renderer, view, xs, ys, levels=(), bailout=256, frac_bits=None, inclusive=False, device_iters=None):
+    """The frame in the renderer's iteration buffer (or device_iters: another device buffer of its geometry) against the exact
+    counts min(E - 1, view.num_iterations) at the samples (xs[i], ys[i]) of the view's antialiased frame, with the stability of
+    every sample at the ladder `levels` (at most 8; s = the frame's width / 2^level): an AuditReport.  One call (fs_exact_audit):
+    all len(xs) * (1 + 4 len(levels)) runs advance as one list on the device, the frame is read next to them, and only the record
+    and three small per-sample arrays come back.  The frame's rule must be min(E - 1, N): the perturbation kernels (bailout 256)
+    and the direct kernels with a CPU twin (bailout 4), not the low-precision direct kernels."""
+    F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
+    L = limbs_for(F)
+    levels = tuple(int(lv) for lv in levels)
+    xs, ys = np.asarray(xs, np.int64), np.asarray(ys, np.int64)
+    cx, cy = axes(view, F, limbs=L)
+    cx_runs, cy_runs = [cx[:, xs]], [cy[:, ys]]
+    for level in levels:
+        cx3, cy3 = axes(view, F, level=level, limbs=L)
+        for ax, ay in ((cx3[1], cy3[0]), (cx3[2], cy3[0]), (cx3[0], cy3[1]), (cx3[0], cy3[2])):  # c + s, c - s, c + is, c - is
+            cx_runs.append(ax[:, xs])
+            cy_runs.append(ay[:, ys])
+    err, res, values, frame_values, bits = renderer.ExactAudit(F, L, xs, ys, np.stack(cx_runs), np.stack(cy_runs), bailout, inclusive,
+                                                               view.num_iterations, device_iters=device_iters)
+    _check(renderer, err, "fs_exact_audit")
+    k = len(levels)
+    stable = ((bits[:, None] >> np.arange(k, dtype=np.uint32)[None, :]) & 1).astype(bool).reshape(len(xs), k)
+    offenders = [{"sample": int(o.sample), "x": int(xs[o.sample]), "y": int(ys[o.sample]), "frame_value": int(o.frame_value),
+                  "exact_value": int(o.exact_value), "stable": [bool((o.stable_bits >> j) & 1) for j in range(k)]}
+                 for o in res.offenders[:res.n_offenders]]
+    return AuditReport(levels, res.n_samples, res.stable[:k], res.stable_differ[:k], res.stable_capped[:k], res.max_abs_diff[:k],
+                       res.n_equal, res.n_differ, res.n_capped, offenders, values.astype(np.int64), frame_values.astype(np.int64),
+                       stable, res)
+
+
 def stable_mask(renderer, view, level, bailout=4, frac_bits=None):
     """bool[H, W]: the pixels of the exact frame in the iteration buffer (exact.render of the same view, bailout and frac_bits,
     strict) whose count is the same at c +- s and c +- is, s = the frame's width / 2^level."""
@@ -96,4 +177,4 @@ def stable_mask(renderer, view, level, bailout=4, frac_bits=None):
 
 
 __all__ = ["GUARD_BITS", "MAX_FRAC_BITS", "MAX_WIDE_LIMBS", "MAX_WIDE_FRAC_BITS", "limbs_for", "axes", "render", "uses_wide",
-           "sample_counts", "stable_mask"]
+           "sample_counts", "stable_mask", "lattice", "audit", "AuditReport"]

@@ -193,6 +193,30 @@ class GPURenderer:
                                                int(bailout), 1 if inclusive else 0, int(n_iterations), out.ctypes.data)
         return err, out
 
+    def ExactAudit(self, frac_bits, limbs, xs, ys, cx_runs, cy_runs, bailout, inclusive, n_iterations, device_iters=None,
+                   per_sample=True):
+        """fs_exact_audit: the frame in the iteration buffer (device_iters: another device buffer of the frame's geometry, raw
+        pointer) against exact counts at the samples (xs[i], ys[i]).  cx_runs, cy_runs = uint32[1 + 4 n_levels, limbs, n]: run 0 = c,
+        run 1 + 4 j + d = level j's c + s, c - s, c + is, c - is.  Returns (error code, _capi.AuditResult, exact uint64[n], frame
+        uint64[n], stable_bits uint32[n]); the three arrays are None without per_sample, and then only the record crosses the bus.
+        Synchronous."""
+        xs, ys = np.ascontiguousarray(xs, np.uint32), np.ascontiguousarray(ys, np.uint32)
+        cx_runs, cy_runs = np.ascontiguousarray(cx_runs, np.uint32), np.ascontiguousarray(cy_runs, np.uint32)
+        n = len(xs)
+        if xs.ndim != 1 or ys.shape != xs.shape:
+            raise ValueError("xs, ys must be two lists of the same length")
+        if cx_runs.ndim != 3 or cx_runs.shape != cy_runs.shape or cx_runs.shape[1:] != (limbs, n) or cx_runs.shape[0] % 4 != 1:
+            raise ValueError("cx_runs, cy_runs must both be uint32[1 + 4 n_levels, limbs, n]")
+        res = _capi.AuditResult()
+        exact = np.zeros(n, np.uint64) if per_sample else None
+        frame = np.zeros(n, np.uint64) if per_sample else None
+        bits = np.zeros(n, np.uint32) if per_sample else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        err = self._lib.fs_exact_audit(self._h, device_iters, int(frac_bits), int(limbs), xs.ctypes.data, ys.ctypes.data, n,
+                                       cx_runs.shape[0] // 4, cx_runs.ctypes.data, cy_runs.ctypes.data, int(bailout),
+                                       1 if inclusive else 0, int(n_iterations), C.byref(res), ptr(exact), ptr(frame), ptr(bits))
+        return err, res, exact, frame, bits
+
     def ExactWideState(self, frac_bits, limbs, cx, cy, steps):
         """Test hook (fs_exact_wide_state): (error code, x, y) -- uint32[limbs, n] each: z after `steps` steps of the wide kernel
         from z_1 = c, a z beyond |z|^2 > 256 kept as it is."""

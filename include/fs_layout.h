@@ -499,9 +499,31 @@ typedef struct fs_autozoom_result {
     double sum_sq, sum_sq_x, sum_sq_y;
 } fs_autozoom_result;
 
+/* fs_exact_audit (fsmi355.h): what a frame gets wrong against exact counts on a list of sample pixels.  Level j of the call's
+ * stability ladder is bit j of stable_bits and index j of the per-level arrays; a sample is stable at a level when its exact count
+ * is the same at c + s, c - s, c + i s and c - i s.  A capped sample (exact == n_iterations) counts like any other.  Only the
+ * first n_levels entries of the per-level arrays and the first n_offenders offenders are set, the rest is zero. */
+enum { FS_AUDIT_MAX_LEVELS = 8, FS_AUDIT_MAX_OFFENDERS = 16 };
+typedef struct fs_audit_offender {
+    uint32_t sample, stable_bits; /* index into the call's sample list; the levels it is stable at */
+    uint64_t frame_value, exact_value;
+} fs_audit_offender;
+typedef struct fs_audit_result {
+    uint32_t n_samples, n_levels;
+    uint32_t n_equal, n_differ;   /* frame == exact, frame != exact: n_equal + n_differ == n_samples */
+    uint32_t n_capped;            /* exact == n_iterations */
+    uint32_t n_offenders;         /* min(n_differ, FS_AUDIT_MAX_OFFENDERS) */
+    uint32_t stable[FS_AUDIT_MAX_LEVELS];        /* samples stable at the level, capped ones included */
+    uint32_t stable_differ[FS_AUDIT_MAX_LEVELS]; /* ... of which the frame differs on */
+    uint32_t stable_capped[FS_AUDIT_MAX_LEVELS]; /* ... of which are capped */
+    uint64_t max_abs_diff[FS_AUDIT_MAX_LEVELS];  /* max |frame - exact| over the level's stable differing samples; 0 if none */
+    fs_audit_offender offenders[FS_AUDIT_MAX_OFFENDERS]; /* the first differing samples in sample order */
+} fs_audit_result;
+
 #ifdef __cplusplus
 }
 static_assert(sizeof(fs_autozoom_result) == 200, "autozoom record");
+static_assert(sizeof(fs_audit_offender) == 24 && sizeof(fs_audit_result) == 568, "audit record");
 static_assert(sizeof(fs_feature_in_hdr32) == 32&& sizeof(fs_feature_in_hdr64) == 56 && sizeof(fs_feature_out_hdr32) == 64 &&
                   sizeof(fs_feature_out_hdr64) == 104,
               "Feature Finder records");

@@ -334,6 +334,29 @@ uint32_t fs_exact_sample_counts(fs_renderer *r, uint32_t frac_bits, uint32_t lim
                                 uint32_t n_samples, uint32_t bailout, int inclusive, uint64_t n_iterations, uint64_t *counts_out);
 uint32_t fs_render_exact_wide(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx,
                               const uint32_t *cy, uint32_t bailout, int inclusive, uint64_t n_iterations);
+/* The exact audit: the project's definition of a correct frame -- equal to the exact count on every sample that is stable at a
+ * stated level -- as one call on the frame in the iteration buffer (device_iters: another device buffer of the same
+ * geometry and IterType, NULL = the current one).  n_samples sample pixels (xs[i], ys[i]) of the W x H of fs_init_memory and a
+ * ladder of n_levels <= FS_AUDIT_MAX_LEVELS shifts give n_samples * (1 + 4 n_levels) runs of the exact recurrence above:
+ * cx_runs, cy_runs = [1 + 4 n_levels][limbs][n_samples] (host), run 0 = c and run 1 + 4 j + d = c + s_j, c - s_j, c + i s_j,
+ * c - i s_j for d = 0 .. 3.  All runs of a call are ONE list that fills the chip and compacts together: one lane per run for
+ * limbs = 2 .. 24, one wave per run beyond, up to 704.  A second kernel reads the frame at the samples, next to it, and reduces
+ * everything to *out (fs_layout.h): exact = the count of run 0, bit j of stable_bits = the four counts of level j equal it, differ =
+ * frame != exact.  Integers only; the same record from run to run.  Only the record crosses the bus, and whichever of
+ * exact_out[n_samples], frame_out[n_samples], stable_out[n_samples] (the stable_bits) are not NULL.
+ * The rule is min(E - 1, n_iterations): the perturbation families (bailout 256) and the direct kernels that have a CPU twin
+ * (bailout 4).  The low-precision direct kernels of fs_render_direct_lp count differently (a row shift, multiples of
+ * iteration_precision): their frames are out of scope.
+ * Synchronous on the compute stream; the frame, the orbit and LA caches, recorded tile costs and orders and the kernel-time history
+ * are left as they were.  fs_read_exact_stats reports the call's lane slots, steps and launches.  n_samples == 0: 0 and a zeroed
+ * record.
+ * FS_ERR_6: no fs_init_memory yet.  FS_ERR_UNSUPPORTED: row bands set; limbs outside 2 .. 704 or 32 * limbs < frac_bits + 10;
+ * bailout outside 1 .. 256; n_levels > 8; an axis value outside [-32, 32).  hipErrorInvalidValue: NULL xs, ys, cx_runs, cy_runs
+ * or out; a sample outside the frame; more than 2^31 - 1 runs; an n_iterations the frame's IterType cannot hold. */
+uint32_t fs_exact_audit(fs_renderer *r, const void *device_iters, uint32_t frac_bits, uint32_t limbs, const uint32_t *xs,
+                        const uint32_t *ys, uint32_t n_samples, uint32_t n_levels, const uint32_t *cx_runs, const uint32_t *cy_runs,
+                        uint32_t bailout, int inclusive, uint64_t n_iterations, fs_audit_result *out, uint64_t *exact_out,
+                        uint64_t *frame_out, uint32_t *stable_out);
 
 /* GPURenderer::ClearMemory<IterType> (GPU_Render.cu:212-225). */
 uint32_t fs_clear(fs_renderer *r);
