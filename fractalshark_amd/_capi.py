@@ -150,6 +150,10 @@ def render_lib():
     _decl(lib, "fs_render_exact_wide", u32, [vp, u32, u32, u32, vp, vp, u32, C.c_int, u64])
     _decl(lib, "fs_exact_wide_state", u32, [vp, u32, u32, vp, vp, u32, u32, vp, vp])
     _decl(lib, "fs_exact_audit", u32, [vp, vp, u32, u32, vp, vp, u32, u32, vp, vp, u32, C.c_int, u64, C.POINTER(AuditResult), vp, vp, vp])
+    _decl(lib, "fs_set_exact_cycle_check", u32, [vp, C.c_int])
+    _decl(lib, "fs_read_exact_proved", u32, [vp, vp, u64])
+    _decl(lib, "fs_read_exact_cycle_stats", u32, [vp, vp])
+    _decl(lib, "fs_set_exact_cycle_fingerprint_bits", u32, [vp, u32])
     _decl(lib, "fs_render_bla", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_render_direct", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_upload_orbit_scaled", u32, [vp, C.c_int, u32, vp, vp, u64, u64])
@@ -232,6 +236,7 @@ RENDER_SYMBOLS = [
     "fs_autozoom_pick", "fs_set_autozoom_gather_cap",
     "fs_render_exact", "fs_exact_stable_mask", "fs_set_exact_slice", "fs_read_exact_stats",
     "fs_exact_sample_counts", "fs_render_exact_wide", "fs_exact_wide_state", "fs_exact_audit",
+    "fs_set_exact_cycle_check", "fs_read_exact_proved", "fs_read_exact_cycle_stats", "fs_set_exact_cycle_fingerprint_bits",
     "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
     "fs_render_direct_lp", "fs_clear",

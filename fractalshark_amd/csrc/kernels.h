@@ -523,10 +523,15 @@ struct FsExactArgs {
     uint32_t slice;          // steps per lane at most
     uint32_t *dst_count;     // += samples still running
     unsigned long long *stats; // [0] += lane slots occupied in the step loop, [1] += steps taken
+    // the cycle check (read by the C = true kernels only; exact_cycle_math.hpp): the checkpoints of the running samples, 2L more
+    // limb planes per list (tx, then ty); stats[2] += samples finished by proof, stats[3] += checkpoints read back
+    uint32_t *src_ck, *dst_ck;
+    uint8_t *proved;         // [W * H] (samples: [W]): 1 where the sample was proved; zeroed by the caller
+    uint32_t fp_mx, fp_my;   // the fingerprint masks on x[0] and y[0]
 };
 // samples: the list is W == H runs of their own, run e at cx[l * W + e], cy[l * W + e], and iters = uint64 counts[W] (fs_exact_audit)
-// false: `limbs` is not an instantiated limb count (nothing launched)
-bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, hipStream_t s);
+// cycle: the kernels with the cycle check.  false: `limbs` is not an instantiated limb count (nothing launched)
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, hipStream_t s);
 // mask[y * W + x] = (first ? 1 : mask) & (centre == shifted) over two frames of the same pitch (elements)
 void fsk_exact_mask(const void *centre, const void *shifted, int iter_u64, uint8_t *mask, uint32_t W, uint32_t H, uint32_t pitch,
                     int first, hipStream_t s);

@@ -14,13 +14,20 @@
 // Sample mode (S = true; fs_exact_audit): the list is n runs of their own instead of a frame's pixels -- run e reads cx[l * n + e]
 // and cy[l * n + e] (A.W = A.H = n, the addressing of the wide kernel's W == 0) and leaves its count as uint64 in counts[e]
 // (A.iters).  Step loop, slices, compaction and statistics are the frame mode's, which compiles to what it was without the flag.
+//
+// Cycle check (C = true; fs_set_exact_cycle_check, exact_cycle_math.hpp holds the rule and its proof): a sample whose state repeats
+// its checkpoint limb for limb never escapes; it leaves the cap at once and 1 in proved[pixel] (sample mode: proved[e]).  The
+// checkpoint is 2L more limb planes per list, the lane's slot of the SOURCE list while the slice runs: written there when it is
+// taken, read back only when the two-register fingerprint matches, and copied to the destination slot with the rest of the state by
+// a lane that goes on to the next slice.  C = false compiles to what it was without the parameter.
 #include <hip/hip_runtime.h>
 
+#include "exact_cycle_math.hpp"
 #include "kernels.h"
 
 namespace {
 
-template <int L, bool S> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
+template <int L, bool S, bool C> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
 {
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     bool alive = i < A.n_src;
@@ -53,6 +60,17 @@ template <int L, bool S> __global__ void __launch_bounds__(64) k_exact_slice(con
         }
     }
 
+    // the checkpoint: this lane's slot of the source list's planes (a running lane's slot is i); its low limbs stay in registers
+    uint32_t fx = 0, fy = 0, my_compares = 0, my_proved = 0;
+    if constexpr (C) {
+        if (A.first) {
+            if (alive)
+                fsx::cycle_take<L>(x, y, A.src_ck, A.stride, i, fx, fy);
+        } else {
+            fx = A.src_ck[slot], fy = A.src_ck[(size_t)L * A.stride + slot];
+        }
+    }
+
     const size_t out_idx = S ? (size_t)pix : (size_t)row * A.rounded_width + col;
     uint32_t my_steps = 0, wave_steps = 0;
     for (uint32_t k = 0; k < A.slice; k++) {
@@ -71,6 +89,19 @@ template <int L, bool S> __global__ void __launch_bounds__(64) k_exact_slice(con
                 alive = false;
             } else {
                 n++;
+                if constexpr (C) {
+                    if (fsx::cycle_check<L>(x, y, n, A.src_ck, A.stride, i, fx, fy, A.fp_mx, A.fp_my, my_compares)) {
+                        if (S || A.iter_u64)
+                            ((uint64_t *)A.iters)[out_idx] = A.cap;
+                        else
+                            ((uint32_t *)A.iters)[out_idx] = (uint32_t)A.cap;
+                        uint32_t p = pix;
+                        FSX_PIN(p); // (the address is made here, not kept across the loop)
+                        A.proved[p] = 1;
+                        my_proved = 1;
+                        alive = false;
+                    }
+                }
             }
         }
     }
@@ -96,6 +127,13 @@ template <int L, bool S> __global__ void __launch_bounds__(64) k_exact_slice(con
         }
         A.dst_n[dst] = n;
         A.dst_pix[dst] = pix;
+        if constexpr (C) {
+            if (A.compact) { // (without compaction source and destination are one list and dst == slot)
+#pragma unroll
+                for (int l = 0; l < 2 * L; l++)
+                    A.dst_ck[(size_t)l * A.stride + dst] = A.src_ck[(size_t)l * A.stride + i];
+            }
+        }
     } else if (!A.compact && i < A.n_src) {
         A.dst_n[dst] = 0;
         A.dst_pix[dst] = 0;
@@ -108,6 +146,19 @@ template <int L, bool S> __global__ void __launch_bounds__(64) k_exact_slice(con
     if (threadIdx.x == 0) {
         atomicAdd(&A.stats[0], 64ull * wave_steps);
         atomicAdd(&A.stats[1], (unsigned long long)my_steps);
+    }
+    if constexpr (C) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            my_proved += __shfl_xor(my_proved, off);
+            my_compares += __shfl_xor(my_compares, off);
+        }
+        if (threadIdx.x == 0) {
+            if (my_proved)
+                atomicAdd(&A.stats[2], (unsigned long long)my_proved);
+            if (my_compares)
+                atomicAdd(&A.stats[3], (unsigned long long)my_compares);
+        }
     }
 }
 
@@ -125,16 +176,20 @@ __global__ void __launch_bounds__(256) k_exact_mask(const T *__restrict__ centre
 
 } // namespace
 
-bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, hipStream_t s)
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, hipStream_t s)
 {
     const dim3 grid((A.n_src + 63u) / 64u), block(64);
     switch (limbs) {
 #define FS_EXACT_CASE(L)                                                                                                \
     case L:                                                                                                             \
-        if (samples)                                                                                                    \
-            hipLaunchKernelGGL((k_exact_slice<L, true>), grid, block, 0, s, A);                                         \
+        if (cycle && samples)                                                                                           \
+            hipLaunchKernelGGL((k_exact_slice<L, true, true>), grid, block, 0, s, A);                                   \
+        else if (cycle)                                                                                                 \
+            hipLaunchKernelGGL((k_exact_slice<L, false, true>), grid, block, 0, s, A);                                  \
+        else if (samples)                                                                                               \
+            hipLaunchKernelGGL((k_exact_slice<L, true, false>), grid, block, 0, s, A);                                  \
         else                                                                                                            \
-            hipLaunchKernelGGL((k_exact_slice<L, false>), grid, block, 0, s, A);                                        \
+            hipLaunchKernelGGL((k_exact_slice<L, false, false>), grid, block, 0, s, A);                                 \
         return true;
         FS_EXACT_FOR_EACH_L(FS_EXACT_CASE)
 #undef FS_EXACT_CASE

@@ -1,21 +1,27 @@
 #include "renderer_state.hpp"
 
+#include "exact_cycle_math.hpp"
+
 using namespace fsr;
 
 // ---- what the two exact paths (fs_render_exact: a lane per sample, fs_render_exact_wide: a wave per sample) share on the host.
 // The device block of one call: [counter, statistics | cx | cy | `lists` lists of running samples], a list being the limb planes of
-// x and y, then n, then the sample's id.
+// x and y, then n, then the sample's id; with the cycle check (`cycle`) a list ends with the limb planes of the checkpoints, and
+// the block with the byte plane of the proved samples.
 struct ExactLayout {
     static constexpr size_t head = 256;
-    size_t cx_bytes, cy_bytes, xy_bytes, n_bytes, id_bytes, list_bytes;
-    ExactLayout(uint32_t limbs, uint32_t nx, uint32_t ny, uint32_t n)
+    size_t cx_bytes, cy_bytes, xy_bytes, n_bytes, id_bytes, list_bytes, proved_bytes;
+    ExactLayout(uint32_t limbs, uint32_t nx, uint32_t ny, uint32_t n, bool cycle = false)
     {
         auto up = [](size_t b) { return (b + 255) / 256 * 256; };
         cx_bytes = up((size_t)limbs * nx * 4), cy_bytes = up((size_t)limbs * ny * 4);
         xy_bytes = up((size_t)2 * limbs * n * 4), n_bytes = up((size_t)n * 8), id_bytes = up((size_t)n * 4);
-        list_bytes = xy_bytes + n_bytes + id_bytes;
+        list_bytes = xy_bytes + n_bytes + id_bytes + (cycle ? xy_bytes : 0);
+        proved_bytes = cycle ? up(n) : 0;
     }
-    size_t bytes(int lists) const { return head + cx_bytes + cy_bytes + (size_t)lists * list_bytes; }
+    size_t bytes(int lists) const { return head + cx_bytes + cy_bytes + (size_t)lists * list_bytes + proved_bytes; }
+    uint32_t *checkpoints(char *list) const { return (uint32_t *)(list + xy_bytes + n_bytes + id_bytes); }
+    uint8_t *proved(char *blk, int lists) const { return (uint8_t *)list(blk, lists); }
     uint32_t *count(char *blk) const { return (uint32_t *)blk; }
     unsigned long long *stats(char *blk) const { return (unsigned long long *)(blk + 16); }
     uint32_t *cx(char *blk) const { return (uint32_t *)(blk + head); }
@@ -83,6 +89,52 @@ uint32_t fs_read_exact_stats(const fs_renderer *r, uint64_t out[4])
     return 0;
 }
 
+uint32_t fs_set_exact_cycle_check(fs_renderer *r, int enable)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    r->exact_cycle_check = enable != 0;
+    return 0;
+}
+
+uint32_t fs_set_exact_cycle_fingerprint_bits(fs_renderer *r, uint32_t bits)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    r->exact_cycle_fp_bits = bits;
+    return 0;
+}
+
+uint32_t fs_read_exact_cycle_stats(const fs_renderer *r, uint64_t out[2])
+{
+    if (!r || !out)
+        return hipErrorInvalidValue;
+    memcpy(out, r->exact_cycle_stats, sizeof r->exact_cycle_stats);
+    return 0;
+}
+
+uint32_t fs_read_exact_proved(const fs_renderer *r, uint8_t *out, uint64_t n)
+{
+    if (!r || !out)
+        return hipErrorInvalidValue;
+    if (!r->exact_proved_valid)
+        return FS_ERR_6;
+    if (n != r->exact_proved.size())
+        return hipErrorInvalidValue;
+    memcpy(out, r->exact_proved.data(), (size_t)n);
+    return 0;
+}
+
+// What every exact entry point does to the statistics before it starts.  keep_proved: the call leaves the mask of
+// fs_read_exact_proved as it is (the shifted frames of fs_exact_stable_mask with the check on).
+static void exact_reset_stats(fs_renderer *r, bool keep_proved = false)
+{
+    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    memset(r->exact_cycle_stats, 0, sizeof r->exact_cycle_stats);
+    if (!keep_proved)
+        r->exact_proved_valid = false;
+}
+
 // What both entry points refuse, in the order the header lists it.
 static uint32_t exact_begin(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, uint32_t bailout, uint64_t n_iterations)
 {
@@ -119,12 +171,15 @@ static bool exact_axis_in_range(const uint32_t *axis, uint32_t n, uint32_t limbs
 // One exact frame into `out` (a buffer of the iteration buffer's geometry).  One device block per call: [counter, statistics | cx |
 // cy | two lists of running samples]; synchronous.  n_runs != 0 (fs_exact_audit): a list of n_runs runs of their own instead of a
 // frame, cx and cy holding n_runs values each and `out` uint64 counts[n_runs] on the device (the kernel's sample mode).
+// With the cycle check on (fs_set_exact_cycle_check) the C = true kernels run and the lists carry the checkpoints; keep_proved:
+// the call's proved mask becomes the one fs_read_exact_proved returns.
 static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
-                            uint32_t bailout, int inclusive, uint64_t n_iterations, void *out, uint32_t n_runs = 0)
+                            uint32_t bailout, int inclusive, uint64_t n_iterations, void *out, uint32_t n_runs = 0,
+                            bool keep_proved = false)
 {
-    const bool samples = n_runs != 0;
+    const bool samples = n_runs != 0, cycle = r->exact_cycle_check;
     const uint32_t W = samples ? n_runs : r->width, H = samples ? n_runs : r->height, npix = samples ? n_runs : W * H;
-    const ExactLayout Y(limbs, W, H, npix);
+    const ExactLayout Y(limbs, W, H, npix, cycle);
     const bool compact = !r->exact_no_compaction;
     char *blk = nullptr;
     hipStream_t s = r->compute;
@@ -145,9 +200,15 @@ static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, 
     A.compact = compact ? 1u : 0u;
     A.dst_count = Y.count(blk);
     A.stats = d_stats;
+    if (cycle) {
+        A.proved = Y.proved(blk, compact ? 2 : 1);
+        fsx::cycle_masks(r->exact_cycle_fp_bits, A.fp_mx, A.fp_my);
+    }
 
     uint64_t slices = 0, after_first = 0;
     hipError_t e = hipMemsetAsync(blk, 0, Y.head, s);
+    if (e == hipSuccess && cycle)
+        e = hipMemsetAsync(A.proved, 0, npix, s);
     if (e == hipSuccess)
         e = hipMemcpyAsync(Y.cx(blk), cx, (size_t)limbs * W * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
@@ -160,8 +221,10 @@ static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, 
                 A.src_xy = (const uint32_t *)src, A.src_n = (const uint64_t *)(src + Y.xy_bytes);
                 A.src_pix = (const uint32_t *)(src + Y.xy_bytes + Y.n_bytes);
                 A.dst_xy = (uint32_t *)dst, A.dst_n = (uint64_t *)(dst + Y.xy_bytes), A.dst_pix = (uint32_t *)(dst + Y.xy_bytes + Y.n_bytes);
+                if (cycle)
+                    A.src_ck = Y.checkpoints(src), A.dst_ck = Y.checkpoints(dst);
                 A.slice = r->exact_slice ? r->exact_slice : exact_default_slice(limbs, A.n_src);
-                return fsk_exact_slice(A, limbs, samples, s);
+                return fsk_exact_slice(A, limbs, samples, cycle, s);
             },
             [&](uint32_t left) {
                 A.first = 0;
@@ -169,12 +232,19 @@ static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, 
                     A.n_src = left;
             },
             slices, after_first);
-    unsigned long long st[2] = {0, 0};
+    unsigned long long st[4] = {0, 0, 0, 0};
     if (e == hipSuccess)
         e = hipMemcpyAsync(st, d_stats, sizeof st, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && cycle && keep_proved) {
+        r->exact_proved.resize(npix);
+        e = hipMemcpyAsync(r->exact_proved.data(), A.proved, npix, hipMemcpyDeviceToHost, s);
+    }
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);
     r->exact_stats[0] += st[0], r->exact_stats[1] += st[1], r->exact_stats[2] += slices, r->exact_stats[3] += after_first;
+    r->exact_cycle_stats[0] += st[2], r->exact_cycle_stats[1] += st[3];
+    if (cycle && keep_proved)
+        r->exact_proved_valid = e == hipSuccess;
     (void)r_free(r, blk);
     return (uint32_t)e;
 }
@@ -190,8 +260,8 @@ uint32_t fs_render_exact(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits
         return (uint32_t)hipErrorInvalidValue;
     if (!exact_axis_in_range(cx, r->width, limbs, frac_bits) || !exact_axis_in_range(cy, r->height, limbs, frac_bits))
         return FS_ERR_UNSUPPORTED;
-    memset(r->exact_stats, 0, sizeof r->exact_stats);
-    return exact_frame(r, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations, r->iters());
+    exact_reset_stats(r);
+    return exact_frame(r, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations, r->iters(), 0, true);
 }
 
 uint32_t fs_exact_stable_mask(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *const cx[3], const uint32_t *const cy[3],
@@ -212,7 +282,7 @@ uint32_t fs_exact_stable_mask(fs_renderer *r, uint32_t frac_bits, uint32_t limbs
     char *blk = nullptr;
     FS_TRY(r_alloc(r, (void **)&blk, frame_bytes + (size_t)W * H, kFrame));
     uint8_t *d_mask = (uint8_t *)(blk + frame_bytes);
-    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    exact_reset_stats(r, r->exact_cycle_check);
     uint32_t rc = 0;
     for (int d = 0; d < 4 && rc == 0; d++) { // c + s, c - s, c + is, c - is
         rc = exact_frame(r, frac_bits, limbs, d < 2 ? cx[1 + d] : cx[0], d < 2 ? cy[0] : cy[d - 1], bailout, 0, n_iterations, blk);
@@ -366,7 +436,7 @@ uint32_t fs_exact_sample_counts(fs_renderer *r, uint32_t frac_bits, uint32_t lim
         return e;
     uint64_t *d_out = nullptr;
     FS_TRY(r_alloc(r, (void **)&d_out, (size_t)n_samples * 8, kFrame));
-    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    exact_reset_stats(r);
     WideJob J{};
     J.frac_bits = frac_bits, J.limbs = limbs, J.cx = cx, J.cy = cy, J.nx = J.ny = J.n = n_samples, J.W = 0;
     J.bailout = bailout, J.inclusive = inclusive, J.cap = n_iterations;
@@ -398,7 +468,7 @@ uint32_t fs_render_exact_wide(fs_renderer *r, uint32_t iter_bytes, uint32_t frac
         return (uint32_t)hipErrorInvalidValue;
     if (!exact_axis_in_range(cx, r->width, limbs, frac_bits) || !exact_axis_in_range(cy, r->height, limbs, frac_bits))
         return FS_ERR_UNSUPPORTED;
-    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    exact_reset_stats(r);
     WideJob J{};
     J.frac_bits = frac_bits, J.limbs = limbs, J.cx = cx, J.cy = cy, J.nx = r->width, J.ny = r->height, J.W = r->width;
     J.n = r->width * r->height;
@@ -453,7 +523,7 @@ uint32_t fs_exact_audit(fs_renderer *r, const void *device_iters, uint32_t frac_
     if (!out || (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8) || n_iterations == ~0ull)
         return (uint32_t)hipErrorInvalidValue;
     memset(out, 0, sizeof *out);
-    memset(r->exact_stats, 0, sizeof r->exact_stats);
+    exact_reset_stats(r);
     if (n_samples == 0)
         return 0;
     const uint32_t runs_per_sample = 1u + 4u * n_levels;
@@ -496,7 +566,8 @@ uint32_t fs_exact_audit(fs_renderer *r, const void *device_iters, uint32_t frac_
         rc = (uint32_t)hipMemcpyAsync((void *)A.ys, ys, (size_t)n_samples * 4, hipMemcpyHostToDevice, s);
     if (rc == 0) {
         if (limbs <= fsx::kMaxLimbs) {
-            rc = exact_frame(r, frac_bits, limbs, cx.data(), cy.data(), bailout, inclusive, n_iterations, (void *)A.counts, n_runs);
+            rc = exact_frame(r, frac_bits, limbs, cx.data(), cy.data(), bailout, inclusive, n_iterations, (void *)A.counts, n_runs,
+                             true);
         } else {
             WideJob J{};
             J.frac_bits = frac_bits, J.limbs = limbs, J.cx = cx.data(), J.cy = cy.data(), J.nx = J.ny = J.n = n_runs, J.W = 0;

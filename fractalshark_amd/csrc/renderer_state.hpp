@@ -185,6 +185,11 @@ struct fs_renderer {
     uint32_t exact_slice = 0;        // fs_set_exact_slice (tests, tools): steps per lane per launch of the exact renderer, 0 = default
     bool exact_no_compaction = false; // ... and its A/B switch: every sample keeps its slot from slice to slice
     uint64_t exact_stats[4] = {};    // fs_read_exact_stats: what the last exact frame did
+    bool exact_cycle_check = false;  // fs_set_exact_cycle_check: the lane-per-sample kernels prove non-escape by a repeat of the state
+    uint32_t exact_cycle_fp_bits = 0; // fs_set_exact_cycle_fingerprint_bits (tests): low bits the fingerprint keeps, 0 = all 64
+    uint64_t exact_cycle_stats[2] = {}; // fs_read_exact_cycle_stats: samples finished by proof, checkpoints read back
+    std::vector<uint8_t> exact_proved; // fs_read_exact_proved: the proved mask of the last fs_render_exact / fs_exact_audit ...
+    bool exact_proved_valid = false; // ... when the last exact call ran with the check on
     uint32_t az_gather_rows = 0;     // fs_set_autozoom_gather_cap (tests): frame rows the FilamentTip gather buffer holds, 0 = default
     FsAzStats az_seed{};             // source of the stream-ordered seed copy in fs_autozoom_pick (must outlive the copy)
     bool inject_input_oom = false;   // fault injection: FSMI355_FAIL_INPUT_ALLOC=1 at fs_create time

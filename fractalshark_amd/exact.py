@@ -10,6 +10,10 @@ min(E - 1, N) like every other path.  The axes come from the view's bounding-box
 audit() asks the library which sample pixels of a frame ANOTHER kernel rendered differ from those counts, and at which stability
 levels the frame is clean (fs_exact_audit: the runs of all samples and ladder positions as one list on the device, the frame read
 next to them, one small record back).
+
+prove_interior=True on render, stable_mask and audit switches the cycle check on for the call (fs_set_exact_cycle_check; DESIGN.md
+6.3 "Cycle check"): a sample whose state repeats exactly is proved never to escape and stops at once instead of running to the cap.
+No count changes; frames with an interior at a shallow or middle depth get cheaper.  The wide path has no such check.
 """
 import numpy as np
 
@@ -44,19 +48,44 @@ def _check(renderer, err, what):
         raise RuntimeError("%s failed: %d (%s)" % (what, err, renderer.ConvertErrorToString(err)))
 
 
-def render(renderer, view, bailout=4, frac_bits=None, iter_bytes=4, inclusive=False):
+class _cycle_check:
+    """The cycle check on for the duration of a call, off again behind it."""
+
+    def __init__(self, renderer, on):
+        self.renderer, self.on = renderer, bool(on)
+
+    def __enter__(self):
+        if self.on:
+            _check(self.renderer, self.renderer.SetExactCycleCheck(True), "fs_set_exact_cycle_check")
+
+    def __exit__(self, *exc):
+        if self.on:
+            self.renderer.SetExactCycleCheck(False)
+
+
+def _proved(renderer, n=None):
+    err, mask = renderer.ExactProved(n)
+    _check(renderer, err, "fs_read_exact_proved")
+    return mask.astype(bool)
+
+
+def render(renderer, view, bailout=4, frac_bits=None, iter_bytes=4, inclusive=False, prove_interior=False):
     """The view's exact frame into the renderer's iteration buffer (InitializeMemory with the view's antialiased size and
     iter_bytes comes first), view.num_iterations the cap.  frac_bits defaults to view.precision_bits + 64.  Has the shape
     autozoom.zoom wants for its `render` argument.  Up to 24 limbs (758 bits) a lane holds a sample (fs_render_exact); beyond, a
-    wave does (fs_render_exact_wide), up to 704 limbs."""
+    wave does (fs_render_exact_wide), up to 704 limbs.
+    prove_interior: the cycle check is on for the call, and the result is bool[H, W], the samples it proved never to escape (they
+    hold the cap, like those that ran to it).  On the wide path the check stays off and the result is None, as without it."""
     F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
     L = limbs_for(F)
     cx, cy = axes(view, F, limbs=L)
     if uses_wide(L):
         _check(renderer, renderer.RenderExactWide(iter_bytes, F, L, cx, cy, bailout, inclusive, view.num_iterations),
                "fs_render_exact_wide")
-    else:
+        return None
+    with _cycle_check(renderer, prove_interior):
         _check(renderer, renderer.RenderExact(iter_bytes, F, L, cx, cy, bailout, inclusive, view.num_iterations), "fs_render_exact")
+    return _proved(renderer).reshape(cy.shape[1], cx.shape[1]) if prove_interior else None
 
 
 def uses_wide(limbs):
@@ -106,10 +135,11 @@ class AuditReport:
     n_offenders, and per level, in the order of `levels`, stable_count (the record's stable[]), stable_differ, stable_capped and
     max_abs_diff; `record` is the _capi.AuditResult itself.  Per sample: values (the exact counts, int64[n]), frame_values
     (int64[n]) and stable (bool[n, len(levels)]).  offenders: the first (at most 16) differing samples in sample order, as dicts
-    {sample, x, y, frame_value, exact_value, stable: [bool per level]}."""
+    {sample, x, y, frame_value, exact_value, stable: [bool per level]}.  With audit(prove_interior=True): n_proved, how many of the
+    samples' own runs (at c) the cycle check finished by proof, and proved (bool[n]), which; 0 and None otherwise."""
 
     def __init__(self, levels, n_samples, stable_count, stable_differ, stable_capped=None, max_abs_diff=None, n_equal=0, n_differ=0,
-                 n_capped=0, offenders=(), values=None, frame_values=None, stable=None, record=None):
+                 n_capped=0, offenders=(), values=None, frame_values=None, stable=None, record=None, n_proved=0, proved=None):
         k = len(levels)
         ints = lambda a: [int(v) for v in (a if a is not None else [0] * k)]
         self.levels, self.n_samples, self.n_levels = tuple(int(lv) for lv in levels), int(n_samples), k
@@ -119,6 +149,7 @@ class AuditReport:
         self.offenders = list(offenders)
         self.n_offenders = len(self.offenders)
         self.values, self.frame_values, self.stable, self.record = values, frame_values, stable, record
+        self.n_proved, self.proved = int(n_proved), proved
 
     def finest_clean_level(self, min_samples=MIN_STABLE_SAMPLES, min_share=MIN_STABLE_SHARE):
         """The finest level (the largest k of s = width / 2^k) at which the frame misses on no stable sample and whose stable set
@@ -134,13 +165,15 @@ class AuditReport:
                 "stable_capped": self.stable_capped, "max_abs_diff": self.max_abs_diff}
 
 
-def audit(renderer, view, xs, ys, levels=(), bailout=256, frac_bits=None, inclusive=False, device_iters=None):
+def audit(renderer, view, xs, ys, levels=(), bailout=256, frac_bits=None, inclusive=False, device_iters=None, prove_interior=False):
     """The frame in the renderer's iteration buffer (or device_iters: another device buffer of its geometry) against the exact
     counts min(E - 1, view.num_iterations) at the samples (xs[i], ys[i]) of the view's antialiased frame, with the stability of
     every sample at the ladder `levels` (at most 8; s = the frame's width / 2^level): an AuditReport.  One call (fs_exact_audit):
     all len(xs) * (1 + 4 len(levels)) runs advance as one list on the device, the frame is read next to them, and only the record
     and three small per-sample arrays come back.  The frame's rule must be min(E - 1, N): the perturbation kernels (bailout 256)
-    and the direct kernels with a CPU twin (bailout 4), not the low-precision direct kernels."""
+    and the direct kernels with a CPU twin (bailout 4), not the low-precision direct kernels.
+    prove_interior: the cycle check is on for the call (up to 24 limbs; beyond, it is ignored); the report is the same but for
+    n_proved and proved, and renderer.ExactProved(len(xs) * (1 + 4 len(levels))) holds the proved mask of all runs."""
     F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
     L = limbs_for(F)
     levels = tuple(int(lv) for lv in levels)
@@ -152,9 +185,12 @@ def audit(renderer, view, xs, ys, levels=(), bailout=256, frac_bits=None, inclus
         for ax, ay in ((cx3[1], cy3[0]), (cx3[2], cy3[0]), (cx3[0], cy3[1]), (cx3[0], cy3[2])):  # c + s, c - s, c + is, c - is
             cx_runs.append(ax[:, xs])
             cy_runs.append(ay[:, ys])
-    err, res, values, frame_values, bits = renderer.ExactAudit(F, L, xs, ys, np.stack(cx_runs), np.stack(cy_runs), bailout, inclusive,
-                                                               view.num_iterations, device_iters=device_iters)
+    proving = bool(prove_interior) and not uses_wide(L) and len(xs) > 0
+    with _cycle_check(renderer, proving):
+        err, res, values, frame_values, bits = renderer.ExactAudit(F, L, xs, ys, np.stack(cx_runs), np.stack(cy_runs), bailout,
+                                                                   inclusive, view.num_iterations, device_iters=device_iters)
     _check(renderer, err, "fs_exact_audit")
+    proved = _proved(renderer, len(xs) * (1 + 4 * len(levels)))[:len(xs)] if proving else None
     k = len(levels)
     stable = ((bits[:, None] >> np.arange(k, dtype=np.uint32)[None, :]) & 1).astype(bool).reshape(len(xs), k)
     offenders = [{"sample": int(o.sample), "x": int(xs[o.sample]), "y": int(ys[o.sample]), "frame_value": int(o.frame_value),
@@ -162,16 +198,18 @@ def audit(renderer, view, xs, ys, levels=(), bailout=256, frac_bits=None, inclus
                  for o in res.offenders[:res.n_offenders]]
     return AuditReport(levels, res.n_samples, res.stable[:k], res.stable_differ[:k], res.stable_capped[:k], res.max_abs_diff[:k],
                        res.n_equal, res.n_differ, res.n_capped, offenders, values.astype(np.int64), frame_values.astype(np.int64),
-                       stable, res)
+                       stable, res, n_proved=0 if proved is None else int(proved.sum()), proved=proved)
 
 
-def stable_mask(renderer, view, level, bailout=4, frac_bits=None):
+def stable_mask(renderer, view, level, bailout=4, frac_bits=None, prove_interior=False):
     """bool[H, W]: the pixels of the exact frame in the iteration buffer (exact.render of the same view, bailout and frac_bits,
-    strict) whose count is the same at c +- s and c +- is, s = the frame's width / 2^level."""
+    strict) whose count is the same at c +- s and c +- is, s = the frame's width / 2^level.  prove_interior: the four shifted
+    frames are rendered with the cycle check on; the mask is the same."""
     F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
     L = limbs_for(F)
     cx3, cy3 = axes(view, F, level=level, limbs=L)
-    err, mask = renderer.ExactStableMask(F, L, cx3, cy3, bailout, view.num_iterations)
+    with _cycle_check(renderer, prove_interior):
+        err, mask = renderer.ExactStableMask(F, L, cx3, cy3, bailout, view.num_iterations)
     _check(renderer, err, "fs_exact_stable_mask")
     return mask.astype(bool)
 

@@ -252,6 +252,29 @@ class GPURenderer:
         self._lib.fs_read_exact_stats(self._h, out)
         return dict(zip(("lane_slots", "lane_steps", "launches", "running_after_first_slice"), (int(v) for v in out)))
 
+    def SetExactCycleCheck(self, enable):
+        """fs_set_exact_cycle_check: the lane-per-sample exact kernels (RenderExact, ExactStableMask, ExactAudit up to 24 limbs)
+        prove non-escape by an exact repeat of the state; off by default.  Changes no pixel."""
+        return self._lib.fs_set_exact_cycle_check(self._h, 1 if enable else 0)
+
+    def ExactProved(self, n=None):
+        """fs_read_exact_proved: (error code, uint8[n]) -- 1 for the samples the last RenderExact (n = W * H, the default, row-major)
+        or the last ExactAudit (n = its runs, run order) finished by proof; FS_ERR_6 when that call ran with the check off."""
+        n = self.GetWidth() * self.GetHeight() if n is None else int(n)
+        out = np.zeros(n, np.uint8)
+        err = self._lib.fs_read_exact_proved(self._h, out.ctypes.data, n)
+        return err, out
+
+    def exact_cycle_stats(self):
+        """fs_read_exact_cycle_stats of the last exact call: (samples finished by proof, checkpoints read back)."""
+        out = (C.c_uint64 * 2)()
+        self._lib.fs_read_exact_cycle_stats(self._h, out)
+        return int(out[0]), int(out[1])
+
+    def SetExactCycleFingerprintBits(self, bits):
+        """Test hook (fs_set_exact_cycle_fingerprint_bits): low bits of the checkpoint's fingerprint, 0 = all 64."""
+        return self._lib.fs_set_exact_cycle_fingerprint_bits(self._h, int(bits))
+
     def _feature_eval(self, entry, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
         from . import features
         din, dout, dreal = features.records(T == T_HDR64)

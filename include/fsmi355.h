@@ -358,6 +358,23 @@ uint32_t fs_exact_audit(fs_renderer *r, const void *device_iters, uint32_t frac_
                         uint32_t bailout, int inclusive, uint64_t n_iterations, fs_audit_result *out, uint64_t *exact_out,
                         uint64_t *frame_out, uint32_t *stable_out);
 
+/* The exact renderer's cycle check: a proof of non-escape by an exact repeat of the state (DESIGN.md 6.3 "Cycle check").  The
+ * recurrence is integer and nothing is rounded, so a sample whose z_n equals, limb for limb, a z_m it held before (m < n) walks a
+ * cycle of states that have all passed the escape test: it escapes at no cap, and it leaves the loop with n_iterations as its value
+ * at once instead of after n_iterations + 1 steps.  No pixel changes.  Every sample keeps one checkpoint, z_1 = c at first and
+ * retaken at every n that is a power of two.
+ * fs_set_exact_cycle_check: enable = 1 switches the check on for fs_render_exact, the four shifted frames of fs_exact_stable_mask
+ * and fs_exact_audit up to 24 limbs (the running samples then carry 2 * limbs more limb planes); 0, the default, off: every call
+ * does exactly what it does without this function.  fs_render_exact_wide, fs_exact_sample_counts and fs_exact_audit beyond 24
+ * limbs ignore the switch.  What the check cannot prove within the cap -- long periods, samples near a component's boundary,
+ * parabolic ones -- runs to the cap as before.
+ * fs_read_exact_proved: out[n] (host) = 1 for the samples the last call finished by proof: of the last fs_render_exact, row-major
+ * over the W x H of fs_init_memory (n = W * H); of the last fs_exact_audit, its runs in run order (n = n_samples * (1 + 4
+ * n_levels), run k of sample i at k * n_samples + i).  fs_exact_stable_mask with the check on leaves the mask of the frame before
+ * it.  FS_ERR_6: the last exact call ran with the check off (or there was none); hipErrorInvalidValue: n is not the mask's size. */
+uint32_t fs_set_exact_cycle_check(fs_renderer *r, int enable);
+uint32_t fs_read_exact_proved(const fs_renderer *r, uint8_t *out, uint64_t n);
+
 /* GPURenderer::ClearMemory<IterType> (GPU_Render.cu:212-225). */
 uint32_t fs_clear(fs_renderer *r);
 

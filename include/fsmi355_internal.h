@@ -119,6 +119,15 @@ uint32_t fs_read_exact_stats(const fs_renderer *r, uint64_t out[4]);
  * count is blind to wrong low limbs over a short run; the state shows a dropped carry at once.  Leaves fs_read_exact_stats alone. */
 uint32_t fs_exact_wide_state(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
                              uint32_t n_samples, uint32_t steps, uint32_t *out_x, uint32_t *out_y);
+/* The cycle check of the exact renderer (fs_set_exact_cycle_check of fsmi355.h).
+ * fs_read_exact_cycle_stats: of the last exact call, summed over its frames: out[0] = samples finished by proof, [1] = times a lane
+ * read its checkpoint back for the full compare (fs_read_exact_stats reports what it reports without the check).
+ * fs_set_exact_cycle_fingerprint_bits (test hook): a lane reads its checkpoint back only when a fingerprint matches: the low limbs
+ * of x and y, 64 bits, so that the full compare runs next to never unless its answer is "equal".  bits = 1 .. 63 keeps that many low
+ * bits of the 64-bit number (y[0] : x[0]) -- up to 32, bits of x[0] only -- and makes the compare run, and answer "not equal", on
+ * one step in 2^bits; 0 = the default, all 64.  Changes no result. */
+uint32_t fs_read_exact_cycle_stats(const fs_renderer *r, uint64_t out[2]);
+uint32_t fs_set_exact_cycle_fingerprint_bits(fs_renderer *r, uint32_t bits);
 uint32_t fs_enable_step_count(fs_renderer *r, int enable);
 uint32_t fs_read_step_count(fs_renderer *r, uint64_t counts[8]);
 /* The whole statistics buffer (measurement builds append per-wave trace records behind the 8 counters: library built

@@ -10,11 +10,14 @@ One JSON line per audit: the record per level (stable, stable_differ, stable_cap
 first offenders, and the time of the audit call (a host clock around exact.audit: the axes on the host, all runs, the
 classification, the read-back of the record).  --against-sample-counts also runs exact.sample_counts -- one synchronous call per
 run position, a wave per sample -- on the same samples and levels in the same process, checks that both agree and prints the
-factor between the two times.  One run each; the first call of either path in a process is preceded by a two-sample call that
+factor between the two times.  --prove-interior audits with the cycle check on (exact.audit(prove_interior=True), DESIGN.md 6.3
+"Cycle check"; up to 24 limbs): the record must be the same, and the line also carries n_proved (of the samples' own runs),
+runs_proved (of all runs) and the checkpoints read back.  One run each; the first call of either path in a process is preceded by a two-sample call that
 loads its kernels.
 
   python tools/audit_frame.py shallow_1e-28:exact --against-sample-counts
   python tools/audit_frame.py c3_hdr32 c3_hdr64 --levels 17,30 [--parity cpu|gpustage] [--lattice 24x12]
+  python tools/audit_frame.py view0_70x37:exact --prove-interior
 """
 import argparse
 import json
@@ -39,6 +42,7 @@ ap.add_argument("--levels", default=None, help="comma-separated ladder levels (a
 ap.add_argument("--lattice", default=None, help="COLSxROWS over the frame; default: the fixture's samples of the case")
 ap.add_argument("--parity", choices=("cpu", "gpustage"), default="cpu", help="stage-test direction of the LAv2 kernels")
 ap.add_argument("--against-sample-counts", action="store_true")
+ap.add_argument("--prove-interior", action="store_true", help="audit with the exact renderer's cycle check on")
 args = ap.parse_args()
 
 
@@ -74,7 +78,7 @@ for wl in args.workloads:
     render_s = render(r, c, v, kernel, F)
     exact.audit(r, v, xs[:2], ys[:2], levels=(), bailout=256, frac_bits=F)  # (loads the kernels)
     t0 = time.perf_counter()
-    rep = exact.audit(r, v, xs, ys, levels=levels, bailout=256, frac_bits=F)
+    rep = exact.audit(r, v, xs, ys, levels=levels, bailout=256, frac_bits=F, prove_interior=args.prove_interior)
     audit_s = time.perf_counter() - t0
     st = r.exact_stats()
     line = dict(what="audit", workload=wl, case=name, kernel=kernel, parity=args.parity if kernel != "exact" else None,
@@ -82,6 +86,9 @@ for wl in args.workloads:
                 runs=len(xs) * (1 + 4 * len(levels)), **rep.as_dict(), finest_clean_level=rep.finest_clean_level(),
                 offenders=rep.offenders[:4], render_seconds=round(render_s, 3), audit_seconds=round(audit_s, 4),
                 launches=st["launches"], lane_steps=st["lane_steps"], lane_slots=st["lane_slots"])
+    if args.prove_interior:
+        runs_proved, compares = r.exact_cycle_stats()
+        line.update(prove_interior=rep.proved is not None, n_proved=rep.n_proved, runs_proved=runs_proved, checkpoint_reads=compares)
     if args.against_sample_counts:
         exact.sample_counts(r, v, xs[:2], ys[:2], bailout=256, frac_bits=F)
         t0 = time.perf_counter()

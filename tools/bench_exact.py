@@ -19,10 +19,17 @@
   view11    (--view11) View 11's 200 fixture samples at the fixture's cap, (--view14) View 14's six at cap 1 800 000: equality with
             the fixture's counts and the wall time next to the entry's generator_seconds.  One run each.
 
+  cycle     (--cycle) the cycle check (fs_set_exact_cycle_check; DESIGN.md 6.3 "Cycle check"): (a) what it costs where it proves
+            nothing -- the two paces of `pace`, with the check off and on in the same run, on frames whose every sample is c = 1/4 (a
+            parabolic point: never escapes, never repeats; the tool asserts that no sample was proved), per limb count of
+            --cycle-limbs, as the on / off ratio of the time per step; (b) what it saves: View 0 at 1024 x 768 (R 4) with the check
+            off and on at caps 8 192 and 100 000: call time, launches, steps and proved samples
+
 Times are host clocks around synchronous calls.  One JSON line per measurement.
 
   python tools/bench_exact.py [--pace] [--frames] [--view5] [--limbs 2,4,7,8,11,12,16,20,23,24]
                               [--wide] [--wide-limbs 25,64,80,128,160,320,683,704] [--view11] [--view14]
+                              [--cycle] [--cycle-limbs 2,4,8,12,16,24]
 """
 import argparse
 import json
@@ -47,8 +54,10 @@ ap.add_argument("--wide", action="store_true")
 ap.add_argument("--wide-limbs", default="25,64,80,128,160,320,683,704")
 ap.add_argument("--view11", action="store_true")
 ap.add_argument("--view14", action="store_true")
+ap.add_argument("--cycle", action="store_true")
+ap.add_argument("--cycle-limbs", default="2,4,8,12,16,24")
 args = ap.parse_args()
-if not (args.pace or args.frames or args.view5 or args.wide or args.view11 or args.view14):
+if not (args.pace or args.frames or args.view5 or args.wide or args.view11 or args.view14 or args.cycle):
     args.pace = args.frames = True
 
 
@@ -65,6 +74,13 @@ def inside_axes(L, w, h, F):
     return cx, cy
 
 
+def quarter_axes(L, w, h, F):
+    """Axes of a w x h frame whose every sample is c = 1/4: it creeps towards 1/2 for ever, so it neither escapes nor repeats."""
+    limbs = lambda v: [(v >> (32 * l)) & 0xFFFFFFFF for l in range(L)]
+    cx = np.array([limbs(1 << (F - 2))] * w, np.uint32).T.copy()
+    return cx, np.zeros((L, h), np.uint32)
+
+
 def timed_render(r, F, L, cx, cy, R, n):
     t0 = time.perf_counter()
     err = r.RenderExact(4, F, L, cx, cy, R, False, n)
@@ -75,29 +91,72 @@ def timed_render(r, F, L, cx, cy, R, n):
 
 r = GPURenderer(0)
 
+def pace(L, F, make_axes):
+    """(microseconds per step of a wave by itself, lane steps per second of the full chip) on frames of make_axes' samples."""
+    # eight waves, one per workgroup
+    assert r.InitializeMemory(64, 8, 1, None, 0, 0, 0, False) == 0
+    cx, cy = make_axes(L, 64, 8, F)
+    n1, n2 = 4096, 4096 * 9
+    timed_render(r, F, L, cx, cy, 4, n1)
+    t1 = min(timed_render(r, F, L, cx, cy, 4, n1) for _ in range(3))
+    t2 = min(timed_render(r, F, L, cx, cy, 4, n2) for _ in range(3))
+    us_step = (t2 - t1) / (n2 - n1) * 1e6
+    # every SIMD full
+    assert r.InitializeMemory(1024, 1024, 1, None, 0, 0, 0, False) == 0
+    cx, cy = make_axes(L, 1024, 1024, F)
+    m1, m2 = 64, 64 + (512 if L <= 12 else 128)
+    timed_render(r, F, L, cx, cy, 4, m1)
+    u1 = min(timed_render(r, F, L, cx, cy, 4, m1) for _ in range(2))
+    u2 = min(timed_render(r, F, L, cx, cy, 4, m2) for _ in range(2))
+    return us_step, (m2 - m1) * 1024 * 1024 / (u2 - u1)
+
+
 if args.pace:
     r.SetExactSlice(4096)  # (the default shortens the slices of a frame that fills the chip)
     for L in [int(s) for s in args.limbs.split(",")]:
         F = 32 * L - 10
-        # eight waves, one per workgroup
-        assert r.InitializeMemory(64, 8, 1, None, 0, 0, 0, False) == 0
-        cx, cy = inside_axes(L, 64, 8, F)
-        n1, n2 = 4096, 4096 * 9
-        timed_render(r, F, L, cx, cy, 4, n1)
-        t1 = min(timed_render(r, F, L, cx, cy, 4, n1) for _ in range(3))
-        t2 = min(timed_render(r, F, L, cx, cy, 4, n2) for _ in range(3))
-        us_step = (t2 - t1) / (n2 - n1) * 1e6
-        # every SIMD full
-        assert r.InitializeMemory(1024, 1024, 1, None, 0, 0, 0, False) == 0
-        cx, cy = inside_axes(L, 1024, 1024, F)
-        m1, m2 = 64, 64 + (512 if L <= 12 else 128)
-        timed_render(r, F, L, cx, cy, 4, m1)
-        u1 = min(timed_render(r, F, L, cx, cy, 4, m1) for _ in range(2))
-        u2 = min(timed_render(r, F, L, cx, cy, 4, m2) for _ in range(2))
-        lane_steps = (m2 - m1) * 1024 * 1024 / (u2 - u1)
+        us_step, lane_steps = pace(L, F, inside_axes)
         say(what="pace", limbs=L, frac_bits=F, wave_us_per_step=round(us_step, 4), slice_of_4096_ms=round(us_step * 4096 / 1000, 2),
             chip_lane_steps_per_s=round(lane_steps), chip_gmad_per_s=round(lane_steps * (2 * L * L + L) / 1e9, 1))
 
+
+if args.cycle:
+    r.SetExactSlice(4096)
+    for L in [int(s) for s in args.cycle_limbs.split(",")]:
+        F = 32 * L - 10
+        got = {}
+        for on in (False, True):
+            assert r.SetExactCycleCheck(on) == 0
+            got[on] = pace(L, F, quarter_axes)
+            assert r.exact_cycle_stats()[0] == 0 and r.exact_stats()["lane_steps"] > 0  # nothing proved: the two paces compare
+        r.SetExactCycleCheck(False)
+        say(what="cycle pace", limbs=L, frac_bits=F, wave_us_per_step_off=round(got[False][0], 4),
+            wave_us_per_step_on=round(got[True][0], 4), wave_on_over_off=round(got[True][0] / got[False][0], 3),
+            chip_lane_steps_per_s_off=round(got[False][1]), chip_lane_steps_per_s_on=round(got[True][1]),
+            chip_on_over_off=round(got[False][1] / got[True][1], 3))
+    r.SetExactSlice(0)
+    c = _truth.Case("view0_1024x768")
+    v, F = c.view(inputs), c.raw["frac_bits"]
+    L = exact.limbs_for(F)
+    cx, cy = exact.axes(v, F, limbs=L)
+    assert r.InitializeMemory(c.w, c.h, 1, None, 0, 0, 0, False) == 0
+    for cap in (8192, 100000):
+        row, frames = {}, {}
+        for on in (False, True):
+            assert r.SetExactCycleCheck(on) == 0
+            timed_render(r, F, L, cx, cy, 4, 64)  # (memory and code warm)
+            dt = timed_render(r, F, L, cx, cy, 4, cap)
+            st = r.exact_stats()
+            row["on" if on else "off"] = dict(seconds=round(dt, 4), launches=st["launches"], lane_steps=st["lane_steps"],
+                                              lane_slots=st["lane_slots"], proved=r.exact_cycle_stats()[0],
+                                              checkpoint_reads=r.exact_cycle_stats()[1])
+            frames[on] = r.new_iter_buffer()
+            assert r.RenderCurrent(cap, frames[on]) == 0 and r.SyncComputeStream() == 0
+        r.SetExactCycleCheck(False)
+        assert frames[True].tobytes() == frames[False].tobytes()
+        say(what="cycle frame", name="view0_1024x768", bailout=4, frac_bits=F, limbs=L, cap=cap,
+            at_the_cap=int((frames[True][:c.h, :c.w] == cap).sum()), **row,
+            time_off_over_on=round(row["off"]["seconds"] / row["on"]["seconds"], 2))
 
 r.SetExactSlice(0)
 
