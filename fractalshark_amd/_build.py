@@ -1,7 +1,7 @@
 """Build recipes for the native libraries (in-tree, so the .so files travel to the GPU box).
 
   csrc/libfsmi355.so   hipcc --offload-arch=gfx950: HIP kernels + the C ABI of include/fsmi355.h  (the product)
-  host/libfsinputs.so  g++ + GMP: host-side input builders of include/fs_inputs.h (view / orbit / LA / BLA)
+  host/libfsinputs.so  g++ + GMP: host-side input builders of include/fs_inputs.h (view / orbit / LA / BLA), every host/*.cpp
 
 `-ffp-contract=off` is part of the numerical contract (see csrc/hdr_math.hpp): the parity target is the
 reference's CPU build, which has no FMA.
@@ -102,25 +102,25 @@ def _unit_digest(src, hdr_digest, extra=()):
     return _digest([src], [hdr_digest, *_unit_flags(src), *extra])
 
 
-def _compile(hipcc, src, obj, flags):
+def _hip_lang(src):
     # csrc/*.cpp (renderer*.cpp, group.cpp) are host-only C++ that include HIP runtime headers: compiled by hipcc as HIP so
     # that <hip/hip_runtime.h> types (float4, hipStream_t) match the kernels' launchers
-    lang = [] if src.endswith(".hip") else ["-x", "hip"]
-    _run([hipcc, *flags, *_unit_flags(src), "-c", *lang, src, "-o", obj])
+    return [] if src.endswith(".hip") else ["-x", "hip"]
 
 
 def _hipcc():
     return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
-def _compile_all(jobs, force=False):
-    """jobs: (src, obj, flags, digest) -- each object is compiled unless its stamp already matches its digest."""
-    hipcc = _hipcc()
+def _compile_all(jobs, force=False, cc=None, lang=_hip_lang):
+    """jobs: (src, obj, flags, digest) -- each object is compiled (by cc, default hipcc; lang(src) = its language options) unless
+    its stamp already matches its digest."""
+    cc = cc or _hipcc()
 
     def one(job):
         src, obj, flags, d = job
         if force or not _stamp_ok(obj, d):
-            _compile(hipcc, src, obj, flags)
+            _run([cc, *flags, *_unit_flags(src), "-c", *lang(src), src, "-o", obj])
             _write_stamp(obj, d)
         return obj
 
@@ -134,13 +134,22 @@ def _link(lib, objs):
     _run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs, "-ldl", "-lpthread"])
 
 
+def _inputs_units():
+    """Translation units of libfsinputs.so: every host/*.cpp (they share host/inputs_state.hpp)."""
+    return sorted(glob.glob(os.path.join(HOST, "*.cpp")))
+
+
+def _inputs_headers():
+    return sorted(glob.glob(os.path.join(HOST, "*.hpp"))) + [
+        os.path.join(CSRC, "hdr_math.hpp"), os.path.join(CSRC, "la_math.hpp"), os.path.join(CSRC, "df32_math.hpp"),
+        os.path.join(CSRC, "bla_math.hpp"), os.path.join(ROOT, "include", "fs_inputs.h"), os.path.join(ROOT, "include", "fs_layout.h")]
+
+
 def _inputs_sources():
-    return [os.path.join(HOST, "refinputs.cpp"), os.path.join(CSRC, "hdr_math.hpp"), os.path.join(CSRC, "la_math.hpp"),
-            os.path.join(CSRC, "df32_math.hpp"), os.path.join(CSRC, "bla_math.hpp"),
-            os.path.join(ROOT, "include", "fs_inputs.h"), os.path.join(ROOT, "include", "fs_layout.h")]
+    return _inputs_units() + _inputs_headers()
 
 
-_INPUTS_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
+_INPUTS_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 
 
 def _render_digest(units, headers, flags):
@@ -200,8 +209,14 @@ def build_inputs(force=False):
     digest = _digest(srcs, _INPUTS_FLAGS)
     if not force and _stamp_ok(LIB_INPUTS, digest):
         return LIB_INPUTS
-    _run(["g++", *_INPUTS_FLAGS, "-I" + os.path.join(GMP_PREFIX, "include"), "-o", LIB_INPUTS,
-          os.path.join(HOST, "refinputs.cpp"), "-L" + os.path.join(GMP_PREFIX, "lib"), "-lgmp",
+    obj_dir = os.path.join(HOST, "build")
+    os.makedirs(obj_dir, exist_ok=True)
+    flags = [*_INPUTS_FLAGS, "-I" + os.path.join(GMP_PREFIX, "include")]
+    hdr_digest = _digest(_inputs_headers(), flags)
+    jobs = [(src, os.path.join(obj_dir, os.path.basename(src) + ".o"), flags, _unit_digest(src, hdr_digest))
+            for src in _inputs_units()]
+    objs = _compile_all(jobs, force, cc="g++", lang=lambda src: [])
+    _run(["g++", "-shared", "-fPIC", "-o", LIB_INPUTS, *objs, "-L" + os.path.join(GMP_PREFIX, "lib"), "-lgmp",
           "-Wl,-rpath," + os.path.join(GMP_PREFIX, "lib")])
     _write_stamp(LIB_INPUTS, digest)
     return LIB_INPUTS

@@ -1,5 +1,5 @@
 // bla_math.hpp -- bilinear-approximation (BLA) record arithmetic, shared by the device table builder
-// (kernels_tables.hip), the host builder (host/refinputs.cpp) and the known-answer harness (tests/kat): one
+// (kernels_tables.hip), the host builder (host/bla_table.cpp) and the known-answer harness (tests/kat): one
 // definition, compiled by g++ and by hipcc for gfx950.  Follows the reference's HpSharkFloatLib/BLA.cuh (record
 // operations) and FractalSharkLib/BLAS.cpp (how records are made and merged), file:line per function; -ffp-contract=off
 // like everything that must agree with the CPU functions.  F = float | double: the records hold HDRFloat<F> values.

@@ -11,7 +11,7 @@
 // reference's non-fast-math build.
 //
 // There is no CPU twin of this type in the reference (CudaDblflt arithmetic only exists under __CUDACC__); the
-// host-side converters (double -> head/tail) live in fractalshark_amd/host/refinputs.cpp.
+// host-side converters (double -> head/tail) live in fractalshark_amd/host/convert_2x32.cpp.
 #pragma once
 
 #include "hdr_math.hpp"

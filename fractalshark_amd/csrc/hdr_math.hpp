@@ -399,8 +399,12 @@ template <class F> FS_HD hcplx<F> hc_reduced(hcplx<F> a)
     return a;
 }
 
-// HDRFloatComplex.h:544-548 norm_squared.
-template <class F> FS_HD hreal<F> hc_norm2(hcplx<F> a) { return hreal<F>{a.re * a.re + a.im * a.im, a.e << 1}; }
+// HDRFloatComplex.h:544-548 norm_squared.  (The shift is made on the unsigned value: the same instruction, and defined for the
+// negative exponents that C++17 leaves undefined under a signed `<<`.)
+template <class F> FS_HD hreal<F> hc_norm2(hcplx<F> a)
+{
+    return hreal<F>{a.re * a.re + a.im * a.im, (int32_t)((uint32_t)a.e << 1)};
+}
 
 // HDRFloatComplex.h:691-695 chebychevNorm: both parts share the exponent, so the larger |mantissa| wins
 // (ties and the `> 0 ? a : b` orientation pick the imaginary part, which has the same value).

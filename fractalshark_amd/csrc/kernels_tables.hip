@@ -3,7 +3,7 @@
 // Replaces the host-side BLAS<IterType,T>::Init (FractalSharkLib/BLAS.cpp:212-255), which the reference re-runs on the
 // CPU for every BLA render (Fractal.cpp:2739-2740) and then copies to the GPU.  Here the table is built in HBM straight
 // from the uploaded orbit and never crosses PCIe.  Results are bit-identical to the host builder
-// (fractalshark_amd/host/refinputs.cpp BlaBuilder, itself pinned through the golden CRCs of the Cpu*PerturbedBLAHDR
+// (fractalshark_amd/host/bla_table.cpp BlaBuilder, itself pinned through the golden CRCs of the Cpu*PerturbedBLAHDR
 // algorithms): same operations in the same order, -ffp-contract=off, correctly rounded sqrt and divide.
 //
 //   first materialised level (m_FirstLevel = 2, BLAS.h:22): element m = CreateLStep(2, m) (BLAS.cpp:49-72) = the merge

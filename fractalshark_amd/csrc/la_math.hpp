@@ -1,4 +1,4 @@
-// la_math.hpp -- the arithmetic of one LAv2 table record, shared by the host input builder (host/refinputs.cpp, the
+// la_math.hpp -- the arithmetic of one LAv2 table record, shared by the host input builder (host/la_table.cpp, the
 // golden-pinned one) and the device builder (csrc/kernels_la.hip, fs_build_la): LAInfoDeep construction, Step, Composite,
 // DetectPeriod (LAInfoDeep.h:108-391), CreateAT (:456-506), ATInfo::Usable (ATInfo.h:101-116), LAParameters defaults
 // (LAParameters.h:66-75).  ONE source for both, so that a record built on the device is the record the host builder

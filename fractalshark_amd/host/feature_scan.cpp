@@ -1,0 +1,400 @@
+// feature_scan.cpp -- Feature Finder scan (fsh_feature_*).
+#include "inputs_state.hpp"
+
+// FeatureFinderOrchestrator's PT / PTScan grid (FeatureFinderOrchestrator.cpp:485-559) and FeatureFinder::FindPeriodicPoint_Common
+// up to SetFound (FeatureFinder.cpp:2443-2697), restated as a batched state machine: every candidate's evaluations are asked for
+// together (fsh_feature_next_batch), made elsewhere (fs_feature_eval or the CPU checker), and handed back (fsh_feature_consume);
+// the Newton updates stay here, in mpf, as the reference keeps them.  FeatureFinder::Params defaults (FeatureFinder.h:58-63):
+// MaxNewtonIters 32, RelStepTol 2^-40, Eps2Accept = T{} (off).  The Direct / DirectScan modes (fsh_feature_begin_direct*) are the same
+// machine without an orbit: FindPeriodicPoint_Common takes nothing from it, only PTEvaluator does (dc), so their records carry dc = 0.
+namespace {
+
+// HighPrecision{HDRFloat<F>} (HDRFloat.h:396-411): exact, at 64 bits.
+template <class F> Mp mp_from_hr(hreal<F> v)
+{
+    Mp r(64, 0);
+    mpf_set_d(r.v, (double)v.m);
+    if (v.e >= 0)
+        mpf_mul_2exp(r.v, r.v, (mp_bitcnt_t)v.e);
+    else
+        mpf_div_2exp(r.v, r.v, (mp_bitcnt_t)(-(int64_t)v.e));
+    return r;
+}
+
+template <class F> hcplx<F> ct_from_mp(const Mp &x, const Mp &y)
+{
+    return hc_reduced(hc_from_hr(hr_from_mpf<F>(x.v), hr_from_mpf<F>(y.v)));
+}
+
+// FeatureFinder::Div (FeatureFinder.cpp:1550-1574), in HDRFloat<double>.
+template <class F> hcplx<F> feat_div(hcplx<F> a, hcplx<F> b)
+{
+    using H = hreal<double>;
+    const H br{(double)b.re, b.e}, bi{(double)b.im, b.e};
+    const H denom = hr_reduced(hr_add(hr_mul(br, br), hr_mul(bi, bi)));
+    if (hr_cmp_pos(denom, hr_zero<double>()) <= 0)
+        return hc_zero<F>();
+    const H ar{(double)a.re, a.e}, ai{(double)a.im, a.e};
+    const H rr = hr_reduced(hr_div(hr_add(hr_mul(ar, br), hr_mul(ai, bi)), denom));
+    const H ii = hr_reduced(hr_div(hr_sub(hr_mul(ai, br), hr_mul(ar, bi)), denom));
+    return hc_from_hr(hreal<F>{(F)rr.m, rr.e}, hreal<F>{(F)ii.m, ii.e});
+}
+
+template <class F> hreal<F> ld_real(const void *p)
+{
+    if constexpr (sizeof(F) == 4) {
+        const fs_real_hdr32 *r = (const fs_real_hdr32 *)p;
+        return hreal<F>{r->m, r->e};
+    } else {
+        const fs_real_hdr64 *r = (const fs_real_hdr64 *)p;
+        return hreal<F>{r->m, r->e};
+    }
+}
+
+template <class F> std::vector<FeatCand<F>> &cands(fsh_feature &f);
+template <> std::vector<FeatCand<float>> &cands<float>(fsh_feature &f) { return f.c32; }
+template <> std::vector<FeatCand<double>> &cands<double>(fsh_feature &f) { return f.c64; }
+
+// PointZoomBBConverter::X/YFromScreenToCalc (PointZoomBBConverter.cpp:339-354), antialiasing 1
+struct FeatScreen {
+    uint64_t prec;
+    Mp wX, wY, OriginX, OriginY, hwaa, hhaa;
+    explicit FeatScreen(const fsh_view &v)
+        : prec(v.prec_bits), wX(v.maxX - v.minX), wY(v.maxY - v.minY), OriginX(v.prec_bits, 0), OriginY(v.prec_bits, 0),
+          hwaa(v.prec_bits, 0), hhaa(v.prec_bits, 0)
+    {
+        const Mp aa = Mp::from_ui(1), highWidth = Mp::from_ui(v.width), highHeight = Mp::from_ui(v.height);
+        Mp negMinX(v.minX.prec(), 0);
+        mpf_neg(negMinX.v, v.minX.v);
+        mpf_mul(hwaa.v, highWidth.v, aa.v);
+        mpf_div(OriginX.v, hwaa.v, wX.v);
+        mpf_mul(OriginX.v, OriginX.v, negMinX.v);
+        mpf_mul(hhaa.v, highHeight.v, aa.v);
+        mpf_div(OriginY.v, hhaa.v, wY.v);
+        mpf_mul(OriginY.v, OriginY.v, v.maxY.v);
+    }
+    Mp X(uint64_t x) const
+    {
+        Mp px = Mp::from_ui(x), cx(prec, 0);
+        mpf_sub(cx.v, px.v, OriginX.v);
+        mpf_mul(cx.v, cx.v, wX.v);
+        mpf_div(cx.v, cx.v, hwaa.v);
+        return cx;
+    }
+    Mp Y(uint64_t y) const
+    {
+        Mp py = Mp::from_ui(y), cy(prec, 0);
+        mpf_sub(cy.v, py.v, OriginY.v);
+        mpf_neg(cy.v, cy.v);
+        mpf_mul(cy.v, cy.v, wY.v);
+        mpf_div(cy.v, cy.v, hhaa.v);
+        return cy;
+    }
+};
+
+// The scan's screen points (FeatureFinderOrchestrator.cpp:541-548)
+inline uint64_t feat_grid_px(uint64_t extent, uint32_t g, uint32_t n) { return (extent * (2 * (uint64_t)g + 1)) / (2 * (uint64_t)n); }
+
+// `at`: the one screen point of the non-scan mode instead of the nx x ny grid
+template <class F>
+void feature_begin(fsh_feature &f, const fsh_view &v, uint32_t nx, uint32_t ny, const uint64_t *at = nullptr)
+{
+    mpf_set_default_prec(v.prec_bits);
+    // radiusY = T{MaxY - MinY} / T{2.0f}; HighPrecision radius{radiusY}; radius /= HighPrecision{12}
+    const hreal<F> radiusY = hr_div(hr_from_mpf<F>((v.maxY - v.minY).v), hr_from_number<F>(F(2)));
+    f.radius_hp = mp_from_hr(radiusY);
+    {
+        Mp twelve = Mp::from_ui(12);
+        mpf_div(f.radius_hp.v, f.radius_hp.v, twelve.v);
+    }
+    const FeatScreen scr(v);
+    auto &cs = cands<F>(f);
+    auto add = [&](uint64_t x, uint64_t y, uint32_t grid) {
+        FeatCand<F> c;
+        c.cx = scr.X(x);
+        c.cy = scr.Y(y);
+        c.grid = grid;
+        cs.push_back(c);
+    };
+    if (at) {
+        add(at[0], at[1], 0);
+        return;
+    }
+    for (uint32_t gy = 0; gy < ny; ++gy)
+        for (uint32_t gx = 0; gx < nx; ++gx)
+            add(feat_grid_px(v.width, gx, nx), feat_grid_px(v.height, gy, ny), gy * nx + gx);
+}
+
+// FindPeriodicPoint_Common's search radius: R = HdrAbs(T{radius}), SqrRadius = R * R reduced; what PTEvaluator::Eval passes on
+// is HdrSqrt(SqrRadius).
+template <class F> hreal<F> feature_eval_radius(const fsh_feature &f)
+{
+    hreal<F> R = hr_abs(hr_from_mpf<F>(f.radius_hp.v));
+    const hreal<F> sqr = hr_reduced(hr_mul(R, R));
+    return hr_sqrt(sqr);
+}
+
+template <class F, class In> uint64_t feature_next(fsh_feature &f, In *in, uint64_t cap, int *mode)
+{
+    auto &cs = cands<F>(f);
+    f.batch.clear();
+    // one mode per batch: while any candidate still waits for its period search, a batch holds only those
+    bool any_find = false;
+    for (const FeatCand<F> &c : cs)
+        any_find |= c.stage == kFind;
+    for (uint32_t k = 0; k < cs.size(); ++k)
+        if (cs[k].stage < kFound && (cs[k].stage == kFind) == any_find && f.batch.size() < cap) {
+            FeatCand<F> &c = cs[k];
+            const hcplx<F> cc = ct_from_mp<F>(c.cx, c.cy);
+            In r{};
+            if (!f.direct) {
+                const hcplx<F> dc = ct_from_mp<F>(c.cx - f.hiX, c.cy - f.hiY);
+                r.dc.re = dc.re, r.dc.im = dc.im, r.dc.e = dc.e;
+            }
+            r.c.re = cc.re, r.c.im = cc.im, r.c.e = cc.e;
+            r.period = c.stage == kFind ? 0 : c.period;
+            in[f.batch.size()] = r;
+            f.batch.push_back(k);
+        }
+    *mode = any_find ? 0 : 1;
+    return f.batch.size();
+}
+
+// The Newton step of FindPeriodicPoint_Common: c <- c - diff / dzdc, in mpf only.  False: dzdc is degenerate (rejected).
+template <class F> bool newton_step(FeatCand<F> &c, hcplx<F> diff, hcplx<F> dzdc, hcplx<F> *step_out)
+{
+    if (hr_cmp_pos(hr_reduced(hc_norm2(dzdc)), hr_zero<F>()) <= 0)
+        return false;
+    const hcplx<F> step = hc_reduced(feat_div(diff, dzdc));
+    c.cx = c.cx - mp_from_hr(hc_re(step));
+    c.cy = c.cy - mp_from_hr(hc_im(step));
+    if (step_out)
+        *step_out = step;
+    return true;
+}
+
+template <class F, class Out> void feature_consume(fsh_feature &f, const Out *out, uint64_t n)
+{
+    auto &cs = cands<F>(f);
+    const hreal<F> tol = hr_reduced(hr_from_number<F>(F(0x1p-40))); // diffTol and RelStepTol alike
+    const hreal<F> tol2 = hr_reduced(hr_mul(tol, tol));
+    for (uint64_t j = 0; j < n && j < f.batch.size(); ++j) {
+        FeatCand<F> &c = cs[f.batch[j]];
+        const Out &o = out[j];
+        if (o.status == 0) { // rejected: findPeriod / evalAtPeriod / final eval failed
+            c.stage = kRejected;
+            continue;
+        }
+        const hcplx<F> diff{o.diff.re, o.diff.im, o.diff.e}, dzdc{o.dzdc.re, o.dzdc.im, o.dzdc.e};
+        const hcplx<F> zcoeff{o.zcoeff.re, o.zcoeff.im, o.zcoeff.e};
+        switch (c.stage) {
+        case kFind:
+            c.period = o.period;
+            c.stage = newton_step<F>(c, diff, dzdc, nullptr) ? kNewton : kRejected;
+            break;
+        case kNewton: {
+            const hcplx<F> cT = ct_from_mp<F>(c.cx, c.cy);
+            const hreal<F> diff2 = hr_reduced(hc_norm2(diff));
+            if (hr_cmp_pos(diff2, hr_reduced(hr_mul(hr_reduced(hc_norm2(cT)), tol2))) <= 0) {
+                c.stage = kFinal1;
+                break;
+            }
+            hcplx<F> step;
+            if (!newton_step<F>(c, diff, dzdc, &step)) {
+                c.stage = kRejected;
+                break;
+            }
+            const hcplx<F> cNew = ct_from_mp<F>(c.cx, c.cy);
+            const hreal<F> step2 = hr_reduced(hc_norm2(step));
+            if (hr_cmp_pos(step2, hr_reduced(hr_mul(hr_reduced(hc_norm2(cNew)), tol2))) <= 0 || ++c.it >= 32)
+                c.stage = kFinal1;
+            break;
+        }
+        case kFinal1:
+            c.stage = newton_step<F>(c, diff, dzdc, nullptr) ? kFinal2 : kRejected;
+            break;
+        case kFinal2: {
+            // the candidate store's w test (:2636-2662), then ComputeIntrinsicRadius_HP (:1713-1746)
+            using H = hreal<double>;
+            const H zr{(double)zcoeff.re, zcoeff.e}, zi{(double)zcoeff.im, zcoeff.e};
+            const H dr{(double)dzdc.re, dzdc.e}, di{(double)dzdc.im, dzdc.e};
+            const H wr = hr_reduced(hr_sub(hr_mul(zr, dr), hr_mul(zi, di)));
+            const H wi = hr_reduced(hr_add(hr_mul(zr, di), hr_mul(zi, dr)));
+            const H w2 = hr_reduced(hr_add(hr_mul(wr, wr), hr_mul(wi, wi)));
+            if (!(hr_cmp_pos(w2, hr_zero<double>()) > 0)) {
+                c.stage = kRejected;
+                break;
+            }
+            const H absW = hr_reduced(hr_sqrt(w2));
+            const H radius = hr_reduced(hr_div(hr_from_number<double>(4.0), absW));
+            c.radius = mp_from_hr(radius);
+            const hreal<F> r2{o.residual2.m, o.residual2.e};
+            c.residual2 = H{(double)r2.m, r2.e};
+            c.stage = kFound;
+            break;
+        }
+        default:
+            break;
+        }
+    }
+}
+
+template <class F> const FeatCand<F> *found_at(fsh_feature &f, uint64_t k)
+{
+    uint64_t seen = 0;
+    for (const FeatCand<F> &c : cands<F>(f))
+        if (c.stage == kFound && seen++ == k)
+            return &c;
+    return nullptr;
+}
+
+} // namespace
+
+extern "C" fsh_feature *fsh_feature_begin(const fsh_view *v, const fsh_orbit *o, uint32_t nx, uint32_t ny, uint32_t iter_bytes,
+                                          uint64_t max_iters)
+{
+    if (!v || !o || nx == 0 || ny == 0 || (iter_bytes != 4 && iter_bytes != 8))
+        return nullptr;
+    auto f = std::make_unique<fsh_feature>();
+    f->is64 = o->is64;
+    f->iter_bytes = iter_bytes;
+    f->max_iters = max_iters;
+    f->prec_bits = v->prec_bits;
+    f->hiX = o->is64 ? o->d.cx : o->f.cx;
+    f->hiY = o->is64 ? o->d.cy : o->f.cy;
+    if (f->is64)
+        feature_begin<double>(*f, *v, nx, ny);
+    else
+        feature_begin<float>(*f, *v, nx, ny);
+    return f.release();
+}
+
+static fsh_feature *feature_begin_direct(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, const uint64_t *at,
+                                         uint32_t iter_bytes, uint64_t max_iters)
+{
+    if (!v || nx == 0 || ny == 0 || (iter_bytes != 4 && iter_bytes != 8))
+        return nullptr;
+    auto f = std::make_unique<fsh_feature>();
+    f->is64 = is64 != 0;
+    f->iter_bytes = iter_bytes;
+    f->max_iters = max_iters;
+    f->prec_bits = v->prec_bits;
+    f->direct = true;
+    if (f->is64)
+        feature_begin<double>(*f, *v, nx, ny, at);
+    else
+        feature_begin<float>(*f, *v, nx, ny, at);
+    return f.release();
+}
+
+extern "C" fsh_feature *fsh_feature_begin_direct(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, uint32_t iter_bytes,
+                                                 uint64_t max_iters)
+{
+    return feature_begin_direct(v, is64, nx, ny, nullptr, iter_bytes, max_iters);
+}
+
+extern "C" fsh_feature *fsh_feature_begin_direct_at(const fsh_view *v, int is64, uint32_t px, uint32_t py, uint32_t iter_bytes,
+                                                    uint64_t max_iters)
+{
+    const uint64_t at[2] = {px, py};
+    return feature_begin_direct(v, is64, 1, 1, at, iter_bytes, max_iters);
+}
+
+namespace {
+
+template <class F, class In, class Real> void feature_direct_grid(const fsh_view &v, uint32_t nx, uint32_t ny, In *in, Real *radius)
+{
+    mpf_set_default_prec(v.prec_bits);
+    fsh_feature f; // for its search radius only
+    f.prec_bits = v.prec_bits;
+    feature_begin<F>(f, v, 1, 1);
+    const hreal<F> R = feature_eval_radius<F>(f);
+    Real rad{};
+    rad.m = R.m, rad.e = R.e;
+    *radius = rad;
+    // T{cX_hp} per column and T{cY_hp} per row; MakeCTFromHP = C(re, im), reduced, per point
+    const FeatScreen scr(v);
+    std::vector<hreal<F>> re(nx), im(ny);
+    for (uint32_t gx = 0; gx < nx; ++gx)
+        re[gx] = hr_from_mpf<F>(scr.X(feat_grid_px(v.width, gx, nx)).v);
+    for (uint32_t gy = 0; gy < ny; ++gy)
+        im[gy] = hr_from_mpf<F>(scr.Y(feat_grid_px(v.height, gy, ny)).v);
+    for (uint32_t gy = 0; gy < ny; ++gy)
+        for (uint32_t gx = 0; gx < nx; ++gx) {
+            const hcplx<F> cc = hc_reduced(hc_from_hr(re[gx], im[gy]));
+            In r{};
+            r.c.re = cc.re, r.c.im = cc.im, r.c.e = cc.e;
+            in[(size_t)gy * nx + gx] = r;
+        }
+}
+
+} // namespace
+
+extern "C" int fsh_feature_direct_grid(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, void *in, void *radius)
+{
+    if (!v || nx == 0 || ny == 0 || !in || !radius)
+        return -1;
+    if (is64)
+        feature_direct_grid<double>(*v, nx, ny, (fs_feature_in_hdr64 *)in, (fs_real_hdr64 *)radius);
+    else
+        feature_direct_grid<float>(*v, nx, ny, (fs_feature_in_hdr32 *)in, (fs_real_hdr32 *)radius);
+    return 0;
+}
+
+extern "C" void fsh_feature_destroy(fsh_feature *f) { delete f; }
+extern "C" int fsh_feature_is64(const fsh_feature *f) { return f->is64; }
+extern "C" uint64_t fsh_feature_candidates(const fsh_feature *f) { return f->is64 ? f->c64.size() : f->c32.size(); }
+
+extern "C" uint64_t fsh_feature_next_batch(fsh_feature *f, void *in, uint64_t cap, int *mode, void *radius, uint64_t *max_iters)
+{
+    mpf_set_default_prec(f->prec_bits);
+    *max_iters = f->max_iters;
+    if (f->is64) {
+        const hreal<double> R = feature_eval_radius<double>(*f);
+        *(fs_real_hdr64 *)radius = fs_real_hdr64{R.m, R.e, 0};
+        return feature_next<double>(*f, (fs_feature_in_hdr64 *)in, cap, mode);
+    }
+    const hreal<float> R = feature_eval_radius<float>(*f);
+    *(fs_real_hdr32 *)radius = fs_real_hdr32{R.m, R.e};
+    return feature_next<float>(*f, (fs_feature_in_hdr32 *)in, cap, mode);
+}
+
+extern "C" void fsh_feature_consume(fsh_feature *f, const void *out, uint64_t n)
+{
+    mpf_set_default_prec(f->prec_bits);
+    if (f->is64)
+        feature_consume<double>(*f, (const fs_feature_out_hdr64 *)out, n);
+    else
+        feature_consume<float>(*f, (const fs_feature_out_hdr32 *)out, n);
+    f->batch.clear();
+}
+
+extern "C" uint64_t fsh_feature_found(const fsh_feature *f)
+{
+    uint64_t n = 0;
+    if (f->is64) {
+        for (const auto &c : f->c64)
+            n += c.stage == kFound;
+    } else {
+        for (const auto &c : f->c32)
+            n += c.stage == kFound;
+    }
+    return n;
+}
+
+extern "C" int fsh_feature_result(fsh_feature *f, uint64_t k, char *cx, char *cy, char *radius, size_t buflen, uint64_t *period,
+                                  fs_real_hdr64 *residual2, uint32_t *grid_index)
+{
+    auto fill = [&](const auto *c) {
+        if (!c)
+            return -1;
+        gmp_snprintf(cx, buflen, "%.Fe", c->cx.v);
+        gmp_snprintf(cy, buflen, "%.Fe", c->cy.v);
+        gmp_snprintf(radius, buflen, "%.Fe", c->radius.v);
+        *period = c->period;
+        *residual2 = fs_real_hdr64{c->residual2.m, c->residual2.e, 0};
+        *grid_index = c->grid;
+        return 0;
+    };
+    return f->is64 ? fill(found_at<double>(*f, k)) : fill(found_at<float>(*f, k));
+}

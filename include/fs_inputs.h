@@ -5,7 +5,7 @@
  * table.  Inside FractalShark none of this is needed -- Fractal.cpp hands the renderer its own
  * PerturbationResults / LAReference buffers, which have the layouts in fs_layout.h.
  *
- * Reference code each entry point follows is cited in fractalshark_amd/host/refinputs.cpp.
+ * Reference code each entry point follows is cited in the units of fractalshark_amd/host/ (map: inputs_state.hpp).
  */
 #ifndef FS_INPUTS_H
 #define FS_INPUTS_H

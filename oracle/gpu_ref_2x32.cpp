@@ -13,7 +13,7 @@
 // against an execution of the reference.  What it can be (and is) checked against:
 //   * the host-side half -- the HDRFloat<double> orbit / LA table it starts from -- is pinned by the golden CRCs of
 //     the Cpu64* algorithms (tests/test_oracle_pins.py); the double -> 2x32 conversion restated in
-//     fractalshark_amd/host/refinputs.cpp is plain host C++ in the reference (dblflt.h:30-52);
+//     fractalshark_amd/host/convert_2x32.cpp is plain host C++ in the reference (dblflt.h:30-52);
 //   * the double-float primitives are cross-checked against exact rational arithmetic (tests/test_2x32_oracle.py);
 //   * the rendered iteration counts are compared with the pinned HDRFloat<double> oracle on the same view
 //     (same algorithm, 48 vs 53 mantissa bits: equal except at chaotic pixels).

@@ -39,7 +39,7 @@ def test_view_precision(native_libs, case):
 @pytest.mark.parametrize("case", VEC["double_float_split"], ids=[c["name"] for c in VEC["double_float_split"]])
 def test_double_to_double_float_split(native_libs, case):
     """TestCudaDblflt.cpp: what MattDblflt(double) / CudaDblflt(double) must give back.  The product's converter is the one every
-    HDRFloat<CudaDblflt> / CudaDblflt orbit, table and coordinate goes through (fsh_convert_*_to_*2x32, host/refinputs.cpp)."""
+    HDRFloat<CudaDblflt> / CudaDblflt orbit, table and coordinate goes through (fsh_convert_*_to_*2x32, host/convert_2x32.cpp)."""
     import numpy as np
     lib = _capi.inputs_lib()
     src = np.zeros(1, np.dtype([("x", "<f8"), ("y", "<f8")]))

@@ -1,6 +1,6 @@
 """Imagina ".im" files that carry a reference orbit: the writer
 (RefOrbitCalc::SaveOrbitResults(results, filename) -> CompressMax + SaveOrbitBin) and the reader (LoadOrbitBin +
-DecompressMax) restated in fractalshark_amd/host/refinputs.cpp.
+DecompressMax) restated in fractalshark_amd/host/im_files.cpp.
 
 Parity status: UNPINNED against reference-written files (the reference tree's .im files are git-LFS pointer stubs).
 Pinned here: the byte layout -- restated independently below, and the struct sizes / offsets it assumes are checked
