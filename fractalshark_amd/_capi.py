@@ -84,6 +84,13 @@ class AuditResult(C.Structure):
                 ("offenders", AuditOffender * AUDIT_MAX_OFFENDERS)]
 
 
+class ExactKept(C.Structure):
+    """fs_exact_kept (include/fs_layout.h)."""
+    _fields_ = [("samples", u64), ("proved", u64), ("cap", u64), ("device_bytes", u64), ("frac_bits", u32), ("limbs", u32),
+                ("bailout", u32), ("inclusive", u32), ("wide", u32), ("cycle_check", u32), ("valid", u32), ("reserved", u32)]
+
+
+assert C.sizeof(ExactKept) == 64
 assert C.sizeof(AutozoomResult) == 200
 assert C.sizeof(AuditOffender) == 24 and C.sizeof(AuditResult) == 568
 assert C.sizeof(AtHdr32) == 116 and C.sizeof(AtHdr64) == 232 and C.sizeof(At2x32) == 184
@@ -154,6 +161,10 @@ def render_lib():
     _decl(lib, "fs_read_exact_proved", u32, [vp, vp, u64])
     _decl(lib, "fs_read_exact_cycle_stats", u32, [vp, vp])
     _decl(lib, "fs_set_exact_cycle_fingerprint_bits", u32, [vp, u32])
+    _decl(lib, "fs_set_exact_keep", u32, [vp, C.c_int])
+    _decl(lib, "fs_render_exact_continue", u32, [vp, u64])
+    _decl(lib, "fs_exact_kept_info", u32, [vp, C.POINTER(ExactKept)])
+    _decl(lib, "fs_exact_drop_kept", u32, [vp])
     _decl(lib, "fs_render_bla", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_render_direct", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_upload_orbit_scaled", u32, [vp, C.c_int, u32, vp, vp, u64, u64])
@@ -237,6 +248,7 @@ RENDER_SYMBOLS = [
     "fs_render_exact", "fs_exact_stable_mask", "fs_set_exact_slice", "fs_read_exact_stats",
     "fs_exact_sample_counts", "fs_render_exact_wide", "fs_exact_wide_state", "fs_exact_audit",
     "fs_set_exact_cycle_check", "fs_read_exact_proved", "fs_read_exact_cycle_stats", "fs_set_exact_cycle_fingerprint_bits",
+    "fs_set_exact_keep", "fs_render_exact_continue", "fs_exact_kept_info", "fs_exact_drop_kept",
     "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
     "fs_render_direct_lp", "fs_clear",

@@ -1,6 +1,7 @@
 // exact_cycle_math.hpp -- the exact renderer's proof of non-escape by an exact repeat of the state (DESIGN.md 6.3 "Cycle check"),
 // for the device (kernels_exact.hip, the C = true instantiations) and for the host (g++; tests/exact/exact_cycle_host.cpp runs the
-// same functions on the CPU).
+// same functions on the CPU), and the park-and-resume rule of the continuation (fs_set_exact_keep; the K = true instantiations,
+// tests/exact/exact_keep_host.cpp), at the end of the file.
 //
 // The arithmetic of exact_math.hpp is integer and nothing is rounded, so z_{k+1} is a function of z_k alone.  n is the index of the
 // z a sample holds (z_1 = c).  If the z_n it holds equals, limb for limb, the z_m it held at an earlier m, then z_k = z_{k - (n - m)}
@@ -90,34 +91,82 @@ struct CycleRun {
     uint64_t compares; // times the checkpoint was read back
 };
 
-// One sample from z_1 = c to its end: the loop of k_exact_slice<L, S, true> without the slices.  (Host loops and tests.)
-template <int L>
-FSX_HD CycleRun cycle_run(const uint32_t (&cx)[L], const uint32_t (&cy)[L], const Params &P, uint64_t cap, uint32_t mx, uint32_t my)
+// ---- Keeping (fs_set_exact_keep, fs_render_exact_continue; DESIGN.md 6.3 "Continuation").
+// step() tests z_n and replaces it in one call, so a sample that stops at n == cap + 1 holds z_{cap+2} with n still cap + 1: it has
+// passed the escape test at cap + 1, and neither the n++ nor the rule at n = cap + 2 has happened -- a run with that cap never gets
+// there, and its mask says "unproved".  That is the PARKED state: (x, y) = z_{cap+2}, n = cap + 1 and the checkpoint as it stands.
+// Under a larger cap the same sample would have gone on with exactly those two things, so a resumed sample does them first
+// (cycle_resume) and then enters the step loop as a running one does: the rule at cap + 2 is neither skipped nor run twice, nor run
+// before anyone asked for a larger cap.  The step that made z_{cap+2} is not repeated: steps and read-backs of the two runs add up
+// to those of one run with the larger cap.
+// (The wave-per-sample kernel of kernels_exact_wide.hip tests before it steps and parks z_{cap+1} with n = cap + 1: it resumes as a
+// running sample, and repeats the one escape test.)
+template <int L, bool C>
+FSX_HD bool cycle_resume(const uint32_t (&x)[L], const uint32_t (&y)[L], uint64_t &n, uint32_t *ck, uint32_t stride, uint32_t slot,
+                         uint32_t &fx, uint32_t &fy, uint32_t mx, uint32_t my, uint32_t &compares)
 {
-    uint32_t x[L], y[L], ck[2 * L], fx, fy, compares = 0;
-    FSX_UNROLL
-    for (int i = 0; i < L; i++)
-        x[i] = cx[i], y[i] = cy[i];
-    cycle_take<L>(x, y, ck, 1, 0, fx, fy);
+    n++;
+    if constexpr (C)
+        return cycle_check<L>(x, y, n, ck, stride, slot, fx, fy, mx, my, compares);
+    else
+        return false;
+}
+
+// A sample between two runs: what a list holds of it (the fingerprint is read back from the checkpoint, as a slice does).
+template <int L> struct CycleState {
+    uint32_t x[L], y[L], ck[2 * L];
+    uint64_t n;
+};
+
+// One sample from the state S to its end under `cap`: from z_1 = c (resume = false: S is set up here) or from a parked state
+// (resume = true, cap above the one it was parked under).  A sample that ends capped leaves S parked.  check = false: the loop of
+// the C = false kernels (no proof, no read-back).  (Host loops and tests.)
+template <int L>
+FSX_HD CycleRun cycle_run_from(CycleState<L> &S, bool resume, const uint32_t (&cx)[L], const uint32_t (&cy)[L], const Params &P,
+                               uint64_t cap, bool check, uint32_t mx, uint32_t my)
+{
+    uint32_t fx, fy, compares = 0;
     CycleRun R{kCycleCapped, cap, 0, 0};
-    for (uint64_t n = 1;;) {
+    if (!resume) {
+        FSX_UNROLL
+        for (int i = 0; i < L; i++)
+            S.x[i] = cx[i], S.y[i] = cy[i];
+        S.n = 1;
+        cycle_take<L>(S.x, S.y, S.ck, 1, 0, fx, fy);
+    } else {
+        fx = S.ck[0], fy = S.ck[L];
+        const bool proved = check ? cycle_resume<L, true>(S.x, S.y, S.n, S.ck, 1, 0, fx, fy, mx, my, compares)
+                                  : cycle_resume<L, false>(S.x, S.y, S.n, S.ck, 1, 0, fx, fy, mx, my, compares);
+        R.compares = compares;
+        if (proved) {
+            R.outcome = kCycleProved;
+            return R;
+        }
+    }
+    for (;;) {
         R.steps++;
-        const bool escaped = step<L>(x, y, cx, cy, P);
-        if (escaped || n == cap + 1) {
+        const bool escaped = step<L>(S.x, S.y, cx, cy, P);
+        if (escaped || S.n == cap + 1) {
             R.outcome = escaped ? kCycleEscaped : kCycleCapped;
-            R.value = escaped ? n - 1 : cap;
+            R.value = escaped ? S.n - 1 : cap;
             break;
         }
-        n++;
-        const uint32_t before = compares;
-        const bool proved = cycle_check<L>(x, y, n, ck, 1, 0, fx, fy, mx, my, compares);
-        R.compares += compares - before;
-        if (proved) {
+        S.n++;
+        if (check && cycle_check<L>(S.x, S.y, S.n, S.ck, 1, 0, fx, fy, mx, my, compares)) {
             R.outcome = kCycleProved;
             break;
         }
     }
+    R.compares = compares;
     return R;
+}
+
+// One sample from z_1 = c to its end: the loop of k_exact_slice<L, S, true> without the slices.  (Host loops and tests.)
+template <int L>
+FSX_HD CycleRun cycle_run(const uint32_t (&cx)[L], const uint32_t (&cy)[L], const Params &P, uint64_t cap, uint32_t mx, uint32_t my)
+{
+    CycleState<L> S;
+    return cycle_run_from<L>(S, false, cx, cy, P, cap, true, mx, my);
 }
 
 } // namespace fsx

@@ -528,10 +528,23 @@ struct FsExactArgs {
     uint32_t *src_ck, *dst_ck;
     uint8_t *proved;         // [W * H] (samples: [W]): 1 where the sample was proved; zeroed by the caller
     uint32_t fp_mx, fp_my;   // the fingerprint masks on x[0] and y[0]
+    // keeping (read by the K = true kernels only; fs_set_exact_keep): a sample that stops at n == cap + 1 unproved is parked -- its
+    // state, n and pixel, with the cycle check its checkpoint -- in a list no survivor is written to in that slice, at a slot
+    // counted by park_count; resume: the list's samples are parked ones and make the step's deferred n++ and cycle check first
+    uint32_t *park_xy;
+    uint64_t *park_n;
+    uint32_t *park_pix;
+    uint32_t *park_ck;
+    uint32_t *park_count;
+    uint32_t resume;
 };
 // samples: the list is W == H runs of their own, run e at cx[l * W + e], cy[l * W + e], and iters = uint64 counts[W] (fs_exact_audit)
-// cycle: the kernels with the cycle check.  false: `limbs` is not an instantiated limb count (nothing launched)
-bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, hipStream_t s);
+// cycle: the kernels with the cycle check.  keep: the kernels that park (frames only).  false: `limbs` is not an instantiated limb
+// count (nothing launched)
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, bool keep, hipStream_t s);
+// the pixels with proved[y * W + x] != 0 become `value` in a frame of `pitch` elements per row
+void fsk_exact_set_proved(void *iters, int iter_u64, const uint8_t *proved, uint32_t W, uint32_t H, uint32_t pitch, uint64_t value,
+                          hipStream_t s);
 // mask[y * W + x] = (first ? 1 : mask) & (centre == shifted) over two frames of the same pitch (elements)
 void fsk_exact_mask(const void *centre, const void *shifted, int iter_u64, uint8_t *mask, uint32_t W, uint32_t H, uint32_t pitch,
                     int first, hipStream_t s);
@@ -560,9 +573,13 @@ struct FsExactWideArgs {
     uint32_t slice;          // steps at most
     uint32_t *dst_count;     // += samples still running
     unsigned long long *stats; // [0] += steps taken
+    // keeping (read by the K = true kernels only; fs_set_exact_keep): a sample that stops at n == cap + 1 goes to the destination
+    // list as a running one does -- no survivor is written there in that slice -- at a slot counted by park_count
+    uint32_t *park_count;
 };
-// one workgroup of 64 per sample; false: the limb count needs more than 11 limbs per lane (nothing launched)
-bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, hipStream_t s);
+// one workgroup of 64 per sample; keep: the kernels that park; false: the limb count needs more than 11 limbs per lane (nothing
+// launched)
+bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, bool keep, hipStream_t s);
 
 // ---- fs_exact_audit (kernels_exact_audit.hip, exact_audit_math.hpp): the frame at the samples against their runs' counts.
 // counts[k * n_samples + i] = run k of sample i (run 0 = c, run 1 + 4 j + d = level j's four shifts).  One workgroup of one wave

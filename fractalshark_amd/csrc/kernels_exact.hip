@@ -20,6 +20,14 @@
 // checkpoint is 2L more limb planes per list, the lane's slot of the SOURCE list while the slice runs: written there when it is
 // taken, read back only when the two-register fingerprint matches, and copied to the destination slot with the rest of the state by
 // a lane that goes on to the next slice.  C = false compiles to what it was without the parameter.
+//
+// Keeping (K = true; fs_set_exact_keep, frames only): a sample that stops at n == cap + 1 unproved is PARKED (exact_cycle_math.hpp
+// says what that state is): it writes the cap into the frame as ever and its state to the park list, at a slot taken the way the
+// survivors take theirs -- ballot, prefix count, one atomic add per wave -- from a counter of its own.  Every sample starts at n = 1
+// and a slice advances every running lane by the same number of steps, so all running samples hold the same n: they meet the cap in
+// one and the same slice, the last one, which has no survivor, and the host hands that slice's unused destination list in as the
+// park list (without compaction, a list of its own).  A.resume: the source list holds parked samples, which make their deferred n++
+// and cycle check (fsx::cycle_resume) before the step loop.  K = false compiles to what it was without the parameter.
 #include <hip/hip_runtime.h>
 
 #include "exact_cycle_math.hpp"
@@ -27,7 +35,7 @@
 
 namespace {
 
-template <int L, bool S, bool C> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
+template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
 {
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     bool alive = i < A.n_src;
@@ -73,6 +81,20 @@ template <int L, bool S, bool C> __global__ void __launch_bounds__(64) k_exact_s
 
     const size_t out_idx = S ? (size_t)pix : (size_t)row * A.rounded_width + col;
     uint32_t my_steps = 0, wave_steps = 0;
+    bool parked = false;
+    if constexpr (K) {
+        if (A.resume && alive) {
+            if (fsx::cycle_resume<L, C>(x, y, n, A.src_ck, A.stride, i, fx, fy, A.fp_mx, A.fp_my, my_compares)) {
+                if (A.iter_u64)
+                    ((uint64_t *)A.iters)[out_idx] = A.cap;
+                else
+                    ((uint32_t *)A.iters)[out_idx] = (uint32_t)A.cap;
+                A.proved[pix] = 1;
+                my_proved = 1;
+                alive = false;
+            }
+        }
+    }
     for (uint32_t k = 0; k < A.slice; k++) {
         if (__ballot(alive) == 0)
             break;
@@ -87,6 +109,8 @@ template <int L, bool S, bool C> __global__ void __launch_bounds__(64) k_exact_s
                 else
                     ((uint32_t *)A.iters)[out_idx] = (uint32_t)v;
                 alive = false;
+                if constexpr (K)
+                    parked = !escaped;
             } else {
                 n++;
                 if constexpr (C) {
@@ -139,6 +163,32 @@ template <int L, bool S, bool C> __global__ void __launch_bounds__(64) k_exact_s
         A.dst_pix[dst] = 0;
     }
 
+    // the samples that met the cap go to the park list
+    if constexpr (K) {
+        const uint64_t pk = __ballot(parked);
+        if (pk != 0) {
+            uint32_t base = 0;
+            if (threadIdx.x == 0)
+                base = atomicAdd(A.park_count, (uint32_t)__popcll(pk));
+            base = __shfl(base, 0);
+            const uint32_t ps = base + (uint32_t)__popcll(pk & ((1ull << threadIdx.x) - 1ull));
+            if (parked) {
+#pragma unroll
+                for (int l = 0; l < L; l++) {
+                    A.park_xy[(size_t)l * A.stride + ps] = x[l];
+                    A.park_xy[(size_t)(L + l) * A.stride + ps] = y[l];
+                }
+                A.park_n[ps] = n;
+                A.park_pix[ps] = pix;
+                if constexpr (C) {
+#pragma unroll
+                    for (int l = 0; l < 2 * L; l++)
+                        A.park_ck[(size_t)l * A.stride + ps] = A.src_ck[(size_t)l * A.stride + i];
+                }
+            }
+        }
+    }
+
     // lane slots the wave occupied in its step loop, and the steps its lanes really took
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1)
@@ -162,6 +212,16 @@ template <int L, bool S, bool C> __global__ void __launch_bounds__(64) k_exact_s
     }
 }
 
+// a continuation's proved pixels take the new cap
+template <class T>
+__global__ void __launch_bounds__(256) k_exact_set_proved(T *__restrict__ iters, const uint8_t *__restrict__ proved, uint32_t W, uint32_t H,
+                                                           uint32_t pitch, T value)
+{
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p < W * H && proved[p])
+        iters[(size_t)(p / W) * pitch + p % W] = value;
+}
+
 template <class T>
 __global__ void __launch_bounds__(256) k_exact_mask(const T *__restrict__ centre, const T *__restrict__ shifted, uint8_t *__restrict__ mask,
                                                      uint32_t W, uint32_t H, uint32_t pitch, int first)
@@ -176,26 +236,42 @@ __global__ void __launch_bounds__(256) k_exact_mask(const T *__restrict__ centre
 
 } // namespace
 
-bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, hipStream_t s)
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, bool keep, hipStream_t s)
 {
+    if (keep && samples)
+        return false;
     const dim3 grid((A.n_src + 63u) / 64u), block(64);
     switch (limbs) {
 #define FS_EXACT_CASE(L)                                                                                                \
     case L:                                                                                                             \
-        if (cycle && samples)                                                                                           \
-            hipLaunchKernelGGL((k_exact_slice<L, true, true>), grid, block, 0, s, A);                                   \
+        if (keep && cycle)                                                                                              \
+            hipLaunchKernelGGL((k_exact_slice<L, false, true, true>), grid, block, 0, s, A);                            \
+        else if (keep)                                                                                                  \
+            hipLaunchKernelGGL((k_exact_slice<L, false, false, true>), grid, block, 0, s, A);                           \
+        else if (cycle && samples)                                                                                      \
+            hipLaunchKernelGGL((k_exact_slice<L, true, true, false>), grid, block, 0, s, A);                            \
         else if (cycle)                                                                                                 \
-            hipLaunchKernelGGL((k_exact_slice<L, false, true>), grid, block, 0, s, A);                                  \
+            hipLaunchKernelGGL((k_exact_slice<L, false, true, false>), grid, block, 0, s, A);                           \
         else if (samples)                                                                                               \
-            hipLaunchKernelGGL((k_exact_slice<L, true, false>), grid, block, 0, s, A);                                  \
+            hipLaunchKernelGGL((k_exact_slice<L, true, false, false>), grid, block, 0, s, A);                           \
         else                                                                                                            \
-            hipLaunchKernelGGL((k_exact_slice<L, false, false>), grid, block, 0, s, A);                                 \
+            hipLaunchKernelGGL((k_exact_slice<L, false, false, false>), grid, block, 0, s, A);                          \
         return true;
         FS_EXACT_FOR_EACH_L(FS_EXACT_CASE)
 #undef FS_EXACT_CASE
     default:
         return false;
     }
+}
+
+void fsk_exact_set_proved(void *iters, int iter_u64, const uint8_t *proved, uint32_t W, uint32_t H, uint32_t pitch, uint64_t value,
+                          hipStream_t s)
+{
+    const dim3 grid((W * H + 255u) / 256u), block(256);
+    if (iter_u64)
+        hipLaunchKernelGGL(k_exact_set_proved<uint64_t>, grid, block, 0, s, (uint64_t *)iters, proved, W, H, pitch, value);
+    else
+        hipLaunchKernelGGL(k_exact_set_proved<uint32_t>, grid, block, 0, s, (uint32_t *)iters, proved, W, H, pitch, (uint32_t)value);
 }
 
 void fsk_exact_mask(const void *centre, const void *shifted, int iter_u64, uint8_t *mask, uint32_t W, uint32_t H, uint32_t pitch,

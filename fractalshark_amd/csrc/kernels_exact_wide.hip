@@ -23,6 +23,12 @@
 // Slices as in kernels_exact.hip: a launch takes at most `slice` steps; a sample still running is written to the destination
 // list (limb-major: plane l holds limb l of every slot) at a slot taken from one atomic add, so the next launch has exactly one
 // wave per running sample.
+//
+// Keeping (K = true; fs_set_exact_keep): a sample that stops at n == cap + 1 is parked.  The kernel breaks BEFORE it steps, so the
+// parked state is z_{cap+1} with n = cap + 1 -- a running sample's, and it resumes as one: the escape test on z_{cap+1} is made
+// again (and counted again), nothing else.  All running samples hold the same n, so they meet the cap in one and the same slice,
+// which has no survivor: the parked samples go to that slice's destination list, at slots counted by a counter of their own.
+// K = false compiles to what it was without the parameter.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -178,7 +184,7 @@ __device__ __forceinline__ void load_blocks(const uint32_t *p, uint32_t stride, 
     }
 }
 
-template <int M> __global__ void __launch_bounds__(64) k_exact_wide_slice(const FsExactWideArgs A)
+template <int M, bool K> __global__ void __launch_bounds__(64) k_exact_wide_slice(const FsExactWideArgs A)
 {
     __shared__ uint32_t lds[128 * M];
     const uint32_t lane = threadIdx.x, slot = blockIdx.x, L = A.limbs;
@@ -202,7 +208,7 @@ template <int M> __global__ void __launch_bounds__(64) k_exact_wide_slice(const 
         load_blocks<M>(A.src_xy + (size_t)L * A.stride, A.stride, slot, L, lane, y);
     }
 
-    bool running = true;
+    bool running = true, parked = false;
     uint32_t steps = 0;
     for (uint32_t k = 0; k < A.slice; k++) {
         // the escape test on z_n, on the untruncated sum
@@ -227,6 +233,8 @@ template <int M> __global__ void __launch_bounds__(64) k_exact_wide_slice(const 
                         ((uint32_t *)A.out)[o] = (uint32_t)v;
                 }
                 running = false;
+                if constexpr (K)
+                    parked = !escaped;
                 break;
             }
         }
@@ -253,11 +261,11 @@ template <int M> __global__ void __launch_bounds__(64) k_exact_wide_slice(const 
         n++;
     }
 
-    if (running) {
+    if (running || (K && parked)) {
         uint32_t dst = slot;
         if (!A.state_only) {
             if (lane == 0)
-                dst = atomicAdd(A.dst_count, 1u);
+                dst = atomicAdd(K && parked ? A.park_count : A.dst_count, 1u);
             dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)dst);
         }
 #pragma unroll
@@ -279,13 +287,16 @@ template <int M> __global__ void __launch_bounds__(64) k_exact_wide_slice(const 
 
 } // namespace
 
-bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, hipStream_t s)
+bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, bool keep, hipStream_t s)
 {
     const dim3 grid(n_src), block(64);
     switch (fsw::block_for(A.limbs)) {
 #define FS_EXACT_WIDE_CASE(M)                                                                                          \
     case M:                                                                                                             \
-        hipLaunchKernelGGL(k_exact_wide_slice<M>, grid, block, 0, s, A);                                                \
+        if (keep)                                                                                                       \
+            hipLaunchKernelGGL((k_exact_wide_slice<M, true>), grid, block, 0, s, A);                                    \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_exact_wide_slice<M, false>), grid, block, 0, s, A);                                   \
         return true;
         FS_EXACT_WIDE_FOR_EACH_M(FS_EXACT_WIDE_CASE)
 #undef FS_EXACT_WIDE_CASE

@@ -260,6 +260,7 @@ uint32_t ensure_iter_buffer(fs_renderer *r)
 void free_all(fs_renderer *r)
 {
     free_perturb(r);
+    exact_drop_kept(r);
     buf_release(r, r->iters_internal);
     (void)r_release(r, r->colors);
     (void)r_release(r, r->reduction);
@@ -391,6 +392,7 @@ uint32_t fs_init_memory(fs_renderer *r, uint32_t w, uint32_t h, uint32_t antiali
         return e;
     if (iter_bytes != 4 && iter_bytes != 8)
         return FS_ERR_UNSUPPORTED;
+    exact_drop_kept(r);
     if (uint32_t e = ensure_streams(r))
         return e;
     // palette: re-upload when the host pointer or the generation changes (GPU_Render.cu:270-304)
@@ -480,6 +482,7 @@ uint32_t fs_set_row_bands(fs_renderer *r, uint32_t band_first_row, uint32_t band
         return FS_ERR_6;
     if (band_rows != 0 && (band_stride_rows < band_rows))
         return FS_ERR_7;
+    exact_drop_kept(r);
     r->band_first = band_first_row;
     r->band_rows = band_rows;
     r->band_stride = band_stride_rows;
@@ -501,6 +504,7 @@ uint32_t fs_set_external_iter_buffer(fs_renderer *r, void *device_ptr, uint64_t 
         return e;
     if (r->width == 0)
         return FS_ERR_6;
+    exact_drop_kept(r);
     r->iters_external = device_ptr;
     r->iters_external_bytes = device_ptr ? (size_t)capacity_bytes : 0;
     const uint32_t e = ensure_iter_buffer(r); // too small for the current geometry: rejected, internal buffer restored

@@ -9,6 +9,7 @@ uint32_t fs_clear(fs_renderer *r)
 {
     if (uint32_t e = use_device(r))
         return e;
+    exact_drop_kept(r);
     if (!r->memory_initialized())
         return 0;
     const size_t elems = (size_t)r->w_block * 16u * r->local_rows_padded;

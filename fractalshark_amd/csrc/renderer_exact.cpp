@@ -7,22 +7,24 @@ using namespace fsr;
 // ---- what the two exact paths (fs_render_exact: a lane per sample, fs_render_exact_wide: a wave per sample) share on the host.
 // The device block of one call: [counter, statistics | cx | cy | `lists` lists of running samples], a list being the limb planes of
 // x and y, then n, then the sample's id; with the cycle check (`cycle`) a list ends with the limb planes of the checkpoints, and
-// the block with the byte plane of the proved samples.
+// the block with the byte plane of the proved samples (n_proved of them when that is not the lists' n: a continuation's lists hold
+// the kept samples, its plane the frame).
 struct ExactLayout {
     static constexpr size_t head = 256;
     size_t cx_bytes, cy_bytes, xy_bytes, n_bytes, id_bytes, list_bytes, proved_bytes;
-    ExactLayout(uint32_t limbs, uint32_t nx, uint32_t ny, uint32_t n, bool cycle = false)
+    ExactLayout(uint32_t limbs, uint32_t nx, uint32_t ny, uint32_t n, bool cycle = false, uint32_t n_proved = 0)
     {
         auto up = [](size_t b) { return (b + 255) / 256 * 256; };
         cx_bytes = up((size_t)limbs * nx * 4), cy_bytes = up((size_t)limbs * ny * 4);
         xy_bytes = up((size_t)2 * limbs * n * 4), n_bytes = up((size_t)n * 8), id_bytes = up((size_t)n * 4);
         list_bytes = xy_bytes + n_bytes + id_bytes + (cycle ? xy_bytes : 0);
-        proved_bytes = cycle ? up(n) : 0;
+        proved_bytes = cycle ? up(n_proved ? n_proved : n) : 0;
     }
     size_t bytes(int lists) const { return head + cx_bytes + cy_bytes + (size_t)lists * list_bytes + proved_bytes; }
     uint32_t *checkpoints(char *list) const { return (uint32_t *)(list + xy_bytes + n_bytes + id_bytes); }
     uint8_t *proved(char *blk, int lists) const { return (uint8_t *)list(blk, lists); }
     uint32_t *count(char *blk) const { return (uint32_t *)blk; }
+    uint32_t *park_count(char *blk) const { return (uint32_t *)(blk + 4); }
     unsigned long long *stats(char *blk) const { return (unsigned long long *)(blk + 16); }
     uint32_t *cx(char *blk) const { return (uint32_t *)(blk + head); }
     uint32_t *cy(char *blk) const { return (uint32_t *)(blk + head + cx_bytes); }
@@ -56,6 +58,62 @@ static hipError_t exact_slice_loop(hipStream_t s, uint32_t *d_cnt, Launch launch
             return hipSuccess;
         survivors(left);
     }
+}
+
+// ---- Keeping (fs_set_exact_keep, fs_render_exact_continue).  kExactKeep: the call parks the samples that meet the cap and leaves
+// them as the renderer's kept set; kExactResume: the call starts from that set instead of z_1 = c (and keeps again).
+enum ExactMode { kExactPlain = 0, kExactKeep = 1, kExactResume = 2 };
+
+void fsr::exact_drop_kept(fs_renderer *r)
+{
+    if (r->exact_kept.blk)
+        (void)r_free(r, r->exact_kept.blk);
+    r->exact_kept = fs_renderer::ExactKept{};
+}
+
+// The kept set of a call that has just ended: the n_parked samples of `park` -- a list of the layout Ys with src_stride slots --
+// repacked into a block of their size, with device copies of the axes and, with the check, the proved plane.  K: what the call was
+// given; block, size and sample count are set here.  The set before it goes once the new one stands (a continuation's sources
+// live in it).
+static hipError_t exact_keep_install(fs_renderer *r, const ExactLayout &Ys, char *park, uint32_t src_stride, uint32_t n_parked,
+                                     const uint32_t *d_cx, const uint32_t *d_cy, const uint8_t *d_proved, fs_renderer::ExactKept K)
+{
+    hipStream_t s = r->compute;
+    const uint32_t L = K.limbs, npix = K.W * K.H;
+    const ExactLayout Yk(L, K.W, K.H, n_parked, K.cycle, npix);
+    char *nb = nullptr;
+    hipError_t e = r_alloc(r, (void **)&nb, Yk.bytes(1), kFrame);
+    if (e != hipSuccess)
+        return e;
+    e = hipMemcpyAsync(Yk.cx(nb), d_cx, (size_t)L * K.W * 4, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(Yk.cy(nb), d_cy, (size_t)L * K.H * 4, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && n_parked != 0) {
+        // the 2L limb planes (and the checkpoint's 2L): rows of n_parked words, from a pitch of src_stride words to one of n_parked
+        char *dl = Yk.list(nb, 0);
+        const size_t row = (size_t)n_parked * 4;
+        e = hipMemcpy2DAsync(dl, row, park, (size_t)src_stride * 4, row, 2 * L, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && K.cycle)
+            e = hipMemcpy2DAsync(Yk.checkpoints(dl), row, Ys.checkpoints(park), (size_t)src_stride * 4, row, 2 * L,
+                                 hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(dl + Yk.xy_bytes, park + Ys.xy_bytes, (size_t)n_parked * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(dl + Yk.xy_bytes + Yk.n_bytes, park + Ys.xy_bytes + Ys.n_bytes, (size_t)n_parked * 4,
+                               hipMemcpyDeviceToDevice, s);
+    }
+    if (e == hipSuccess && K.cycle)
+        e = hipMemcpyAsync(Yk.proved(nb, 1), d_proved, npix, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)r_free(r, nb);
+        return e;
+    }
+    exact_drop_kept(r);
+    K.blk = nb, K.bytes = Yk.bytes(1), K.samples = n_parked, K.valid = true;
+    r->exact_kept = K;
+    return hipSuccess;
 }
 
 extern "C" {
@@ -173,68 +231,101 @@ static bool exact_axis_in_range(const uint32_t *axis, uint32_t n, uint32_t limbs
 // frame, cx and cy holding n_runs values each and `out` uint64 counts[n_runs] on the device (the kernel's sample mode).
 // With the cycle check on (fs_set_exact_cycle_check) the C = true kernels run and the lists carry the checkpoints; keep_proved:
 // the call's proved mask becomes the one fs_read_exact_proved returns.
+// mode (frames only): kExactKeep parks the samples that meet the cap -- in the last slice's destination list, which no survivor is
+// written to; without compaction in a second list -- and leaves them as the kept set.  kExactResume starts from the kept set (cx,
+// cy and the format arguments are not read: the set's hold): its list is the first slice's source and the second of the two lists
+// from then on, the call's block [counter, statistics | one list] the other; axes and proved plane are the set's own, and the
+// pixels proved so far take the new cap first.  *started (when given) = false when the call returns before it has touched the frame
+// or the set: its one allocation failed.
 static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
                             uint32_t bailout, int inclusive, uint64_t n_iterations, void *out, uint32_t n_runs = 0,
-                            bool keep_proved = false)
+                            bool keep_proved = false, ExactMode mode = kExactPlain, bool *started = nullptr)
 {
-    const bool samples = n_runs != 0, cycle = r->exact_cycle_check;
+    if (started)
+        *started = false;
+    const bool samples = n_runs != 0, keep = mode != kExactPlain, resume = mode == kExactResume;
+    const fs_renderer::ExactKept K0 = r->exact_kept;
+    if (resume)
+        frac_bits = K0.frac_bits, limbs = K0.limbs, bailout = K0.bailout, inclusive = K0.inclusive;
+    const bool cycle = resume ? K0.cycle : r->exact_cycle_check;
     const uint32_t W = samples ? n_runs : r->width, H = samples ? n_runs : r->height, npix = samples ? n_runs : W * H;
-    const ExactLayout Y(limbs, W, H, npix, cycle);
+    const uint32_t n_list = resume ? K0.samples : npix; // slots of a list
+    const ExactLayout Y(limbs, W, H, n_list, cycle, npix);
     const bool compact = !r->exact_no_compaction;
+    const int n_lists = compact || keep ? 2 : 1;
     char *blk = nullptr;
     hipStream_t s = r->compute;
-    FS_TRY(r_alloc(r, (void **)&blk, Y.bytes(compact ? 2 : 1), kFrame));
+    FS_TRY(r_alloc(r, (void **)&blk, resume ? Y.head + Y.list_bytes : Y.bytes(n_lists), kFrame));
+    if (started)
+        *started = true;
     unsigned long long *d_stats = Y.stats(blk);
-    char *lists[2] = {Y.list(blk, 0), Y.list(blk, compact ? 1 : 0)};
+    // (without compaction the one list is lists[fixed]; the other, when there is one, is where the samples are parked)
+    const int fixed = resume ? 1 : 0;
+    char *lists[2] = {resume ? blk + Y.head : Y.list(blk, 0), resume ? Y.list(K0.blk, 0) : Y.list(blk, n_lists - 1)};
+    char *axes = resume ? K0.blk : blk, *park = nullptr;
 
     FsExactArgs A{};
-    A.cx = Y.cx(blk), A.cy = Y.cy(blk);
+    A.cx = Y.cx(axes), A.cy = Y.cy(axes);
     A.W = W, A.H = H, A.rounded_width = samples ? 0u : r->w_block * 16u;
     A.iter_u64 = samples || r->iter_bytes == 8 ? 1u : 0u;
     A.iters = out;
     A.cap = n_iterations;
     A.P = fsx::make_params(frac_bits, bailout, inclusive);
-    A.stride = npix;
-    A.n_src = npix;
-    A.first = 1;
+    A.stride = n_list;
+    A.n_src = n_list;
+    A.first = resume ? 0u : 1u;
+    A.resume = resume ? 1u : 0u;
     A.compact = compact ? 1u : 0u;
     A.dst_count = Y.count(blk);
+    A.park_count = Y.park_count(blk);
     A.stats = d_stats;
     if (cycle) {
-        A.proved = Y.proved(blk, compact ? 2 : 1);
+        A.proved = resume ? Y.proved(K0.blk, 1) : Y.proved(blk, n_lists);
         fsx::cycle_masks(r->exact_cycle_fp_bits, A.fp_mx, A.fp_my);
     }
 
     uint64_t slices = 0, after_first = 0;
     hipError_t e = hipMemsetAsync(blk, 0, Y.head, s);
-    if (e == hipSuccess && cycle)
+    if (e == hipSuccess && cycle && !resume)
         e = hipMemsetAsync(A.proved, 0, npix, s);
-    if (e == hipSuccess)
+    if (e == hipSuccess && resume && K0.proved != 0) { // (a sample the continuation proves writes the new cap itself)
+        fsk_exact_set_proved(out, r->iter_bytes == 8, A.proved, W, H, r->w_block * 16u, n_iterations, s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && !resume)
         e = hipMemcpyAsync(Y.cx(blk), cx, (size_t)limbs * W * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
+    if (e == hipSuccess && !resume)
         e = hipMemcpyAsync(Y.cy(blk), cy, (size_t)limbs * H * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
         e = exact_slice_loop(
             s, A.dst_count,
             [&](uint64_t k) {
-                char *src = lists[(k & 1) ^ 1], *dst = lists[k & 1];
+                char *src = compact ? lists[(k & 1) ^ 1] : lists[fixed], *dst = compact ? lists[k & 1] : lists[fixed];
+                if (keep) {
+                    park = compact ? dst : lists[fixed ^ 1];
+                    A.park_xy = (uint32_t *)park, A.park_n = (uint64_t *)(park + Y.xy_bytes);
+                    A.park_pix = (uint32_t *)(park + Y.xy_bytes + Y.n_bytes), A.park_ck = Y.checkpoints(park);
+                }
                 A.src_xy = (const uint32_t *)src, A.src_n = (const uint64_t *)(src + Y.xy_bytes);
                 A.src_pix = (const uint32_t *)(src + Y.xy_bytes + Y.n_bytes);
                 A.dst_xy = (uint32_t *)dst, A.dst_n = (uint64_t *)(dst + Y.xy_bytes), A.dst_pix = (uint32_t *)(dst + Y.xy_bytes + Y.n_bytes);
                 if (cycle)
                     A.src_ck = Y.checkpoints(src), A.dst_ck = Y.checkpoints(dst);
                 A.slice = r->exact_slice ? r->exact_slice : exact_default_slice(limbs, A.n_src);
-                return fsk_exact_slice(A, limbs, samples, cycle, s);
+                return fsk_exact_slice(A, limbs, samples, cycle, keep, s);
             },
             [&](uint32_t left) {
-                A.first = 0;
+                A.first = 0, A.resume = 0;
                 if (compact)
                     A.n_src = left;
             },
             slices, after_first);
     unsigned long long st[4] = {0, 0, 0, 0};
+    uint32_t n_parked = 0;
     if (e == hipSuccess)
         e = hipMemcpyAsync(st, d_stats, sizeof st, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && keep)
+        e = hipMemcpyAsync(&n_parked, A.park_count, sizeof n_parked, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && cycle && keep_proved) {
         r->exact_proved.resize(npix);
         e = hipMemcpyAsync(r->exact_proved.data(), A.proved, npix, hipMemcpyDeviceToHost, s);
@@ -245,6 +336,13 @@ static uint32_t exact_frame(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, 
     r->exact_cycle_stats[0] += st[2], r->exact_cycle_stats[1] += st[3];
     if (cycle && keep_proved)
         r->exact_proved_valid = e == hipSuccess;
+    if (e == hipSuccess && keep) {
+        fs_renderer::ExactKept K = K0; // (a continuation: the set's own parameters)
+        K.wide = false, K.cycle = cycle, K.W = W, K.H = H, K.cap = n_iterations;
+        K.frac_bits = frac_bits, K.limbs = limbs, K.bailout = bailout, K.inclusive = inclusive ? 1 : 0;
+        K.proved = (resume ? K0.proved : 0) + st[2];
+        e = n_parked <= n_list ? exact_keep_install(r, Y, park, n_list, n_parked, A.cx, A.cy, A.proved, K) : hipErrorUnknown;
+    }
     (void)r_free(r, blk);
     return (uint32_t)e;
 }
@@ -261,7 +359,9 @@ uint32_t fs_render_exact(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits
     if (!exact_axis_in_range(cx, r->width, limbs, frac_bits) || !exact_axis_in_range(cy, r->height, limbs, frac_bits))
         return FS_ERR_UNSUPPORTED;
     exact_reset_stats(r);
-    return exact_frame(r, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations, r->iters(), 0, true);
+    exact_drop_kept(r);
+    return exact_frame(r, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations, r->iters(), 0, true,
+                       r->exact_keep ? kExactKeep : kExactPlain);
 }
 
 uint32_t fs_exact_stable_mask(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *const cx[3], const uint32_t *const cy[3],
@@ -346,17 +446,28 @@ struct WideJob {
 };
 
 // One device block per call: [counter, statistics | cx | cy | two lists of running samples]; synchronous.
-static uint32_t exact_wide_run(fs_renderer *r, const WideJob &J)
+// mode (frames only), as exact_frame's: kExactKeep parks the samples that meet the cap in the last slice's destination list and
+// leaves them as the kept set; kExactResume starts from the kept set (J.n = its samples; J.cx and J.cy are not read), whose list is
+// the second of the two lists, the call's block [counter, statistics | one list] the first.  *started as exact_frame's.
+static uint32_t exact_wide_run(fs_renderer *r, const WideJob &J, ExactMode mode = kExactPlain, bool *started = nullptr)
 {
+    if (started)
+        *started = false;
+    const bool keep = mode != kExactPlain, resume = mode == kExactResume;
+    const fs_renderer::ExactKept K0 = r->exact_kept;
     const uint32_t L = J.limbs, n = J.n;
     const ExactLayout Y(L, J.nx, J.ny, n);
     char *blk = nullptr;
     hipStream_t s = r->compute;
-    FS_TRY(r_alloc(r, (void **)&blk, Y.bytes(2), kFrame));
+    FS_TRY(r_alloc(r, (void **)&blk, resume ? Y.head + Y.list_bytes : Y.bytes(2), kFrame));
+    if (started)
+        *started = true;
     unsigned long long *d_stats = Y.stats(blk);
+    char *lists[2] = {resume ? blk + Y.head : Y.list(blk, 0), resume ? Y.list(K0.blk, 0) : Y.list(blk, 1)};
+    char *axes = resume ? K0.blk : blk, *park = nullptr;
 
     FsExactWideArgs A{};
-    A.cx = Y.cx(blk), A.cy = Y.cy(blk);
+    A.cx = Y.cx(axes), A.cy = Y.cy(axes);
     A.nx = J.nx, A.ny = J.ny, A.W = J.W;
     A.out = J.out, A.out_u64 = J.out_u64, A.out_pitch = J.out_pitch;
     A.cap = J.cap;
@@ -364,29 +475,31 @@ static uint32_t exact_wide_run(fs_renderer *r, const WideJob &J)
     // (the state call freezes a sample at the bound the limb count is derived for: |z|^2 > 256 2^2F)
     A.P = J.state_only ? fsx::make_params(J.frac_bits, fsx::kMaxBailout, 0) : fsx::make_params(J.frac_bits, J.bailout, J.inclusive);
     A.stride = n;
-    A.first = 1;
+    A.first = resume ? 0u : 1u;
     A.state_only = J.state_only ? 1u : 0u;
     A.dst_count = Y.count(blk);
+    A.park_count = Y.park_count(blk);
     A.stats = d_stats;
 
     uint32_t n_src = n;
     uint64_t slices = 0, after_first = 0;
     auto set_lists = [&](uint64_t k) {
-        char *src = Y.list(blk, (k & 1) ^ 1), *dst = Y.list(blk, k & 1);
+        char *src = lists[(k & 1) ^ 1], *dst = lists[k & 1];
+        park = dst;
         A.src_xy = (const uint32_t *)src, A.src_n = (const uint64_t *)(src + Y.xy_bytes);
         A.src_id = (const uint32_t *)(src + Y.xy_bytes + Y.n_bytes);
         A.dst_xy = (uint32_t *)dst, A.dst_n = (uint64_t *)(dst + Y.xy_bytes), A.dst_id = (uint32_t *)(dst + Y.xy_bytes + Y.n_bytes);
     };
     hipError_t e = hipMemsetAsync(blk, 0, Y.head, s);
-    if (e == hipSuccess)
+    if (e == hipSuccess && !resume)
         e = hipMemcpyAsync(Y.cx(blk), J.cx, (size_t)L * J.nx * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
+    if (e == hipSuccess && !resume)
         e = hipMemcpyAsync(Y.cy(blk), J.cy, (size_t)L * J.ny * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && J.state_only) {
         // one launch of exactly state_steps steps; every sample is written to list 0 at its own slot
         set_lists(0);
         A.slice = J.state_steps;
-        e = fsk_exact_wide_slice(A, n, s) ? hipGetLastError() : hipErrorInvalidValue;
+        e = fsk_exact_wide_slice(A, n, false, s) ? hipGetLastError() : hipErrorInvalidValue;
         if (e == hipSuccess)
             e = hipMemcpyAsync(J.state_x, Y.list(blk, 0), (size_t)L * n * 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess)
@@ -399,7 +512,7 @@ static uint32_t exact_wide_run(fs_renderer *r, const WideJob &J)
             [&](uint64_t k) {
                 set_lists(k);
                 A.slice = r->exact_slice ? r->exact_slice : wide_default_slice(L, n_src);
-                return fsk_exact_wide_slice(A, n_src, s);
+                return fsk_exact_wide_slice(A, n_src, keep, s);
             },
             [&](uint32_t left) {
                 A.first = 0;
@@ -408,11 +521,20 @@ static uint32_t exact_wide_run(fs_renderer *r, const WideJob &J)
             slices, after_first);
     }
     unsigned long long st = 0;
+    uint32_t n_parked = 0;
     if (e == hipSuccess)
         e = hipMemcpyAsync(&st, d_stats, sizeof st, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && keep)
+        e = hipMemcpyAsync(&n_parked, A.park_count, sizeof n_parked, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);
     r->exact_stats[0] += 64ull * st, r->exact_stats[1] += st, r->exact_stats[2] += slices, r->exact_stats[3] += after_first;
+    if (e == hipSuccess && keep) {
+        fs_renderer::ExactKept K{};
+        K.wide = true, K.cycle = false, K.W = J.nx, K.H = J.ny, K.cap = J.cap;
+        K.frac_bits = J.frac_bits, K.limbs = L, K.bailout = J.bailout, K.inclusive = J.inclusive ? 1 : 0;
+        e = n_parked <= n ? exact_keep_install(r, Y, park, n, n_parked, A.cx, A.cy, nullptr, K) : hipErrorUnknown;
+    }
     (void)r_free(r, blk);
     return (uint32_t)e;
 }
@@ -474,7 +596,94 @@ uint32_t fs_render_exact_wide(fs_renderer *r, uint32_t iter_bytes, uint32_t frac
     J.n = r->width * r->height;
     J.bailout = bailout, J.inclusive = inclusive, J.cap = n_iterations;
     J.out = r->iters(), J.out_u64 = r->iter_bytes == 8 ? 1u : 0u, J.out_pitch = r->w_block * 16u;
-    return exact_wide_run(r, J);
+    exact_drop_kept(r);
+    return exact_wide_run(r, J, r->exact_keep ? kExactKeep : kExactPlain);
+}
+
+// ---- fs_set_exact_keep / fs_render_exact_continue / fs_exact_kept_info / fs_exact_drop_kept
+uint32_t fs_set_exact_keep(fs_renderer *r, int enable)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    r->exact_keep = enable != 0;
+    return 0;
+}
+
+uint32_t fs_exact_kept_info(const fs_renderer *r, fs_exact_kept *out)
+{
+    if (!r || !out)
+        return hipErrorInvalidValue;
+    memset(out, 0, sizeof *out);
+    const fs_renderer::ExactKept &K = r->exact_kept;
+    if (!K.valid)
+        return 0;
+    out->samples = K.samples, out->proved = K.proved, out->cap = K.cap, out->device_bytes = K.bytes;
+    out->frac_bits = K.frac_bits, out->limbs = K.limbs, out->bailout = K.bailout, out->inclusive = (uint32_t)K.inclusive;
+    out->wide = K.wide ? 1u : 0u, out->cycle_check = K.cycle ? 1u : 0u, out->valid = 1u;
+    return 0;
+}
+
+uint32_t fs_exact_drop_kept(fs_renderer *r)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    if (uint32_t e = use_device(r))
+        return e;
+    exact_drop_kept(r);
+    return 0;
+}
+
+uint32_t fs_render_exact_continue(fs_renderer *r, uint64_t n_iterations)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    if (uint32_t e = use_device(r))
+        return e;
+    fs_renderer::ExactKept &K = r->exact_kept;
+    if (!K.valid || !r->memory_initialized() || !r->compute || K.W != r->width || K.H != r->height)
+        return FS_ERR_6;
+    if (n_iterations == ~0ull || n_iterations < K.cap || (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8))
+        return (uint32_t)hipErrorInvalidValue;
+    if (n_iterations == K.cap)
+        return 0;
+    exact_reset_stats(r);
+    const uint32_t npix = K.W * K.H;
+    if (K.samples == 0 && K.proved == 0) { // every pixel escaped: the frame of any cap, and with the check its all-zero mask
+        if (K.cycle)
+            r->exact_proved.assign(npix, 0);
+        r->exact_proved_valid = K.cycle;
+        K.cap = n_iterations;
+        return 0;
+    }
+    hipStream_t s = r->compute;
+    uint32_t rc = 0;
+    bool started = true; // (false: the call failed before it touched the frame or the set, which then stands)
+    if (K.samples != 0) {
+        if (K.wide) {
+            WideJob J{};
+            J.frac_bits = K.frac_bits, J.limbs = K.limbs, J.nx = K.W, J.ny = K.H, J.W = K.W, J.n = K.samples;
+            J.bailout = K.bailout, J.inclusive = K.inclusive, J.cap = n_iterations;
+            J.out = r->iters(), J.out_u64 = r->iter_bytes == 8 ? 1u : 0u, J.out_pitch = r->w_block * 16u;
+            rc = exact_wide_run(r, J, kExactResume, &started);
+        } else {
+            rc = exact_frame(r, 0, 0, nullptr, nullptr, 0, 0, n_iterations, r->iters(), 0, true, kExactResume, &started);
+        }
+    } else { // nothing to resume: the proved pixels take the new cap, the plane stands, the cap moves
+        const ExactLayout Y(K.limbs, K.W, K.H, K.samples, K.cycle, npix);
+        fsk_exact_set_proved(r->iters(), r->iter_bytes == 8, Y.proved(K.blk, 1), K.W, K.H, r->w_block * 16u, n_iterations, s);
+        rc = (uint32_t)hipGetLastError();
+        if (rc == 0) {
+            r->exact_proved.resize(npix);
+            rc = (uint32_t)hipMemcpyAsync(r->exact_proved.data(), Y.proved(K.blk, 1), npix, hipMemcpyDeviceToHost, s);
+        }
+        if (rc == 0)
+            rc = (uint32_t)hipStreamSynchronize(s);
+        r->exact_proved_valid = rc == 0;
+        K.cap = n_iterations;
+    }
+    if (rc != 0 && started)
+        exact_drop_kept(r);
+    return rc;
 }
 
 uint32_t fs_exact_wide_state(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,

@@ -98,6 +98,8 @@ static Begin render_begin(fs_renderer *r, bool type_ok, uint64_t n_iterations, u
         *rc = FS_ERR_UNSUPPORTED;
     else if (n_iterations > 0xFFFFFFFFull && r->iter_bytes != 8)
         *rc = (uint32_t)hipErrorInvalidValue; // a 4-byte IterType cannot hold such a count
+    if (*rc == 0u)
+        exact_drop_kept(r); // (the frame the exact renderer's kept set describes is about to be replaced)
     return *rc != 0u ? Begin::kRefused : Begin::kGo;
 }
 

@@ -190,6 +190,20 @@ struct fs_renderer {
     uint64_t exact_cycle_stats[2] = {}; // fs_read_exact_cycle_stats: samples finished by proof, checkpoints read back
     std::vector<uint8_t> exact_proved; // fs_read_exact_proved: the proved mask of the last fs_render_exact / fs_exact_audit ...
     bool exact_proved_valid = false; // ... when the last exact call ran with the check on
+    bool exact_keep = false;         // fs_set_exact_keep: the two exact renderers leave a kept set for fs_render_exact_continue
+    // The kept set: ONE live device block (no idle memory: r_alloc's, never r_free'd while it is valid) laid out as renderer_exact.cpp's
+    // ExactLayout(limbs, W, H, samples, cycle, W * H) with one list -- [head | cx | cy | the parked samples | proved plane] -- and
+    // what the call was given.  It describes the frame in the iteration buffer: whatever writes, clears or replaces that buffer
+    // drops it (fsr::exact_drop_kept).
+    struct ExactKept {
+        char *blk = nullptr;
+        size_t bytes = 0;
+        bool valid = false, wide = false, cycle = false;
+        uint32_t samples = 0, W = 0, H = 0;
+        uint64_t proved = 0, cap = 0;
+        uint32_t frac_bits = 0, limbs = 0, bailout = 0;
+        int inclusive = 0;
+    } exact_kept;
     uint32_t az_gather_rows = 0;     // fs_set_autozoom_gather_cap (tests): frame rows the FilamentTip gather buffer holds, 0 = default
     FsAzStats az_seed{};             // source of the stream-ordered seed copy in fs_autozoom_pick (must outlive the copy)
     bool inject_input_oom = false;   // fault injection: FSMI355_FAIL_INPUT_ALLOC=1 at fs_create time
@@ -265,6 +279,9 @@ hipError_t la_reserve(fs_renderer *r, size_t las_bytes, size_t stages_bytes); //
 // The orbit, the LA table and the BLA table go (fs_init_memory with a new geometry, fs_destroy).
 void free_perturb(fs_renderer *r);
 uint32_t bla_make_native(fs_renderer *r, int32_t n_levels); // (renderer_inputs.cpp)
+// The exact renderer's kept set goes (renderer_exact.cpp): called by whatever writes, clears or replaces the iteration buffer.
+// Nothing kept: nothing happens, not even a synchronisation.
+void exact_drop_kept(fs_renderer *r);
 
 struct TimedLaunch {
     fs_renderer *r;

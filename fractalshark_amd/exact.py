@@ -14,6 +14,9 @@ next to them, one small record back).
 prove_interior=True on render, stable_mask and audit switches the cycle check on for the call (fs_set_exact_cycle_check; DESIGN.md
 6.3 "Cycle check"): a sample whose state repeats exactly is proved never to escape and stops at once instead of running to the cap.
 No count changes; frames with an interior at a shallow or middle depth get cheaper.  The wide path has no such check.
+
+keep=True on render leaves the samples that reached the cap on the device (fs_set_exact_keep; DESIGN.md 6.3 "Continuation"), and
+continue_render raises the frame's cap from there instead of starting over; render_progressive is the chain cap after cap.
 """
 import numpy as np
 
@@ -69,23 +72,69 @@ def _proved(renderer, n=None):
     return mask.astype(bool)
 
 
-def render(renderer, view, bailout=4, frac_bits=None, iter_bytes=4, inclusive=False, prove_interior=False):
+class _keep:
+    """Keeping on or off for the duration of a call, and behind it what the caller had set with SetExactKeep (off if never)."""
+
+    def __init__(self, renderer, on):
+        self.renderer, self.on = renderer, bool(on)
+
+    def __enter__(self):
+        self.before = bool(getattr(self.renderer, "_exact_keep", False))
+        if self.on != self.before:
+            _check(self.renderer, self.renderer.SetExactKeep(self.on), "fs_set_exact_keep")
+
+    def __exit__(self, *exc):
+        if self.on != self.before:
+            self.renderer.SetExactKeep(self.before)
+
+
+def render(renderer, view, bailout=4, frac_bits=None, iter_bytes=4, inclusive=False, prove_interior=False, keep=False,
+           n_iterations=None):
     """The view's exact frame into the renderer's iteration buffer (InitializeMemory with the view's antialiased size and
     iter_bytes comes first), view.num_iterations the cap.  frac_bits defaults to view.precision_bits + 64.  Has the shape
     autozoom.zoom wants for its `render` argument.  Up to 24 limbs (758 bits) a lane holds a sample (fs_render_exact); beyond, a
     wave does (fs_render_exact_wide), up to 704 limbs.
     prove_interior: the cycle check is on for the call, and the result is bool[H, W], the samples it proved never to escape (they
-    hold the cap, like those that ran to it).  On the wide path the check stays off and the result is None, as without it."""
+    hold the cap, like those that ran to it).  On the wide path the check stays off and the result is None, as without it.
+    keep: the samples that reach the cap stay on the device for continue_render (renderer.ExactKept() describes them); without it
+    nothing is kept.  n_iterations: the cap, in place of view.num_iterations."""
     F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
     L = limbs_for(F)
     cx, cy = axes(view, F, limbs=L)
-    if uses_wide(L):
-        _check(renderer, renderer.RenderExactWide(iter_bytes, F, L, cx, cy, bailout, inclusive, view.num_iterations),
-               "fs_render_exact_wide")
-        return None
-    with _cycle_check(renderer, prove_interior):
-        _check(renderer, renderer.RenderExact(iter_bytes, F, L, cx, cy, bailout, inclusive, view.num_iterations), "fs_render_exact")
+    cap = view.num_iterations if n_iterations is None else int(n_iterations)
+    with _keep(renderer, keep):
+        if uses_wide(L):
+            _check(renderer, renderer.RenderExactWide(iter_bytes, F, L, cx, cy, bailout, inclusive, cap), "fs_render_exact_wide")
+            return None
+        with _cycle_check(renderer, prove_interior):
+            _check(renderer, renderer.RenderExact(iter_bytes, F, L, cx, cy, bailout, inclusive, cap), "fs_render_exact")
     return _proved(renderer).reshape(cy.shape[1], cx.shape[1]) if prove_interior else None
+
+
+def continue_render(renderer, n_iterations):
+    """The kept frame in the iteration buffer raised to the cap n_iterations (fs_render_exact_continue): afterwards the buffer is
+    what render writes with that cap, and the kept set is that cap's, so calls chain.  Path, number format, bailout and cycle check
+    are the kept set's; nothing is chosen here.  Returns what render returns: bool[H, W] of the proved samples when the kept render
+    ran with prove_interior, else None."""
+    _check(renderer, renderer.RenderExactContinue(n_iterations), "fs_render_exact_continue")
+    if not renderer.ExactKept()["cycle_check"]:
+        return None
+    return _proved(renderer).reshape(renderer.GetHeight(), renderer.GetWidth())
+
+
+def render_progressive(renderer, view, caps, bailout=4, frac_bits=None, iter_bytes=4, inclusive=False, prove_interior=False):
+    """A generator: the view's exact frame at every cap of `caps`, in ascending order, each step resuming the samples the one
+    before left at its cap.  Yields (cap, what render returns) with that cap's frame in the iteration buffer -- a valid frame for
+    RenderCurrent, autozoom and audit, equal to render's at that cap.  The kept set is dropped when the generator ends."""
+    caps = sorted(int(c) for c in caps)
+    try:
+        for k, cap in enumerate(caps):
+            if k == 0:
+                yield cap, render(renderer, view, bailout, frac_bits, iter_bytes, inclusive, prove_interior, keep=True, n_iterations=cap)
+            else:
+                yield cap, continue_render(renderer, cap)
+    finally:
+        renderer.DropExactKept()
 
 
 def uses_wide(limbs):
@@ -214,5 +263,6 @@ def stable_mask(renderer, view, level, bailout=4, frac_bits=None, prove_interior
     return mask.astype(bool)
 
 
-__all__ = ["GUARD_BITS", "MAX_FRAC_BITS", "MAX_WIDE_LIMBS", "MAX_WIDE_FRAC_BITS", "limbs_for", "axes", "render", "uses_wide",
+__all__ = ["GUARD_BITS", "MAX_FRAC_BITS", "MAX_WIDE_LIMBS", "MAX_WIDE_FRAC_BITS", "limbs_for", "axes", "render", "continue_render",
+           "render_progressive", "uses_wide",
            "sample_counts", "stable_mask", "lattice", "audit", "AuditReport"]

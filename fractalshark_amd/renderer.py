@@ -275,6 +275,30 @@ class GPURenderer:
         """Test hook (fs_set_exact_cycle_fingerprint_bits): low bits of the checkpoint's fingerprint, 0 = all 64."""
         return self._lib.fs_set_exact_cycle_fingerprint_bits(self._h, int(bits))
 
+    def SetExactKeep(self, enable):
+        """fs_set_exact_keep: RenderExact and RenderExactWide leave the samples that reach the cap on the device, for
+        RenderExactContinue; off by default."""
+        self._exact_keep = bool(enable)  # (the library has no getter; exact.render puts the caller's setting back)
+        return self._lib.fs_set_exact_keep(self._h, 1 if enable else 0)
+
+    def RenderExactContinue(self, n_iterations):
+        """fs_render_exact_continue: the kept frame in the iteration buffer raised to the cap n_iterations >= the kept one, byte for
+        byte what the original call writes with that cap; FS_ERR_6 when nothing valid is kept.  Synchronous."""
+        return self._lib.fs_render_exact_continue(self._h, int(n_iterations))
+
+    def ExactKept(self):
+        """fs_exact_kept_info: the kept set as a dict -- samples, proved, cap, device_bytes, frac_bits, limbs, bailout, inclusive, wide,
+        cycle_check, valid; all zero when nothing is kept."""
+        rec = _capi.ExactKept()
+        err = self._lib.fs_exact_kept_info(self._h, C.byref(rec))
+        if err:
+            raise RuntimeError("fs_exact_kept_info failed: %d (%s)" % (err, self.ConvertErrorToString(err)))
+        return {name: int(getattr(rec, name)) for name, _ in rec._fields_ if name != "reserved"}
+
+    def DropExactKept(self):
+        """fs_exact_drop_kept: frees the kept set."""
+        return self._lib.fs_exact_drop_kept(self._h)
+
     def _feature_eval(self, entry, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
         from . import features
         din, dout, dreal = features.records(T == T_HDR64)

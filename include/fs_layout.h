@@ -520,8 +520,24 @@ typedef struct fs_audit_result {
     fs_audit_offender offenders[FS_AUDIT_MAX_OFFENDERS]; /* the first differing samples in sample order */
 } fs_audit_result;
 
+/* ---- The exact renderer's kept set (fs_set_exact_keep, fs_exact_kept_info): what a continuation would resume.  All zero when
+ * nothing is kept. */
+typedef struct fs_exact_kept {
+    uint64_t samples;      /* samples that reached the cap without escaping and without a proof: their state is on the device */
+    uint64_t proved;       /* pixels finished by proof so far (cycle check on), the calls of the chain together */
+    uint64_t cap;          /* the n_iterations the frame in the iteration buffer was rendered to */
+    uint64_t device_bytes; /* device memory the set holds */
+    uint32_t frac_bits, limbs, bailout;
+    uint32_t inclusive;
+    uint32_t wide;         /* 1: kept by fs_render_exact_wide (a wave per sample), 0: by fs_render_exact */
+    uint32_t cycle_check;  /* 1: the call ran with the cycle check and the set holds the proved plane */
+    uint32_t valid;        /* 1: fs_render_exact_continue has something to continue from */
+    uint32_t reserved;
+} fs_exact_kept;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(fs_exact_kept) == 64, "exact kept record");
 static_assert(sizeof(fs_autozoom_result) == 200, "autozoom record");
 static_assert(sizeof(fs_audit_offender) == 24 && sizeof(fs_audit_result) == 568, "audit record");
 static_assert(sizeof(fs_feature_in_hdr32) == 32&& sizeof(fs_feature_in_hdr64) == 56 && sizeof(fs_feature_out_hdr32) == 64 &&

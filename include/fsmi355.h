@@ -375,6 +375,36 @@ uint32_t fs_exact_audit(fs_renderer *r, const void *device_iters, uint32_t frac_
 uint32_t fs_set_exact_cycle_check(fs_renderer *r, int enable);
 uint32_t fs_read_exact_proved(const fs_renderer *r, uint8_t *out, uint64_t n);
 
+/* Continuation: raise the cap of the exact frame in the iteration buffer without starting over (DESIGN.md 6.3 "Continuation").
+ * z_{n+1} is a function of z_n alone, so a sample's state at step N is the same whatever cap the call was given, and a larger cap
+ * is one more slice boundary.
+ * fs_set_exact_keep: enable = 1 makes fs_render_exact and fs_render_exact_wide leave a kept set on the device when they return:
+ * the state of every sample that reached the cap without escaping and without a proof, the proved plane (cycle check on), the two
+ * axes and the call's parameters.  The set is sized to the samples kept, not to W x H, and replaces any earlier one; it is no idle
+ * memory (fs_release_idle_device_memory leaves it).  A failed allocation while keeping is the call's error.  0, the default: no set
+ * is left and every call does exactly what it does without this function.  The switch is read by the two renderers only:
+ * switching it off neither frees a set that exists nor keeps fs_render_exact_continue from continuing it and keeping again.
+ * fs_render_exact_continue: resumes the kept samples up to n_iterations = N2 >= the kept cap N1, with the path, the parameters and
+ * the cycle-check setting recorded with the set (not the current switches).  Afterwards the iteration buffer is, byte for byte,
+ * what the original call with n_iterations = N2 writes from scratch -- the proved pixels are rewritten to N2 -- and the kept set
+ * is that of cap N2: calls chain.  fs_read_exact_proved returns the mask a fresh call at N2 would give; fs_read_exact_stats and
+ * fs_read_exact_cycle_stats report this call's work only (a resumed sample of the wide path repeats one escape test).  Synchronous
+ * on the compute stream; the orbit and LA caches, recorded tile costs and orders and the kernel-time history are left as they
+ * were.  N2 == N1: 0, nothing changes.  Nothing kept and nothing proved (every pixel escaped): 0 without a launch, N2 recorded.
+ * FS_ERR_6: no valid kept set.  hipErrorInvalidValue: N2 < N1, N2 == ~0, N2 > 2^32 - 1 on a 4-byte frame.  A continuation that
+ * fails on its first allocation, before it has touched the frame or the set, leaves both as they were; one that fails later drops
+ * the set.
+ * fs_exact_kept_info: *out (fs_layout.h) describes the kept set; zeroed, and 0 returned, when nothing is kept.
+ * fs_exact_drop_kept: frees the kept set.
+ * The set describes the frame in the iteration buffer, so whatever writes, clears or replaces that buffer drops it at call time:
+ * fs_init_memory, fs_clear, fs_set_row_bands, fs_set_external_iter_buffer, every fs_render_* into the buffer (the two exact ones
+ * replace it when keep is on and drop it when off) and fs_destroy.  fs_render_current, fs_colorize_frame, fs_autozoom_pick,
+ * fs_exact_audit, fs_exact_stable_mask, fs_exact_sample_counts, fs_feature_eval* and the stream calls leave it alone. */
+uint32_t fs_set_exact_keep(fs_renderer *r, int enable);
+uint32_t fs_render_exact_continue(fs_renderer *r, uint64_t n_iterations);
+uint32_t fs_exact_kept_info(const fs_renderer *r, fs_exact_kept *out);
+uint32_t fs_exact_drop_kept(fs_renderer *r);
+
 /* GPURenderer::ClearMemory<IterType> (GPU_Render.cu:212-225). */
 uint32_t fs_clear(fs_renderer *r);
 

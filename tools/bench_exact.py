@@ -25,11 +25,17 @@
             --cycle-limbs, as the on / off ratio of the time per step; (b) what it saves: View 0 at 1024 x 768 (R 4) with the check
             off and on at caps 8 192 and 100 000: call time, launches, steps and proved samples
 
+  continue  (--continue) the continuation (fs_set_exact_keep, fs_render_exact_continue; DESIGN.md 6.3 "Continuation"): View 0 at
+            1024 x 768 (R 4), caps 8 192 -> 100 000, with the cycle check off and on, in one run: the first call with keep on NEXT TO
+            the same call with keep off (what keeping costs: the park stores, the repack, the kept block); the continuation NEXT TO
+            a fresh call at the larger cap (the saving); samples kept, device bytes held, steps and launches of each.  The frame after
+            the continuation is asserted equal to the fresh one.  No gate.
+
 Times are host clocks around synchronous calls.  One JSON line per measurement.
 
   python tools/bench_exact.py [--pace] [--frames] [--view5] [--limbs 2,4,7,8,11,12,16,20,23,24]
                               [--wide] [--wide-limbs 25,64,80,128,160,320,683,704] [--view11] [--view14]
-                              [--cycle] [--cycle-limbs 2,4,8,12,16,24]
+                              [--cycle] [--cycle-limbs 2,4,8,12,16,24] [--continue]
 """
 import argparse
 import json
@@ -56,8 +62,9 @@ ap.add_argument("--view11", action="store_true")
 ap.add_argument("--view14", action="store_true")
 ap.add_argument("--cycle", action="store_true")
 ap.add_argument("--cycle-limbs", default="2,4,8,12,16,24")
+ap.add_argument("--continue", dest="cont", action="store_true")
 args = ap.parse_args()
-if not (args.pace or args.frames or args.view5 or args.wide or args.view11 or args.view14 or args.cycle):
+if not (args.pace or args.frames or args.view5 or args.wide or args.view11 or args.view14 or args.cycle or args.cont):
     args.pace = args.frames = True
 
 
@@ -157,6 +164,44 @@ if args.cycle:
         say(what="cycle frame", name="view0_1024x768", bailout=4, frac_bits=F, limbs=L, cap=cap,
             at_the_cap=int((frames[True][:c.h, :c.w] == cap).sum()), **row,
             time_off_over_on=round(row["off"]["seconds"] / row["on"]["seconds"], 2))
+
+if args.cont:
+    r.SetExactSlice(0)
+    c = _truth.Case("view0_1024x768")
+    v, F = c.view(inputs), c.raw["frac_bits"]
+    L = exact.limbs_for(F)
+    cx, cy = exact.axes(v, F, limbs=L)
+    assert r.InitializeMemory(c.w, c.h, 1, None, 0, 0, 0, False) == 0
+    n1, n2 = 8192, 100000
+
+    def grab(cap):
+        out = r.new_iter_buffer()
+        assert r.RenderCurrent(cap, out) == 0 and r.SyncComputeStream() == 0
+        return out
+
+    def work(dt):
+        st = r.exact_stats()
+        return dict(seconds=round(dt, 4), launches=st["launches"], lane_steps=st["lane_steps"], proved=r.exact_cycle_stats()[0])
+
+    for on in (False, True):
+        assert r.SetExactCycleCheck(on) == 0 and r.SetExactKeep(False) == 0
+        timed_render(r, F, L, cx, cy, 4, 64)  # (memory and code warm)
+        row = {"first_keep_off": work(timed_render(r, F, L, cx, cy, 4, n1))}
+        row["fresh_at_larger_cap"] = work(timed_render(r, F, L, cx, cy, 4, n2))
+        fresh = grab(n2)
+        assert r.SetExactKeep(True) == 0
+        row["first_keep_on"] = work(timed_render(r, F, L, cx, cy, 4, n1))
+        kept = r.ExactKept()
+        t0 = time.perf_counter()
+        err = r.RenderExactContinue(n2)
+        row["continuation"] = work(time.perf_counter() - t0)
+        assert err == 0 and grab(n2).tobytes() == fresh.tobytes()
+        assert r.SetExactKeep(False) == 0 and r.DropExactKept() == 0
+        say(what="continue", name="view0_1024x768", bailout=4, frac_bits=F, limbs=L, caps=[n1, n2], cycle_check=on,
+            kept_samples=kept["samples"], kept_proved=kept["proved"], kept_device_bytes=kept["device_bytes"], **row,
+            keep_on_over_keep_off_first_call=round(row["first_keep_on"]["seconds"] / row["first_keep_off"]["seconds"], 3),
+            fresh_over_continuation=round(row["fresh_at_larger_cap"]["seconds"] / row["continuation"]["seconds"], 2))
+    r.SetExactCycleCheck(False)
 
 r.SetExactSlice(0)
 
