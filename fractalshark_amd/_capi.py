@@ -146,6 +146,8 @@ def render_lib():
     _decl(lib, "fs_render_lav2", u32, [vp, C.c_int, C.c_int, C.c_int, vp, u64])
     _decl(lib, "fs_feature_eval", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
     _decl(lib, "fs_feature_eval_direct", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
+    _decl(lib, "fs_feature_eval_resident", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
+    _decl(lib, "fs_orbit_form", C.c_int, [vp])
     _decl(lib, "fs_set_feature_slice", u32, [vp, u32])
     _decl(lib, "fs_autozoom_pick", u32, [vp, C.c_int, u64, vp, C.POINTER(AutozoomResult)])
     _decl(lib, "fs_set_autozoom_gather_cap", u32, [vp, u32])
@@ -244,6 +246,7 @@ RENDER_SYMBOLS = [
     "fs_create", "fs_destroy", "fs_test_device_is_working", "fs_device_count", "fs_error_string", "fs_init_memory", "fs_set_row_bands",
     "fs_local_rows", "fs_set_external_iter_buffer", "fs_device_iter_buffer", "fs_rounded_width", "fs_upload_orbit", "fs_upload_orbit_compressed",
     "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_feature_eval", "fs_feature_eval_direct", "fs_set_feature_slice",
+    "fs_feature_eval_resident", "fs_orbit_form",
     "fs_autozoom_pick", "fs_set_autozoom_gather_cap",
     "fs_render_exact", "fs_exact_stable_mask", "fs_set_exact_slice", "fs_read_exact_stats",
     "fs_exact_sample_counts", "fs_render_exact_wide", "fs_exact_wide_state", "fs_exact_audit",

@@ -80,6 +80,17 @@ template <class F> struct FsFeatLane {
     uint64_t step, cap, period;
     uint32_t ref, phase;
 };
+// The same candidate on a waypoint-resident orbit (fs_feature_eval_resident, k_feature_step_seq): FsFeatLane with positions
+// as wide as the IterType (PosT) and the lane's decompression cursor -- the orbit value at `ref` (zx, zy), the number of the
+// first waypoint behind it and that waypoint's orbit index (SeqOrbit's state in seq_orbit.hpp; its idx is `ref`).
+template <class F, class PosT> struct FsFeatSeqLane {
+    fs::hcplx<F> z, dz, dzdc, zcoeff, dc, c;
+    fs::hreal<F> sqr_r, sqr_scale;
+    uint64_t step, cap, period;
+    fs::hreal<F> zx, zy;
+    PosT ref, next_index;
+    uint32_t next, phase;
+};
 // The Direct evaluator's candidate (kernels_feature_direct.hip, fs_feature_eval_direct): no orbit position, no dz, no
 // PeriodicityPP radius (phase 3 = Evaluate_FindPeriod_Direct, 1 = the fixed-period loop, 2 = finished and written out).
 template <class F> struct FsFeatDirectLane {
@@ -378,6 +389,16 @@ void fsk_feature_init(const void *in, FsFeatLane<F> *st, void *out, uint64_t n, 
 template <class F>
 void fsk_feature_step(const typename FsDev<F>::Z *zref, uint32_t count, FsFeatLane<F> *st, void *out, uint64_t n, int find,
                       int iter_u64, uint32_t slice, uint32_t *unfinished, hipStream_t s);
+// The same pair on a waypoint-resident orbit: wp / n_wp = the waypoints (fs_orbit_hdr32_rc / fs_orbit_hdr64_rc), c_low = the
+// decompressor's constant {OrbitXLow, OrbitYLow}, count = the uncompressed length; st = fsk_feature_seq_lane_bytes<F>(iter_u64)
+// bytes per candidate (FsFeatSeqLane<F, uint32_t | uint64_t>: positions are as wide as the IterType).
+template <class F> size_t fsk_feature_seq_lane_bytes(int iter_u64);
+template <class F>
+void fsk_feature_seq_init(const void *in, void *st, void *out, uint64_t n, int find, fs::hreal<F> R, uint64_t max_iters,
+                          uint64_t count, const void *wp, uint32_t n_wp, int iter_u64, hipStream_t s);
+template <class F>
+void fsk_feature_seq_step(const void *wp, uint32_t n_wp, const typename FsDev<F>::Real *c_low, uint64_t count, void *st,
+                          void *out, uint64_t n, int find, int iter_u64, uint32_t slice, uint32_t *unfinished, hipStream_t s);
 // The Direct evaluator (kernels_feature_direct.hip), same calling pattern; needs no orbit.
 template <class F>
 void fsk_feature_direct_init(const void *in, FsFeatDirectLane<F> *st, void *out, uint64_t n, int find, fs::hreal<F> R,

@@ -13,14 +13,16 @@ using namespace fsr;
 // second at the measured pace, whatever the iteration cap.
 static constexpr uint32_t kFeatureSlice = 1u << 18;
 
+// seq: the resident orbit is its waypoints (fs_feature_eval_resident); the lane records then carry a cursor each.
 template <class F>
 static uint32_t feature_eval(fs_renderer *r, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
-                             const void *in, void *out, uint64_t n)
+                             const void *in, void *out, uint64_t n, bool seq = false)
 {
     using In = typename FsFeatRec<F>::In;
     using Out = typename FsFeatRec<F>::Out;
     using Real = typename FsDev<F>::Real;
     const auto *zref = (const typename FsDev<F>::Z *)(sizeof(F) == 4 ? (const void *)r->zref : (const void *)r->zref64);
+    const auto *c_low = (const Real *)(sizeof(F) == 4 ? (const void *)r->c_low32 : (const void *)r->c_low64);
     if (iter_bytes == 4 && mode == FS_FEATURE_FIXED)
         for (uint64_t k = 0; k < n; k++)
             if (((const In *)in)[k].period > 0xFFFFFFFFull)
@@ -33,14 +35,18 @@ static uint32_t feature_eval(fs_renderer *r, uint32_t iter_bytes, int mode, cons
     if (e == hipSuccess)
         e = r_alloc(r, &d_out, n * sizeof(Out), kFrame);
     if (e == hipSuccess)
-        e = r_alloc(r, &d_st, n * sizeof(FsFeatLane<F>), kFrame);
+        e = r_alloc(r, &d_st, n * (seq ? fsk_feature_seq_lane_bytes<F>(iter_bytes == 8) : sizeof(FsFeatLane<F>)), kFrame);
     if (e == hipSuccess)
         e = r_alloc(r, &d_cnt, sizeof(uint32_t), kFrame);
     if (e == hipSuccess)
         e = hipMemcpyAsync(d_in, in, n * sizeof(In), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        fsk_feature_init<F>(d_in, (FsFeatLane<F> *)d_st, d_out, n, mode == FS_FEATURE_FIND, R, max_iters, r->orbit_uncompressed,
-                            s);
+        if (seq)
+            fsk_feature_seq_init<F>(d_in, d_st, d_out, n, mode == FS_FEATURE_FIND, R, max_iters, r->orbit_uncompressed, r->wp_raw,
+                                    (uint32_t)r->orbit_size, iter_bytes == 8, s);
+        else
+            fsk_feature_init<F>(d_in, (FsFeatLane<F> *)d_st, d_out, n, mode == FS_FEATURE_FIND, R, max_iters,
+                                r->orbit_uncompressed, s);
         e = hipGetLastError();
     }
     // slices until no candidate is left running; each ends in a synchronisation (a launch lasts a fraction of a second)
@@ -49,8 +55,13 @@ static uint32_t feature_eval(fs_renderer *r, uint32_t iter_bytes, int mode, cons
         e = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), s);
         if (e != hipSuccess)
             break;
-        fsk_feature_step<F>(zref, (uint32_t)r->orbit_uncompressed, (FsFeatLane<F> *)d_st, d_out, n, mode == FS_FEATURE_FIND,
-                            iter_bytes == 8, r->feature_slice ? r->feature_slice : kFeatureSlice, (uint32_t *)d_cnt, s);
+        const uint32_t slice = r->feature_slice ? r->feature_slice : kFeatureSlice;
+        if (seq)
+            fsk_feature_seq_step<F>(r->wp_raw, (uint32_t)r->orbit_size, c_low, r->orbit_uncompressed, d_st, d_out, n,
+                                    mode == FS_FEATURE_FIND, iter_bytes == 8, slice, (uint32_t *)d_cnt, s);
+        else
+            fsk_feature_step<F>(zref, (uint32_t)r->orbit_uncompressed, (FsFeatLane<F> *)d_st, d_out, n, mode == FS_FEATURE_FIND,
+                                iter_bytes == 8, slice, (uint32_t *)d_cnt, s);
         e = hipGetLastError();
         if (e == hipSuccess)
             e = hipMemcpyAsync(&left, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
@@ -146,6 +157,39 @@ uint32_t fs_feature_eval(fs_renderer *r, int type_tag, uint32_t iter_bytes, int 
         return hipErrorInvalidValue;
     return type_tag == FS_T_HDR32 ? feature_eval<float>(r, iter_bytes, mode, radius, max_iters, in, out, n)
                                   : feature_eval<double>(r, iter_bytes, mode, radius, max_iters, in, out, n);
+}
+
+int fs_orbit_form(const fs_renderer *r)
+{
+    return !r || !r->orbit_ok ? 0 : r->orbit_seq ? 2 : 1;
+}
+
+uint32_t fs_feature_eval_resident(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius,
+                                  uint64_t max_iters, const void *in, void *out, uint64_t n)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if ((type_tag != FS_T_HDR32 && type_tag != FS_T_HDR64) || (iter_bytes != 4 && iter_bytes != 8) ||
+        (mode != FS_FEATURE_FIND && mode != FS_FEATURE_FIXED))
+        return FS_ERR_UNSUPPORTED;
+    if (!r->compute || !r->orbit_ok || r->orbit_type != type_tag)
+        return FS_ERR_6;
+    const bool seq = r->orbit_seq;
+    if (seq) {
+        if (!r->wp_raw || r->orbit_size == 0)
+            return FS_ERR_6;
+        // positions are IterType-wide: 32-bit ones cannot walk an orbit of 2^32 entries and more
+        if (iter_bytes == 4 && r->orbit_uncompressed > 0xFFFFFFFFull)
+            return FS_ERR_UNSUPPORTED;
+    } else if ((type_tag == FS_T_HDR32 ? (const void *)r->zref : (const void *)r->zref64) == nullptr) {
+        return FS_ERR_6;
+    }
+    if (n == 0)
+        return 0;
+    if (!radius || !in || !out)
+        return hipErrorInvalidValue;
+    return type_tag == FS_T_HDR32 ? feature_eval<float>(r, iter_bytes, mode, radius, max_iters, in, out, n, seq)
+                                  : feature_eval<double>(r, iter_bytes, mode, radius, max_iters, in, out, n, seq);
 }
 
 uint32_t fs_feature_eval_direct(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,

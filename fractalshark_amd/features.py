@@ -4,7 +4,7 @@ The reference walks its 12 x 12 grid of screen points one after another and runs
 rounds and two final passes, every one a perturbation evaluation against the reference orbit on one CPU thread
 (FeatureFinderOrchestrator.cpp:535-559, FeatureFinder.cpp:2443-2697).  Here the host keeps the high-precision state of every
 candidate (libfsinputs: fsh_feature_*) and each round evaluates all candidates still running in one fs_feature_eval call, one
-GPU lane per candidate.
+GPU lane per candidate (fs_feature_eval_resident where only the orbit's waypoints are resident).
 
 The Direct / DirectScan modes (scan_direct, find_periodic_points_direct) are the same scan without a reference orbit, through
 fs_feature_eval_direct; period_map is their period search alone over a dense grid of the view.
@@ -81,16 +81,21 @@ def _run(lib, h, evaluate):
 
 def find_periodic_points(renderer, view, orbit, nx=12, ny=12, T=T_HDR32, iter_bytes=4, max_iters=None):
     """Periodic points near an nx x ny grid of the view's screen points (the reference's PTScan: 12 x 12), every evaluation on
-    the GPU.  `renderer` must hold `orbit` (InitializePerturb); T must be the orbit's type.  max_iters: the period search's cap
-    (default: the view's iteration limit).  Returns one dict per found point, in grid order: grid (row-major index), cx, cy
-    (decimal strings), period, residual2 (HDRFloat<double> as (mantissa, exponent)) and intrinsic_radius (decimal string)."""
+    the GPU.  `renderer` must hold `orbit` (InitializePerturb); T must be the orbit's type.  A SimpleCompression orbit may be
+    resident in either form: expanded, or as its waypoints only (renderer.orbit_form == 2, the one form an orbit of 2^32 and more
+    entries fits in), which fs_feature_eval_resident walks with a cursor per candidate -- the same records either way.  max_iters:
+    the period search's cap (default: the view's iteration limit).  Returns one dict per found point, in grid order: grid
+    (row-major index), cx, cy (decimal strings), period, residual2 (HDRFloat<double> as (mantissa, exponent)) and
+    intrinsic_radius (decimal string)."""
     if T not in (T_HDR32, T_HDR64) or (T == T_HDR64) != bool(orbit.is64):
         raise ValueError("T must be the orbit's type, T_HDR32 or T_HDR64")
+    waypoints = renderer.orbit_form == 2
+    entry, name = (renderer.FeatureEvalResident, "fs_feature_eval_resident") if waypoints else (renderer.FeatureEval, "fs_feature_eval")
 
     def evaluate(mode, radius, cap, rin, rout):
-        err = renderer.FeatureEval(T, iter_bytes, mode, radius, cap, rin, rout)
+        err = entry(T, iter_bytes, mode, radius, cap, rin, rout)
         if err:
-            raise RuntimeError("fs_feature_eval failed: %d (%s)" % (err, renderer.ConvertErrorToString(err)))
+            raise RuntimeError("%s failed: %d (%s)" % (name, err, renderer.ConvertErrorToString(err)))
 
     return scan(view, orbit, evaluate, nx, ny, iter_bytes, max_iters)
 

@@ -144,8 +144,16 @@ class GPURenderer:
         """fs_feature_eval: the Feature Finder's perturbation evaluator on the resident orbit (include/fsmi355.h).
         T = T_HDR32 / T_HDR64; mode = features.FIND / features.FIXED; radius = R as the raw bytes of an fs_real_hdr32 /
         fs_real_hdr64 (numpy record); records_in / records_out = numpy arrays of features.FEATURE_IN_* / FEATURE_OUT_* records
-        (the same length).  Synchronous."""
+        (the same length).  Synchronous.  Reads the EXPANDED orbit and refuses a waypoint-resident one (orbit_form == 2):
+        FeatureEvalResident serves both."""
         return self._feature_eval(self._lib.fs_feature_eval, T, iter_bytes, mode, radius, max_iters, records_in, records_out)
+
+    def FeatureEvalResident(self, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
+        """fs_feature_eval_resident: FeatureEval against the resident orbit in whichever form it is held (orbit_form) -- expanded:
+        the records FeatureEval returns; waypoints only (set_compressed_orbit_mode(True)): every candidate walks the orbit with a
+        decompression cursor of its own, positions as wide as iter_bytes.  The arguments of FeatureEval.  Synchronous."""
+        return self._feature_eval(self._lib.fs_feature_eval_resident, T, iter_bytes, mode, radius, max_iters, records_in,
+                                  records_out)
 
     def FeatureEvalDirect(self, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
         """fs_feature_eval_direct: the Feature Finder's Direct evaluator (include/fsmi355.h); the arguments of FeatureEval.  Needs
@@ -492,6 +500,11 @@ class GPURenderer:
     @property
     def orbit_device_bytes(self):
         return int(self._lib.fs_orbit_device_bytes(self._h))
+
+    @property
+    def orbit_form(self):
+        """How the resident orbit is held (fs_orbit_form): 0 = no orbit, 1 = expanded, 2 = waypoints only."""
+        return int(self._lib.fs_orbit_form(self._h))
 
     @property
     def host_fallback_bytes(self):

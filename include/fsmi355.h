@@ -181,11 +181,28 @@ uint32_t fs_upload_la(fs_renderer *r, uint64_t generation, int type_tag, uint32_
  * (4 or 8: the width periods are counted at).  Synchronous on the compute stream; n = 0 does nothing.  Frame state (iteration
  * buffer, recorded tile costs and orders, orbit / LA caches, kernel-time history) is left as it was.
  * FS_ERR_6: no orbit of this type resident.  FS_ERR_UNSUPPORTED: another type tag, iter_bytes or mode (FS_FEATURE_LA: the LA
- * evaluator is not built), or a waypoint-resident orbit (fs_set_compressed_orbit_mode(r, 1)). */
+ * evaluator is not built), or a waypoint-resident orbit (fs_set_compressed_orbit_mode(r, 1)): fs_feature_eval_resident serves
+ * that one. */
 enum { FS_FEATURE_FIND = 0, FS_FEATURE_FIXED = 1, FS_FEATURE_LA = 2 };
 enum { FS_FEATURE_REJECTED = 0, FS_FEATURE_OK = 1, FS_FEATURE_OK_DIRECT = 2 };
 uint32_t fs_feature_eval(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
                          const void *in, void *out, uint64_t n);
+/* fs_feature_eval against the resident orbit in whichever form it is held (fs_orbit_form): the reference's Feature Finder for
+ * PerturbExtras::SimpleCompression (FeatureFinder.cpp:2780-2795), whose Evaluate_PT walks the orbit through a RuntimeDecompressor
+ * (:1757-1771).  The arguments, records, modes and result codes of fs_feature_eval.
+ *   expanded orbit   the kernels of fs_feature_eval: the same records byte for byte;
+ *   waypoints only   (fs_set_compressed_orbit_mode(r, 1)) every candidate walks the orbit with a decompression cursor of its own
+ *                    (c = the OrbitXLow / OrbitYLow of the upload, count = the uncompressed size).  Both forms see the same
+ *                    orbit bit for bit, hence the same records.  Orbit positions are IterType-wide as the reference's are
+ *                    (Perturb.cuh:21-23, 202-203): iter_bytes = 8 serves an orbit of 2^32 entries and more.
+ * Synchronous on the compute stream; slices through fs_set_feature_slice; n = 0 returns 0; frame state is left as it was.
+ * FS_ERR_UNSUPPORTED: another type tag, iter_bytes or mode, or a waypoint-resident orbit of 2^32 entries and more with
+ * iter_bytes = 4.  FS_ERR_6: no orbit of this type resident.  hipErrorInvalidValue: a NULL argument, or a fixed period that a
+ * 4-byte IterType cannot hold.
+ * fs_orbit_form: 0 = no orbit resident, 1 = expanded, 2 = waypoints only. */
+uint32_t fs_feature_eval_resident(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius,
+                                  uint64_t max_iters, const void *in, void *out, uint64_t n);
+int fs_orbit_form(const fs_renderer *r);
 /* FeatureFinder::DirectEvaluator::Eval (FeatureFinder.cpp:2188-2211) for n candidates: FS_FEATURE_FIND = Evaluate_FindPeriod_Direct
  * (:1576-1660: the trigger |z|^2 < R^2 |dzdc|^2 with the fixed R of the call, cap max_iters), FS_FEATURE_FIXED =
  * Evaluate_PeriodResidualAndDzdc_Direct at each candidate's period; no fallback.  The records of fs_feature_eval: reads `c` and,
