@@ -522,7 +522,14 @@ void fsk_az_tip_score(const FsAzFrame &F, double max_dist, FsAzStats *st, hipStr
 void fsk_az_tip_gather(const FsAzFrame &F, double max_dist, uint32_t ya, uint32_t yb, FsAzStats *st, FsAzTipRec *out,
                        uint32_t cap, uint32_t *row_counts, hipStream_t s);
 
-// ---- exact renderer (kernels_exact.hip): one slice of a frame's fixed-point iteration
+// ---- exact renderer (kernels_exact.hip): one slice of a frame's fixed-point iteration.  The running samples live in lists between
+// slices; the wide renderer below has the same lists.
+struct FsExactList {
+    uint32_t *xy; // limb planes of x, then of y (stride slots each)
+    uint64_t *n;  // (lane kernels without compaction: 0 = finished)
+    uint32_t *id; // frame: pixel y * W + x; samples: the sample's index
+    uint32_t *ck; // the checkpoints of the cycle check, 2L more limb planes (tx, then ty); null when the list carries none
+};
 struct FsExactArgs {
     const uint32_t *cx, *cy; // limb-major axes: cx[l * W + column], cy[l * H + row]
     uint32_t W, H, rounded_width;
@@ -530,32 +537,22 @@ struct FsExactArgs {
     void *iters;             // the frame the finished samples write their counts to
     uint64_t cap;            // N
     fsx::Params P;
-    // running samples: limb planes of x, then of y (stride slots each), n (0 = finished, only without compaction) and pixel
-    const uint32_t *src_xy;
-    const uint64_t *src_n;
-    const uint32_t *src_pix;
-    uint32_t *dst_xy;
-    uint64_t *dst_n;
-    uint32_t *dst_pix;
-    uint32_t stride;
+    FsExactList src, dst;    // (ck: read by the C = true kernels only)
+    uint32_t stride;         // slots of a list
     uint32_t n_src;          // slots of the source list (first slice: W * H, and the lists are not read)
     uint32_t first;
     uint32_t compact;        // 0: every sample keeps its slot and dst == src (A/B of the compaction)
     uint32_t slice;          // steps per lane at most
     uint32_t *dst_count;     // += samples still running
     unsigned long long *stats; // [0] += lane slots occupied in the step loop, [1] += steps taken
-    // the cycle check (read by the C = true kernels only; exact_cycle_math.hpp): the checkpoints of the running samples, 2L more
-    // limb planes per list (tx, then ty); stats[2] += samples finished by proof, stats[3] += checkpoints read back
-    uint32_t *src_ck, *dst_ck;
+    // the cycle check (read by the C = true kernels only; exact_cycle_math.hpp): stats[2] += samples finished by proof,
+    // stats[3] += checkpoints read back
     uint8_t *proved;         // [W * H] (samples: [W]): 1 where the sample was proved; zeroed by the caller
     uint32_t fp_mx, fp_my;   // the fingerprint masks on x[0] and y[0]
     // keeping (read by the K = true kernels only; fs_set_exact_keep): a sample that stops at n == cap + 1 unproved is parked -- its
     // state, n and pixel, with the cycle check its checkpoint -- in a list no survivor is written to in that slice, at a slot
     // counted by park_count; resume: the list's samples are parked ones and make the step's deferred n++ and cycle check first
-    uint32_t *park_xy;
-    uint64_t *park_n;
-    uint32_t *park_pix;
-    uint32_t *park_ck;
+    FsExactList park;
     uint32_t *park_count;
     uint32_t resume;
 };
@@ -581,14 +578,8 @@ struct FsExactWideArgs {
     uint64_t cap;            // N
     uint32_t limbs;          // L, 2 .. 64 M
     fsx::Params P;
-    // running samples: limb planes of x, then of y (stride slots each), n and the sample's id
-    const uint32_t *src_xy;
-    const uint64_t *src_n;
-    const uint32_t *src_id;
-    uint32_t *dst_xy;
-    uint64_t *dst_n;
-    uint32_t *dst_id;
-    uint32_t stride;
+    FsExactList src, dst;    // (ck: null, the wide kernels have no cycle check)
+    uint32_t stride;         // slots of a list
     uint32_t first;          // the samples start at z_1 = c and slot = id; the source list is not read
     uint32_t state_only;     // fs_exact_wide_state: no count is written, every sample goes to dst slot = its source slot
     uint32_t slice;          // steps at most

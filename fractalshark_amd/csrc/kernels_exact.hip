@@ -2,9 +2,10 @@
 // no reference orbit and no rounding anywhere (exact_math.hpp holds the arithmetic and the limb bound).
 //
 // A frame advances in slices of at most `slice` steps per lane.  Between slices the running samples live in device memory as
-// (x, y, n, pixel), limb-major: plane l of a list holds limb l of every slot, so a wave's loads and stores are contiguous.  A
-// slice reads list A and writes the samples that are still running to list B: a ballot and a prefix count inside the wave, ONE
-// atomic add per wave for the wave's block of slots.  The next slice then runs full waves instead of one slow lane per wave.
+// (x, y, n, pixel) -- an FsExactList of kernels.h -- limb-major: plane l of a list holds limb l of every slot, so a wave's loads
+// and stores are contiguous.  A slice reads list A and writes the samples that are still running to list B: a ballot and a prefix
+// count inside the wave, ONE atomic add per wave for the wave's block of slots.  The next slice then runs full waves instead of one
+// slow lane per wave.
 // A sample that finishes writes its count into the frame at once.  c never changes: the lanes read their column's cx and their
 // row's cy (limb-major arrays of the whole axes) at the start of every slice.
 //
@@ -35,6 +36,15 @@
 
 namespace {
 
+// a finished sample's count goes to the frame (sample mode: to counts[e])
+template <bool S> __device__ __forceinline__ void write_count(const FsExactArgs &A, size_t out_idx, uint64_t v)
+{
+    if (S || A.iter_u64)
+        ((uint64_t *)A.iters)[out_idx] = v;
+    else
+        ((uint32_t *)A.iters)[out_idx] = (uint32_t)v;
+}
+
 template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
 {
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
@@ -43,8 +53,8 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
     uint64_t n = 1;
     uint32_t pix = slot;
     if (!A.first) {
-        n = A.src_n[slot];
-        pix = A.src_pix[slot];
+        n = A.src.n[slot];
+        pix = A.src.id[slot];
         alive = alive && n != 0; // (without compaction a finished sample keeps its slot, marked n = 0)
     }
     if (__ballot(alive) == 0)
@@ -63,8 +73,8 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
     } else {
 #pragma unroll
         for (int l = 0; l < L; l++) {
-            x[l] = A.src_xy[(size_t)l * A.stride + slot];
-            y[l] = A.src_xy[(size_t)(L + l) * A.stride + slot];
+            x[l] = A.src.xy[(size_t)l * A.stride + slot];
+            y[l] = A.src.xy[(size_t)(L + l) * A.stride + slot];
         }
     }
 
@@ -73,9 +83,9 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
     if constexpr (C) {
         if (A.first) {
             if (alive)
-                fsx::cycle_take<L>(x, y, A.src_ck, A.stride, i, fx, fy);
+                fsx::cycle_take<L>(x, y, A.src.ck, A.stride, i, fx, fy);
         } else {
-            fx = A.src_ck[slot], fy = A.src_ck[(size_t)L * A.stride + slot];
+            fx = A.src.ck[slot], fy = A.src.ck[(size_t)L * A.stride + slot];
         }
     }
 
@@ -84,11 +94,8 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
     bool parked = false;
     if constexpr (K) {
         if (A.resume && alive) {
-            if (fsx::cycle_resume<L, C>(x, y, n, A.src_ck, A.stride, i, fx, fy, A.fp_mx, A.fp_my, my_compares)) {
-                if (A.iter_u64)
-                    ((uint64_t *)A.iters)[out_idx] = A.cap;
-                else
-                    ((uint32_t *)A.iters)[out_idx] = (uint32_t)A.cap;
+            if (fsx::cycle_resume<L, C>(x, y, n, A.src.ck, A.stride, i, fx, fy, A.fp_mx, A.fp_my, my_compares)) {
+                write_count<S>(A, out_idx, A.cap);
                 A.proved[pix] = 1;
                 my_proved = 1;
                 alive = false;
@@ -103,22 +110,15 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
             my_steps++;
             const bool escaped = fsx::step<L>(x, y, cx, cy, A.P);
             if (escaped || n == A.cap + 1) {
-                const uint64_t v = escaped ? n - 1 : A.cap;
-                if (S || A.iter_u64)
-                    ((uint64_t *)A.iters)[out_idx] = v;
-                else
-                    ((uint32_t *)A.iters)[out_idx] = (uint32_t)v;
+                write_count<S>(A, out_idx, escaped ? n - 1 : A.cap);
                 alive = false;
                 if constexpr (K)
                     parked = !escaped;
             } else {
                 n++;
                 if constexpr (C) {
-                    if (fsx::cycle_check<L>(x, y, n, A.src_ck, A.stride, i, fx, fy, A.fp_mx, A.fp_my, my_compares)) {
-                        if (S || A.iter_u64)
-                            ((uint64_t *)A.iters)[out_idx] = A.cap;
-                        else
-                            ((uint32_t *)A.iters)[out_idx] = (uint32_t)A.cap;
+                    if (fsx::cycle_check<L>(x, y, n, A.src.ck, A.stride, i, fx, fy, A.fp_mx, A.fp_my, my_compares)) {
+                        write_count<S>(A, out_idx, A.cap);
                         uint32_t p = pix;
                         FSX_PIN(p); // (the address is made here, not kept across the loop)
                         A.proved[p] = 1;
@@ -146,21 +146,21 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
     if (alive) {
 #pragma unroll
         for (int l = 0; l < L; l++) {
-            A.dst_xy[(size_t)l * A.stride + dst] = x[l];
-            A.dst_xy[(size_t)(L + l) * A.stride + dst] = y[l];
+            A.dst.xy[(size_t)l * A.stride + dst] = x[l];
+            A.dst.xy[(size_t)(L + l) * A.stride + dst] = y[l];
         }
-        A.dst_n[dst] = n;
-        A.dst_pix[dst] = pix;
+        A.dst.n[dst] = n;
+        A.dst.id[dst] = pix;
         if constexpr (C) {
             if (A.compact) { // (without compaction source and destination are one list and dst == slot)
 #pragma unroll
                 for (int l = 0; l < 2 * L; l++)
-                    A.dst_ck[(size_t)l * A.stride + dst] = A.src_ck[(size_t)l * A.stride + i];
+                    A.dst.ck[(size_t)l * A.stride + dst] = A.src.ck[(size_t)l * A.stride + i];
             }
         }
     } else if (!A.compact && i < A.n_src) {
-        A.dst_n[dst] = 0;
-        A.dst_pix[dst] = 0;
+        A.dst.n[dst] = 0;
+        A.dst.id[dst] = 0;
     }
 
     // the samples that met the cap go to the park list
@@ -175,15 +175,15 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
             if (parked) {
 #pragma unroll
                 for (int l = 0; l < L; l++) {
-                    A.park_xy[(size_t)l * A.stride + ps] = x[l];
-                    A.park_xy[(size_t)(L + l) * A.stride + ps] = y[l];
+                    A.park.xy[(size_t)l * A.stride + ps] = x[l];
+                    A.park.xy[(size_t)(L + l) * A.stride + ps] = y[l];
                 }
-                A.park_n[ps] = n;
-                A.park_pix[ps] = pix;
+                A.park.n[ps] = n;
+                A.park.id[ps] = pix;
                 if constexpr (C) {
 #pragma unroll
                     for (int l = 0; l < 2 * L; l++)
-                        A.park_ck[(size_t)l * A.stride + ps] = A.src_ck[(size_t)l * A.stride + i];
+                        A.park.ck[(size_t)l * A.stride + ps] = A.src.ck[(size_t)l * A.stride + i];
                 }
             }
         }

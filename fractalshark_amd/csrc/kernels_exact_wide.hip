@@ -20,9 +20,9 @@
 //             funnel-shifts them by r.
 //   escape    every lane compares its two blocks with the bailout value's; four ballots and the highest differing block decide.
 //
-// Slices as in kernels_exact.hip: a launch takes at most `slice` steps; a sample still running is written to the destination
-// list (limb-major: plane l holds limb l of every slot) at a slot taken from one atomic add, so the next launch has exactly one
-// wave per running sample.
+// Slices as in kernels_exact.hip, with its lists (FsExactList of kernels.h, no checkpoints): a launch takes at most `slice` steps;
+// a sample still running is written to the destination list (limb-major: plane l holds limb l of every slot) at a slot taken from
+// one atomic add, so the next launch has exactly one wave per running sample.
 //
 // Keeping (K = true; fs_set_exact_keep): a sample that stops at n == cap + 1 is parked.  The kernel breaks BEFORE it steps, so the
 // parked state is z_{cap+1} with n = cap + 1 -- a running sample's, and it resumes as one: the escape test on z_{cap+1} is made
@@ -192,8 +192,8 @@ template <int M, bool K> __global__ void __launch_bounds__(64) k_exact_wide_slic
     uint64_t n = 1;
     uint32_t id = slot;
     if (!A.first) {
-        n = A.src_n[slot];
-        id = A.src_id[slot];
+        n = A.src.n[slot];
+        id = A.src.id[slot];
     }
     const uint32_t ix = A.W ? id % A.W : id, iy = A.W ? id / A.W : id;
     uint32_t x[M], y[M], cx[M], cy[M];
@@ -204,8 +204,8 @@ template <int M, bool K> __global__ void __launch_bounds__(64) k_exact_wide_slic
         for (int i = 0; i < M; i++)
             x[i] = cx[i], y[i] = cy[i];
     } else {
-        load_blocks<M>(A.src_xy, A.stride, slot, L, lane, x);
-        load_blocks<M>(A.src_xy + (size_t)L * A.stride, A.stride, slot, L, lane, y);
+        load_blocks<M>(A.src.xy, A.stride, slot, L, lane, x);
+        load_blocks<M>(A.src.xy + (size_t)L * A.stride, A.stride, slot, L, lane, y);
     }
 
     bool running = true, parked = false;
@@ -272,13 +272,13 @@ template <int M, bool K> __global__ void __launch_bounds__(64) k_exact_wide_slic
         for (int i = 0; i < M; i++) {
             const uint32_t g = lane * M + i;
             if (g < L) {
-                A.dst_xy[(size_t)g * A.stride + dst] = x[i];
-                A.dst_xy[(size_t)(L + g) * A.stride + dst] = y[i];
+                A.dst.xy[(size_t)g * A.stride + dst] = x[i];
+                A.dst.xy[(size_t)(L + g) * A.stride + dst] = y[i];
             }
         }
         if (lane == 0) {
-            A.dst_n[dst] = n;
-            A.dst_id[dst] = id;
+            A.dst.n[dst] = n;
+            A.dst.id[dst] = id;
         }
     }
     if (lane == 0 && steps != 0)

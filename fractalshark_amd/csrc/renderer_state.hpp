@@ -26,6 +26,8 @@ struct DevBuf {
     template <class T> T *as() const { return (T *)p; }
 };
 
+struct ExactLayout; // (renderer_exact.cpp) the device block of one exact call
+
 struct fs_renderer {
     int device = 0;
     hipStream_t compute = nullptr;
@@ -182,28 +184,41 @@ struct fs_renderer {
     std::mutex kept_mu; // kept_blocks only: another renderer of the same device may drain them when IT runs out of memory
     size_t host_alloc_bytes = 0;
     uint32_t feature_slice = 0;      // fs_set_feature_slice (tests): steps per launch of the Feature Finder evaluators, 0 = default
-    uint32_t exact_slice = 0;        // fs_set_exact_slice (tests, tools): steps per lane per launch of the exact renderer, 0 = default
-    bool exact_no_compaction = false; // ... and its A/B switch: every sample keeps its slot from slice to slice
-    uint64_t exact_stats[4] = {};    // fs_read_exact_stats: what the last exact frame did
-    bool exact_cycle_check = false;  // fs_set_exact_cycle_check: the lane-per-sample kernels prove non-escape by a repeat of the state
-    uint32_t exact_cycle_fp_bits = 0; // fs_set_exact_cycle_fingerprint_bits (tests): low bits the fingerprint keeps, 0 = all 64
-    uint64_t exact_cycle_stats[2] = {}; // fs_read_exact_cycle_stats: samples finished by proof, checkpoints read back
-    std::vector<uint8_t> exact_proved; // fs_read_exact_proved: the proved mask of the last fs_render_exact / fs_exact_audit ...
-    bool exact_proved_valid = false; // ... when the last exact call ran with the check on
-    bool exact_keep = false;         // fs_set_exact_keep: the two exact renderers leave a kept set for fs_render_exact_continue
-    // The kept set: ONE live device block (no idle memory: r_alloc's, never r_free'd while it is valid) laid out as renderer_exact.cpp's
-    // ExactLayout(limbs, W, H, samples, cycle, W * H) with one list -- [head | cx | cy | the parked samples | proved plane] -- and
-    // what the call was given.  It describes the frame in the iteration buffer: whatever writes, clears or replaces that buffer
-    // drops it (fsr::exact_drop_kept).
+    // The exact renderer's kept set: ONE live device block (no idle memory: r_alloc's, never r_free'd while it is valid) with one
+    // list -- [head | cx | cy | the parked samples | proved plane], the ExactLayout that layout() returns -- and what the call was
+    // given.  It describes the frame in the iteration buffer: whatever writes, clears or replaces that buffer drops it
+    // (fsr::exact_drop_kept).
     struct ExactKept {
         char *blk = nullptr;
-        size_t bytes = 0;
         bool valid = false, wide = false, cycle = false;
         uint32_t samples = 0, W = 0, H = 0;
         uint64_t proved = 0, cap = 0;
         uint32_t frac_bits = 0, limbs = 0, bailout = 0;
         int inclusive = 0;
-    } exact_kept;
+        ExactLayout layout() const; // (renderer_exact.cpp) the one place that says how blk is laid out
+    };
+    // What the exact renderers keep between calls; renderer_exact.cpp alone reads and writes it.
+    struct Exact {
+        uint32_t slice = 0;          // fs_set_exact_slice (tests, tools): steps per lane per launch of the exact renderer, 0 = default
+        bool no_compaction = false;  // ... and its A/B switch: every sample keeps its slot from slice to slice
+        uint64_t stats[4] = {};      // fs_read_exact_stats: what the last exact frame did
+        bool cycle_check = false;    // fs_set_exact_cycle_check: the lane-per-sample kernels prove non-escape by a repeat of the state
+        uint32_t cycle_fp_bits = 0;  // fs_set_exact_cycle_fingerprint_bits (tests): low bits the fingerprint keeps, 0 = all 64
+        uint64_t cycle_stats[2] = {}; // fs_read_exact_cycle_stats: samples finished by proof, checkpoints read back
+        std::vector<uint8_t> proved; // fs_read_exact_proved: the proved mask of the last fs_render_exact / fs_exact_audit ...
+        bool proved_valid = false;   // ... when the last exact call ran with the check on
+        bool keep = false;           // fs_set_exact_keep: the two exact renderers leave a kept set for fs_render_exact_continue
+        ExactKept kept;
+        // What every exact entry point does to the statistics before it starts.  keep_proved: the call leaves the mask of
+        // fs_read_exact_proved as it is (the shifted frames of fs_exact_stable_mask with the check on).
+        void reset_stats(bool keep_proved = false)
+        {
+            memset(stats, 0, sizeof stats);
+            memset(cycle_stats, 0, sizeof cycle_stats);
+            if (!keep_proved)
+                proved_valid = false;
+        }
+    } exact;
     uint32_t az_gather_rows = 0;     // fs_set_autozoom_gather_cap (tests): frame rows the FilamentTip gather buffer holds, 0 = default
     FsAzStats az_seed{};             // source of the stream-ordered seed copy in fs_autozoom_pick (must outlive the copy)
     bool inject_input_oom = false;   // fault injection: FSMI355_FAIL_INPUT_ALLOC=1 at fs_create time

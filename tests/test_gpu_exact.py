@@ -1,6 +1,8 @@
 """The exact renderer (fs_render_exact, fs_exact_stable_mask; fractalshark_amd.exact) on the GPU against GMP integer iteration of
 the same recurrence (tests/_truth.py, run live) and the exact-count fixture: equality on EVERY compared sample, stable or not --
 nothing in this path is rounded, so there is no stability level to choose and no sample to leave out."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -199,6 +201,7 @@ def test_error_returns(renderer):
     cx, cy = np.zeros((7, 64), np.uint32), np.zeros((7, 36), np.uint32)
     try:
         assert fresh._lib.fs_render_exact(fresh._h, 4, 187, 7, cx.ctypes.data, cy.ctypes.data, 4, 0, 100) == FS_ERR_6
+        assert fresh._lib.fs_render_exact(fresh._h, 4, 187, 6, cx.ctypes.data, cy.ctypes.data, 4, 0, 100) == FS_ERR_6  # no frame, bad limbs
     finally:
         fresh.close()
     r = renderer
@@ -216,6 +219,18 @@ def test_error_returns(renderer):
     far = cx.copy()
     far[:, 3] = [(32 << 187 >> (32 * l)) & 0xFFFFFFFF for l in range(7)]  # c = 32
     assert call(x=far) == FS_ERR_UNSUPPORTED
+    # two faults at once: the first refusal in the header's order decides
+    assert call(ib=2, n=1 << 32) == HIP_INVALID_VALUE   # the cap comes before iter_bytes (fs_render_exact_wide: after it)
+    assert r._lib.fs_render_exact(r._h, 2, 187, 7, None, cy.ctypes.data, 4, 0, 100) == FS_ERR_UNSUPPORTED  # iter_bytes before a NULL axis
+    assert call(L=6, n=1 << 32) == FS_ERR_UNSUPPORTED   # the format before the cap
+    assert call(ib=8, x=far) == HIP_INVALID_VALUE       # the frame's iter_bytes before the axis range
+    ptrs = lambda a3: (C.c_void_p * 3)(*[a.ctypes.data if a is not None else None for a in a3])
+    mask = np.zeros((36, 64), np.uint8)
+    stable = lambda x3, y3, R=4, n=100: r._lib.fs_exact_stable_mask(r._h, 187, 7, ptrs(x3), ptrs(y3), R, n, mask.ctypes.data)
+    zx, zy = np.zeros((7, 64), np.uint32), np.zeros((7, 36), np.uint32)
+    assert stable([zx, zx, zx], [zy, zy, zy]) == 0
+    assert stable([zx, None, zx], [zy, zy, zy], R=300) == FS_ERR_UNSUPPORTED  # the format before a NULL axis
+    assert stable([far, zx, zx], [zy, zy, zy], n=1 << 32) == HIP_INVALID_VALUE  # the cap before the axis range
     far[:, 3] = [((-32 << 187) >> (32 * l)) & 0xFFFFFFFF for l in range(7)]  # c = -32 is inside
     assert call(x=far) == 0
     far[:, 3] = [(((-32 << 187) - 1) >> (32 * l)) & 0xFFFFFFFF for l in range(7)]
@@ -226,6 +241,7 @@ def test_error_returns(renderer):
     assert r.SetRowBands(0, 8, 16) == 0
     try:
         assert call() == FS_ERR_UNSUPPORTED
+        assert call(n=1 << 32) == FS_ERR_UNSUPPORTED    # row bands before the cap
         assert r.ExactStableMask(187, 7, cx3, cy3, 4, 100)[0] == FS_ERR_UNSUPPORTED
     finally:
         assert r.SetRowBands(0, 0, 0) == 0

@@ -231,10 +231,17 @@ def test_error_returns(renderer):
     far = cxr.copy()
     far[3, :, 2] = _limbs_of(32 << F, L)                                          # c = 32 in one run
     assert call(r, cx=far) == FS_ERR_UNSUPPORTED and call(r, cy=far) == FS_ERR_UNSUPPORTED
+    # two faults at once: the first refusal in the header's order decides
+    assert call(r, k=9, out=None) == FS_ERR_UNSUPPORTED                            # the levels before a NULL record
+    assert call(r, n=0, out=None) == HIP_INVALID_VALUE                             # a NULL record before "no samples"
+    assert call(r, xs=np.array([0, 1, 64, 3, 4], np.uint32), cx=far) == HIP_INVALID_VALUE  # a sample outside the frame before the axis range
+    assert call(r, L=6, cap=1 << 32) == FS_ERR_UNSUPPORTED                         # the format before the cap
     far[3, :, 2] = _limbs_of(-32 << F, L)                                         # c = -32 is inside
     assert call(r, cx=far) == 0
     res.n_samples = 77
     assert call(r, n=0) == 0 and bytes(res) == bytes(C.sizeof(res))                # no samples: a zeroed record
+    res.n_samples = 77
+    assert call(r, n=0, xs=None) == 0 and bytes(res) == bytes(C.sizeof(res))       # ... before the NULL arrays
     assert r.SetRowBands(0, 8, 16) == 0
     try:
         assert call(r) == FS_ERR_UNSUPPORTED

@@ -261,6 +261,7 @@ def test_error_returns(renderer):
         err, out = fresh.ExactSampleCounts(2550, 80, z(80, 3), z(80, 3), 4, False, 50)  # no InitializeMemory needed
         assert err == 0 and out.tolist() == [50, 50, 50]
         assert fresh._lib.fs_render_exact_wide(fresh._h, 4, 2550, 80, z(80, 64).ctypes.data, z(80, 36).ctypes.data, 4, 0, 100) == FS_ERR_6
+        assert fresh._lib.fs_render_exact_wide(fresh._h, 4, 2550, 79, z(79, 64).ctypes.data, z(79, 36).ctypes.data, 4, 0, 100) == FS_ERR_6  # no frame, bad limbs
     finally:
         fresh.close()
 
@@ -284,6 +285,14 @@ def test_error_returns(renderer):
     far[:, 3] = limbs_of((-32 << 2550) - 1)
     assert counts(x=far) == FS_ERR_UNSUPPORTED
     assert r.ExactWideState(2550, 79, z(79, 4), z(79, 4), 1)[0] == FS_ERR_UNSUPPORTED
+    # two faults at once: the first refusal in the header's order decides
+    raw = lambda L=80, n_samples=4, cap=100, x=None, y=None, out=None: r._lib.fs_exact_sample_counts(r._h, 2550, L, x, y, n_samples, 4, 0, cap, out)
+    zero4, out4 = z(80, 4), np.zeros(4, np.uint64)
+    far[:, 3] = limbs_of(32 << 2550)
+    assert counts(L=79, n=(1 << 64) - 1) == FS_ERR_UNSUPPORTED                       # the format before the cap
+    assert raw(n_samples=0, cap=(1 << 64) - 1, x=zero4.ctypes.data, y=zero4.ctypes.data, out=out4.ctypes.data) == HIP_INVALID_VALUE  # the cap before "no samples"
+    assert raw(n_samples=0) == 0                                                     # "no samples" before the NULL arrays
+    assert raw(x=far.ctypes.data, y=zero4.ctypes.data, out=None) == HIP_INVALID_VALUE  # a NULL array before the axis range
 
     assert r.InitializeMemory(64, 36, 1, None, 0, 0, 0, False) == 0
     cx, cy = z(80, 64), z(80, 36)
@@ -298,6 +307,10 @@ def test_error_returns(renderer):
     farx = cx.copy()
     farx[:, 3] = limbs_of(32 << 2550)
     assert frame(x=farx) == FS_ERR_UNSUPPORTED
+    # two faults at once
+    assert frame(ib=2, n=1 << 32) == FS_ERR_UNSUPPORTED  # iter_bytes before the cap (fs_render_exact: after it)
+    assert frame(L=79, n=1 << 32) == FS_ERR_UNSUPPORTED  # the format before the cap
+    assert frame(ib=8, x=farx) == HIP_INVALID_VALUE      # the frame's iter_bytes before the axis range
     farx[:, 3] = limbs_of(-32 << 2550)
     assert frame(x=farx) == 0
     # the narrow entry points still end at 24 limbs
