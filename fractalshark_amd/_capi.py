@@ -90,6 +90,30 @@ class ExactKept(C.Structure):
                 ("bailout", u32), ("inclusive", u32), ("wide", u32), ("cycle_check", u32), ("valid", u32), ("reserved", u32)]
 
 
+class FeatureInF32(C.Structure):
+    """fs_feature_in_f32 (include/fs_layout.h)."""
+    _fields_ = [("dc", C.c_float * 2), ("c", C.c_float * 2), ("period", u64)]
+
+
+class FeatureInF64(C.Structure):
+    """fs_feature_in_f64 (include/fs_layout.h)."""
+    _fields_ = [("dc", C.c_double * 2), ("c", C.c_double * 2), ("period", u64)]
+
+
+class FeatureOutF32(C.Structure):
+    """fs_feature_out_f32 (include/fs_layout.h)."""
+    _fields_ = [("status", u32), ("pad0_", u32), ("period", u64), ("diff", C.c_float * 2), ("dzdc", C.c_float * 2),
+                ("zcoeff", C.c_float * 2), ("residual2", C.c_float), ("pad1_", u32)]
+
+
+class FeatureOutF64(C.Structure):
+    """fs_feature_out_f64 (include/fs_layout.h)."""
+    _fields_ = [("status", u32), ("pad0_", u32), ("period", u64), ("diff", C.c_double * 2), ("dzdc", C.c_double * 2),
+                ("zcoeff", C.c_double * 2), ("residual2", C.c_double)]
+
+
+assert C.sizeof(FeatureInF32) == 24 and C.sizeof(FeatureInF64) == 40
+assert C.sizeof(FeatureOutF32) == 48 and C.sizeof(FeatureOutF64) == 72
 assert C.sizeof(ExactKept) == 64
 assert C.sizeof(AutozoomResult) == 200
 assert C.sizeof(AuditOffender) == 24 and C.sizeof(AuditResult) == 568
@@ -147,6 +171,8 @@ def render_lib():
     _decl(lib, "fs_feature_eval", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
     _decl(lib, "fs_feature_eval_direct", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
     _decl(lib, "fs_feature_eval_resident", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
+    _decl(lib, "fs_feature_eval_plain", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
+    _decl(lib, "fs_feature_eval_plain_direct", u32, [vp, C.c_int, u32, C.c_int, vp, u64, vp, vp, u64])
     _decl(lib, "fs_orbit_form", C.c_int, [vp])
     _decl(lib, "fs_set_feature_slice", u32, [vp, u32])
     _decl(lib, "fs_autozoom_pick", u32, [vp, C.c_int, u64, vp, C.POINTER(AutozoomResult)])
@@ -246,7 +272,7 @@ RENDER_SYMBOLS = [
     "fs_create", "fs_destroy", "fs_test_device_is_working", "fs_device_count", "fs_error_string", "fs_init_memory", "fs_set_row_bands",
     "fs_local_rows", "fs_set_external_iter_buffer", "fs_device_iter_buffer", "fs_rounded_width", "fs_upload_orbit", "fs_upload_orbit_compressed",
     "fs_upload_la", "fs_upload_bla", "fs_render_lav2", "fs_feature_eval", "fs_feature_eval_direct", "fs_set_feature_slice",
-    "fs_feature_eval_resident", "fs_orbit_form",
+    "fs_feature_eval_resident", "fs_orbit_form", "fs_feature_eval_plain", "fs_feature_eval_plain_direct",
     "fs_autozoom_pick", "fs_set_autozoom_gather_cap",
     "fs_render_exact", "fs_exact_stable_mask", "fs_set_exact_slice", "fs_read_exact_stats",
     "fs_exact_sample_counts", "fs_render_exact_wide", "fs_exact_wide_state", "fs_exact_audit",
@@ -306,6 +332,11 @@ def inputs_lib():
     _decl(lib, "fsh_feature_begin_direct", vp, [vp, C.c_int, u32, u32, u32, u64])
     _decl(lib, "fsh_feature_begin_direct_at", vp, [vp, C.c_int, u32, u32, u32, u64])
     _decl(lib, "fsh_feature_direct_grid", C.c_int, [vp, C.c_int, u32, u32, vp, vp])
+    _decl(lib, "fsh_feature_begin_plain", vp, [vp, vp, u32, u32, u32, u64])
+    _decl(lib, "fsh_feature_begin_plain_direct", vp, [vp, C.c_int, u32, u32, u32, u64])
+    _decl(lib, "fsh_feature_begin_plain_direct_at", vp, [vp, C.c_int, u32, u32, u32, u64])
+    _decl(lib, "fsh_feature_plain_direct_grid", C.c_int, [vp, C.c_int, u32, u32, vp, vp])
+    _decl(lib, "fsh_feature_kind", C.c_int, [vp])
     _decl(lib, "fsh_feature_destroy", None, [vp])
     _decl(lib, "fsh_feature_is64", C.c_int, [vp])
     _decl(lib, "fsh_feature_candidates", u64, [vp])

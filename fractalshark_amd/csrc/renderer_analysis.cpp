@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "autozoom_math.hpp"
+#include "feature_plain.hpp"
 
 using namespace fsr;
 
@@ -135,7 +136,120 @@ static uint32_t feature_eval_direct(fs_renderer *r, uint32_t iter_bytes, int mod
     return (uint32_t)e;
 }
 
+// fs_feature_eval_plain / fs_feature_eval_plain_direct: the same shape for T = float / double (kernels_feature_plain.hip).
+// form = kFeatPExpanded / kFeatPWaypoints / kFeatPDirect.
+template <class T>
+static uint32_t feature_eval_plain(fs_renderer *r, int form, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
+                                   const void *in, void *out, uint64_t n)
+{
+    using In = typename FsFeatPRec<T>::In;
+    using Out = typename FsFeatPRec<T>::Out;
+    const bool find = mode == FS_FEATURE_FIND;
+    if (iter_bytes == 4 && !find)
+        for (uint64_t k = 0; k < n; k++)
+            if (((const In *)in)[k].period > 0xFFFFFFFFull)
+                return hipErrorInvalidValue; // a period IterType cannot hold
+    const T R = *(const T *)radius;
+    const int u64 = iter_bytes == 8;
+    const void *orbit = form == kFeatPWaypoints  ? (const void *)r->wp_raw
+                        : form == kFeatPExpanded ? (sizeof(T) == 4 ? (const void *)r->orbit_plain : (const void *)r->orbit_f64)
+                                                 : nullptr;
+    const uint32_t n_wp = form == kFeatPWaypoints ? (uint32_t)r->orbit_size : 0u;
+    const uint64_t count = form == kFeatPDirect ? 0 : r->orbit_uncompressed;
+    T c_low[2] = {T(0), T(0)};
+    if (form == kFeatPWaypoints) {
+        memcpy(&c_low[0], r->c_low_plain[0], sizeof(T));
+        memcpy(&c_low[1], r->c_low_plain[1], sizeof(T));
+    }
+    const uint32_t slice = r->feature_slice ? r->feature_slice : kFeatureSlice;
+    hipStream_t s = r->compute;
+    void *d_in = nullptr, *d_out = nullptr, *d_st = nullptr, *d_cnt = nullptr;
+    hipError_t e = r_alloc(r, &d_in, n * sizeof(In), kFrame);
+    if (e == hipSuccess)
+        e = r_alloc(r, &d_out, n * sizeof(Out), kFrame);
+    if (e == hipSuccess)
+        e = r_alloc(r, &d_st, n * fsk_featp_lane_bytes<T>(form, u64), kFrame);
+    if (e == hipSuccess)
+        e = r_alloc(r, &d_cnt, sizeof(uint32_t), kFrame);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_in, in, n * sizeof(In), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        fsk_featp_init<T>(form, u64, d_in, d_st, d_out, n, find, R, max_iters, count, orbit, n_wp, s);
+        e = hipGetLastError();
+    }
+    // slices until no candidate is left running; each ends in a synchronisation
+    while (e == hipSuccess) {
+        uint32_t left = 0;
+        e = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), s);
+        if (e != hipSuccess)
+            break;
+        fsk_featp_step<T>(form, u64, orbit, n_wp, c_low[0], c_low[1], count, d_st, d_out, n, find, R, slice, (uint32_t *)d_cnt, s);
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(&left, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (left == 0)
+            break;
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out, d_out, n * sizeof(Out), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    for (void *p : {d_in, d_out, d_st, d_cnt})
+        if (p)
+            (void)r_free(r, p);
+    return (uint32_t)e;
+}
+
 extern "C" {
+
+uint32_t fs_feature_eval_plain(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
+                               const void *in, void *out, uint64_t n)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if ((type_tag != FS_T_F32 && type_tag != FS_T_F64) || (iter_bytes != 4 && iter_bytes != 8) ||
+        (mode != FS_FEATURE_FIND && mode != FS_FEATURE_FIXED))
+        return FS_ERR_UNSUPPORTED;
+    if (!r->compute || !r->orbit_ok || r->orbit_type != type_tag)
+        return FS_ERR_6;
+    const bool seq = r->orbit_seq;
+    if (seq) {
+        if (!r->wp_raw || r->orbit_size == 0)
+            return FS_ERR_6;
+        // positions are IterType-wide: 32-bit ones cannot walk an orbit of 2^32 entries and more
+        if (iter_bytes == 4 && r->orbit_uncompressed > 0xFFFFFFFFull)
+            return FS_ERR_UNSUPPORTED;
+    } else if ((type_tag == FS_T_F32 ? (const void *)r->orbit_plain : (const void *)r->orbit_f64) == nullptr) {
+        return FS_ERR_6;
+    }
+    if (n == 0)
+        return 0;
+    if (!radius || !in || !out)
+        return hipErrorInvalidValue;
+    const int form = seq ? kFeatPWaypoints : kFeatPExpanded;
+    return type_tag == FS_T_F32 ? feature_eval_plain<float>(r, form, iter_bytes, mode, radius, max_iters, in, out, n)
+                                : feature_eval_plain<double>(r, form, iter_bytes, mode, radius, max_iters, in, out, n);
+}
+
+uint32_t fs_feature_eval_plain_direct(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius,
+                                      uint64_t max_iters, const void *in, void *out, uint64_t n)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if ((type_tag != FS_T_F32 && type_tag != FS_T_F64) || (iter_bytes != 4 && iter_bytes != 8) ||
+        (mode != FS_FEATURE_FIND && mode != FS_FEATURE_FIXED))
+        return FS_ERR_UNSUPPORTED;
+    if (n == 0)
+        return 0;
+    if (!radius || !in || !out)
+        return hipErrorInvalidValue;
+    if (uint32_t e = ensure_streams(r)) // no fs_init_memory needed
+        return e;
+    return type_tag == FS_T_F32 ? feature_eval_plain<float>(r, kFeatPDirect, iter_bytes, mode, radius, max_iters, in, out, n)
+                                : feature_eval_plain<double>(r, kFeatPDirect, iter_bytes, mode, radius, max_iters, in, out, n);
+}
 
 uint32_t fs_feature_eval(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius, uint64_t max_iters,
                          const void *in, void *out, uint64_t n)

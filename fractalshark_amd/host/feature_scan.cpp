@@ -95,18 +95,9 @@ struct FeatScreen {
 // The scan's screen points (FeatureFinderOrchestrator.cpp:541-548)
 inline uint64_t feat_grid_px(uint64_t extent, uint32_t g, uint32_t n) { return (extent * (2 * (uint64_t)g + 1)) / (2 * (uint64_t)n); }
 
-// `at`: the one screen point of the non-scan mode instead of the nx x ny grid
-template <class F>
-void feature_begin(fsh_feature &f, const fsh_view &v, uint32_t nx, uint32_t ny, const uint64_t *at = nullptr)
+// The candidates: `at` = the one screen point of the non-scan mode instead of the nx x ny grid.  F picks the list only.
+template <class F> void feature_grid(fsh_feature &f, const fsh_view &v, uint32_t nx, uint32_t ny, const uint64_t *at)
 {
-    mpf_set_default_prec(v.prec_bits);
-    // radiusY = T{MaxY - MinY} / T{2.0f}; HighPrecision radius{radiusY}; radius /= HighPrecision{12}
-    const hreal<F> radiusY = hr_div(hr_from_mpf<F>((v.maxY - v.minY).v), hr_from_number<F>(F(2)));
-    f.radius_hp = mp_from_hr(radiusY);
-    {
-        Mp twelve = Mp::from_ui(12);
-        mpf_div(f.radius_hp.v, f.radius_hp.v, twelve.v);
-    }
     const FeatScreen scr(v);
     auto &cs = cands<F>(f);
     auto add = [&](uint64_t x, uint64_t y, uint32_t grid) {
@@ -123,6 +114,20 @@ void feature_begin(fsh_feature &f, const fsh_view &v, uint32_t nx, uint32_t ny, 
     for (uint32_t gy = 0; gy < ny; ++gy)
         for (uint32_t gx = 0; gx < nx; ++gx)
             add(feat_grid_px(v.width, gx, nx), feat_grid_px(v.height, gy, ny), gy * nx + gx);
+}
+
+template <class F>
+void feature_begin(fsh_feature &f, const fsh_view &v, uint32_t nx, uint32_t ny, const uint64_t *at = nullptr)
+{
+    mpf_set_default_prec(v.prec_bits);
+    // radiusY = T{MaxY - MinY} / T{2.0f}; HighPrecision radius{radiusY}; radius /= HighPrecision{12}
+    const hreal<F> radiusY = hr_div(hr_from_mpf<F>((v.maxY - v.minY).v), hr_from_number<F>(F(2)));
+    f.radius_hp = mp_from_hr(radiusY);
+    {
+        Mp twelve = Mp::from_ui(12);
+        mpf_div(f.radius_hp.v, f.radius_hp.v, twelve.v);
+    }
+    feature_grid<F>(f, v, nx, ny, at);
 }
 
 // FindPeriodicPoint_Common's search radius: R = HdrAbs(T{radius}), SqrRadius = R * R reduced; what PTEvaluator::Eval passes on
@@ -257,6 +262,7 @@ extern "C" fsh_feature *fsh_feature_begin(const fsh_view *v, const fsh_orbit *o,
         return nullptr;
     auto f = std::make_unique<fsh_feature>();
     f->is64 = o->is64;
+    f->kind = o->is64 ? 1 : 0;
     f->iter_bytes = iter_bytes;
     f->max_iters = max_iters;
     f->prec_bits = v->prec_bits;
@@ -276,6 +282,7 @@ static fsh_feature *feature_begin_direct(const fsh_view *v, int is64, uint32_t n
         return nullptr;
     auto f = std::make_unique<fsh_feature>();
     f->is64 = is64 != 0;
+    f->kind = f->is64;
     f->iter_bytes = iter_bytes;
     f->max_iters = max_iters;
     f->prec_bits = v->prec_bits;
@@ -341,14 +348,265 @@ extern "C" int fsh_feature_direct_grid(const fsh_view *v, int is64, uint32_t nx,
     return 0;
 }
 
+// ------------------------------------------------------------------ T = float / double (fsh_feature_begin_plain*)
+// The same machine with the reference's plain T: C = FloatComplex<T>, HdrReduce empty, compares the plain operators,
+// T{HighPrecision} = mpf_get_d (which truncates) and then the cast (HighPrecision.h:497-506), HighPrecision{T} = mpf_set_d at the
+// default precision (:175-179).  R, SqrRadius = R * R and the tolerances are in T, so SqrRadius underflows to 0 in a view narrow
+// enough (float: below about 1e-21; double: below about 1e-160) and every candidate is then rejected, as in the reference.  Div
+// and the intrinsic radius go through HDRFloat<double> (PromoteToHdrD / DemoteToT, FeatureFinder.h:206-226).
+namespace {
+
+template <class T> T pt_from_mp(const Mp &x) { return (T)mpf_get_d(x.v); }
+
+template <class T> struct pcplx {
+    T re, im;
+};
+template <class T> T pc_norm2(pcplx<T> a) { return a.re * a.re + a.im * a.im; }
+
+using HD = hreal<double>;
+// PromoteToHdrD of an arithmetic value: HDRFloat<double>(double) = {mant, 0} reduced (HDRFloat.h:206-212)
+template <class T> HD promote(T v) { return hr_from_mant<double>((double)v); }
+
+// FeatureFinder::Div (FeatureFinder.cpp:1550-1574)
+template <class T> pcplx<T> feat_div_plain(pcplx<T> a, pcplx<T> b)
+{
+    const HD br = promote(b.re), bi = promote(b.im);
+    const HD denom = hr_reduced(hr_add(hr_mul(br, br), hr_mul(bi, bi)));
+    if (hr_cmp_pos(denom, hr_zero<double>()) <= 0)
+        return pcplx<T>{T(0), T(0)};
+    const HD ar = promote(a.re), ai = promote(a.im);
+    const HD rr = hr_reduced(hr_div(hr_add(hr_mul(ar, br), hr_mul(ai, bi)), denom));
+    const HD ii = hr_reduced(hr_div(hr_sub(hr_mul(ai, br), hr_mul(ar, bi)), denom));
+    return pcplx<T>{(T)hr_to_native<double>(rr), (T)hr_to_native<double>(ii)};
+}
+
+template <class T> void feature_begin_plain(fsh_feature &f, const fsh_view &v, uint32_t nx, uint32_t ny, const uint64_t *at = nullptr)
+{
+    mpf_set_default_prec(v.prec_bits);
+    // radiusY = T{MaxY - MinY} / T{2.0f}; HighPrecision radius{radiusY}; radius /= HighPrecision{12}
+    const T radiusY = pt_from_mp<T>(v.maxY - v.minY) / T(2.0f);
+    f.radius_hp = Mp();
+    mpf_set_d(f.radius_hp.v, (double)radiusY);
+    {
+        Mp twelve = Mp::from_ui(12);
+        mpf_div(f.radius_hp.v, f.radius_hp.v, twelve.v);
+    }
+    feature_grid<T>(f, v, nx, ny, at);
+}
+
+// R = HdrAbs(T{radius}), SqrRadius = R * R; what the evaluators get is HdrSqrt(SqrRadius)
+template <class T> T feature_eval_radius_plain(const fsh_feature &f)
+{
+    const T R = std::fabs(pt_from_mp<T>(f.radius_hp));
+    const T sqr = R * R;
+    return std::sqrt(sqr);
+}
+
+template <class T, class In> uint64_t feature_next_plain(fsh_feature &f, In *in, uint64_t cap, int *mode)
+{
+    auto &cs = cands<T>(f);
+    f.batch.clear();
+    bool any_find = false;
+    for (const FeatCand<T> &c : cs)
+        any_find |= c.stage == kFind;
+    for (uint32_t k = 0; k < cs.size(); ++k)
+        if (cs[k].stage < kFound && (cs[k].stage == kFind) == any_find && f.batch.size() < cap) {
+            FeatCand<T> &c = cs[k];
+            In r{};
+            if (!f.direct) {
+                r.dc[0] = pt_from_mp<T>(c.cx - f.hiX);
+                r.dc[1] = pt_from_mp<T>(c.cy - f.hiY);
+            }
+            r.c[0] = pt_from_mp<T>(c.cx);
+            r.c[1] = pt_from_mp<T>(c.cy);
+            r.period = c.stage == kFind ? 0 : c.period;
+            in[f.batch.size()] = r;
+            f.batch.push_back(k);
+        }
+    *mode = any_find ? 0 : 1;
+    return f.batch.size();
+}
+
+// c <- c - diff / dzdc, in mpf only.  False: dzdc is degenerate (rejected) -- or the step is not finite, which mpf_set_d cannot
+// take (the reference's HighPrecision{T} would abort there).
+template <class T> bool newton_step_plain(FeatCand<T> &c, pcplx<T> diff, pcplx<T> dzdc, pcplx<T> *step_out)
+{
+    if (pc_norm2(dzdc) <= T(0))
+        return false;
+    const pcplx<T> step = feat_div_plain(diff, dzdc);
+    if (!std::isfinite(step.re) || !std::isfinite(step.im))
+        return false;
+    Mp sx, sy;
+    mpf_set_d(sx.v, (double)step.re);
+    mpf_set_d(sy.v, (double)step.im);
+    c.cx = c.cx - sx;
+    c.cy = c.cy - sy;
+    if (step_out)
+        *step_out = step;
+    return true;
+}
+
+template <class T, class Out> void feature_consume_plain(fsh_feature &f, const Out *out, uint64_t n)
+{
+    auto &cs = cands<T>(f);
+    const T tol = T(0x1p-40); // diffTol and RelStepTol alike
+    const T tol2 = tol * tol;
+    for (uint64_t j = 0; j < n && j < f.batch.size(); ++j) {
+        FeatCand<T> &c = cs[f.batch[j]];
+        const Out &o = out[j];
+        if (o.status == 0) {
+            c.stage = kRejected;
+            continue;
+        }
+        const pcplx<T> diff{o.diff[0], o.diff[1]}, dzdc{o.dzdc[0], o.dzdc[1]}, zcoeff{o.zcoeff[0], o.zcoeff[1]};
+        switch (c.stage) {
+        case kFind:
+            c.period = o.period;
+            c.stage = newton_step_plain<T>(c, diff, dzdc, nullptr) ? kNewton : kRejected;
+            break;
+        case kNewton: {
+            const pcplx<T> cT{pt_from_mp<T>(c.cx), pt_from_mp<T>(c.cy)};
+            if (pc_norm2(diff) <= pc_norm2(cT) * tol2) {
+                c.stage = kFinal1;
+                break;
+            }
+            pcplx<T> step;
+            if (!newton_step_plain<T>(c, diff, dzdc, &step)) {
+                c.stage = kRejected;
+                break;
+            }
+            const pcplx<T> cNew{pt_from_mp<T>(c.cx), pt_from_mp<T>(c.cy)};
+            if (pc_norm2(step) <= pc_norm2(cNew) * tol2 || ++c.it >= 32)
+                c.stage = kFinal1;
+            break;
+        }
+        case kFinal1:
+            c.stage = newton_step_plain<T>(c, diff, dzdc, nullptr) ? kFinal2 : kRejected;
+            break;
+        case kFinal2: {
+            // the candidate store's w test (:2636-2662), then ComputeIntrinsicRadius_HP (:1713-1746)
+            const HD zr = promote(zcoeff.re), zi = promote(zcoeff.im), dr = promote(dzdc.re), di = promote(dzdc.im);
+            const HD wr = hr_reduced(hr_sub(hr_mul(zr, dr), hr_mul(zi, di)));
+            const HD wi = hr_reduced(hr_add(hr_mul(zr, di), hr_mul(zi, dr)));
+            const HD w2 = hr_reduced(hr_add(hr_mul(wr, wr), hr_mul(wi, wi)));
+            if (!(hr_cmp_pos(w2, hr_zero<double>()) > 0)) {
+                c.stage = kRejected;
+                break;
+            }
+            const HD absW = hr_reduced(hr_sqrt(w2));
+            const HD radius = hr_reduced(hr_div(hr_from_mant<double>(4.0), absW));
+            c.radius = mp_from_hr(radius);
+            // HDRFloat<double>{residual2}: of a float, the templated constructor (HDRFloat.h:295-317); of a double, {mant, 0}
+            // reduced (:206-212) -- they differ for a zero only
+            c.residual2 = sizeof(T) == 4 ? hr_from_number<double>((double)o.residual2) : hr_from_mant<double>((double)o.residual2);
+            c.stage = kFound;
+            break;
+        }
+        default:
+            break;
+        }
+    }
+}
+
+fsh_feature *feature_begin_plain_any(const fsh_view *v, int kind, const Mp *hiX, const Mp *hiY, uint32_t nx, uint32_t ny,
+                                     const uint64_t *at, uint32_t iter_bytes, uint64_t max_iters)
+{
+    if (!v || (kind != 0 && kind != 1) || nx == 0 || ny == 0 || (iter_bytes != 4 && iter_bytes != 8))
+        return nullptr;
+    auto f = std::make_unique<fsh_feature>();
+    f->kind = 2 + kind;
+    f->is64 = kind;
+    f->iter_bytes = iter_bytes;
+    f->max_iters = max_iters;
+    f->prec_bits = v->prec_bits;
+    f->direct = hiX == nullptr;
+    if (hiX)
+        f->hiX = *hiX, f->hiY = *hiY;
+    if (kind)
+        feature_begin_plain<double>(*f, *v, nx, ny, at);
+    else
+        feature_begin_plain<float>(*f, *v, nx, ny, at);
+    return f.release();
+}
+
+} // namespace
+
+extern "C" fsh_feature *fsh_feature_begin_plain(const fsh_view *v, const fsh_plain *p, uint32_t nx, uint32_t ny, uint32_t iter_bytes,
+                                                uint64_t max_iters)
+{
+    if (!p)
+        return nullptr;
+    const Mp &hiX = p->kind == 0 ? p->f.ob.cx : p->d.ob.cx;
+    const Mp &hiY = p->kind == 0 ? p->f.ob.cy : p->d.ob.cy;
+    return feature_begin_plain_any(v, p->kind, &hiX, &hiY, nx, ny, nullptr, iter_bytes, max_iters);
+}
+
+extern "C" fsh_feature *fsh_feature_begin_plain_direct(const fsh_view *v, int kind, uint32_t nx, uint32_t ny, uint32_t iter_bytes,
+                                                       uint64_t max_iters)
+{
+    return feature_begin_plain_any(v, kind, nullptr, nullptr, nx, ny, nullptr, iter_bytes, max_iters);
+}
+
+extern "C" fsh_feature *fsh_feature_begin_plain_direct_at(const fsh_view *v, int kind, uint32_t px, uint32_t py,
+                                                          uint32_t iter_bytes, uint64_t max_iters)
+{
+    const uint64_t at[2] = {px, py};
+    return feature_begin_plain_any(v, kind, nullptr, nullptr, 1, 1, at, iter_bytes, max_iters);
+}
+
+namespace {
+
+template <class T, class In> void feature_plain_direct_grid(const fsh_view &v, uint32_t nx, uint32_t ny, In *in, T *radius)
+{
+    fsh_feature f; // for its search radius only
+    f.prec_bits = v.prec_bits;
+    feature_begin_plain<T>(f, v, 1, 1);
+    *radius = feature_eval_radius_plain<T>(f);
+    // T{cX_hp} per column and T{cY_hp} per row
+    const FeatScreen scr(v);
+    std::vector<T> re(nx), im(ny);
+    for (uint32_t gx = 0; gx < nx; ++gx)
+        re[gx] = pt_from_mp<T>(scr.X(feat_grid_px(v.width, gx, nx)));
+    for (uint32_t gy = 0; gy < ny; ++gy)
+        im[gy] = pt_from_mp<T>(scr.Y(feat_grid_px(v.height, gy, ny)));
+    for (uint32_t gy = 0; gy < ny; ++gy)
+        for (uint32_t gx = 0; gx < nx; ++gx) {
+            In r{};
+            r.c[0] = re[gx], r.c[1] = im[gy];
+            in[(size_t)gy * nx + gx] = r;
+        }
+}
+
+} // namespace
+
+extern "C" int fsh_feature_plain_direct_grid(const fsh_view *v, int kind, uint32_t nx, uint32_t ny, void *in, void *radius)
+{
+    if (!v || (kind != 0 && kind != 1) || nx == 0 || ny == 0 || !in || !radius)
+        return -1;
+    if (kind)
+        feature_plain_direct_grid<double>(*v, nx, ny, (fs_feature_in_f64 *)in, (double *)radius);
+    else
+        feature_plain_direct_grid<float>(*v, nx, ny, (fs_feature_in_f32 *)in, (float *)radius);
+    return 0;
+}
+
 extern "C" void fsh_feature_destroy(fsh_feature *f) { delete f; }
 extern "C" int fsh_feature_is64(const fsh_feature *f) { return f->is64; }
+extern "C" int fsh_feature_kind(const fsh_feature *f) { return f->kind; }
 extern "C" uint64_t fsh_feature_candidates(const fsh_feature *f) { return f->is64 ? f->c64.size() : f->c32.size(); }
 
 extern "C" uint64_t fsh_feature_next_batch(fsh_feature *f, void *in, uint64_t cap, int *mode, void *radius, uint64_t *max_iters)
 {
     mpf_set_default_prec(f->prec_bits);
     *max_iters = f->max_iters;
+    if (f->kind == 2) {
+        *(float *)radius = feature_eval_radius_plain<float>(*f);
+        return feature_next_plain<float>(*f, (fs_feature_in_f32 *)in, cap, mode);
+    }
+    if (f->kind == 3) {
+        *(double *)radius = feature_eval_radius_plain<double>(*f);
+        return feature_next_plain<double>(*f, (fs_feature_in_f64 *)in, cap, mode);
+    }
     if (f->is64) {
         const hreal<double> R = feature_eval_radius<double>(*f);
         *(fs_real_hdr64 *)radius = fs_real_hdr64{R.m, R.e, 0};
@@ -362,7 +620,11 @@ extern "C" uint64_t fsh_feature_next_batch(fsh_feature *f, void *in, uint64_t ca
 extern "C" void fsh_feature_consume(fsh_feature *f, const void *out, uint64_t n)
 {
     mpf_set_default_prec(f->prec_bits);
-    if (f->is64)
+    if (f->kind == 2)
+        feature_consume_plain<float>(*f, (const fs_feature_out_f32 *)out, n);
+    else if (f->kind == 3)
+        feature_consume_plain<double>(*f, (const fs_feature_out_f64 *)out, n);
+    else if (f->is64)
         feature_consume<double>(*f, (const fs_feature_out_hdr64 *)out, n);
     else
         feature_consume<float>(*f, (const fs_feature_out_hdr32 *)out, n);

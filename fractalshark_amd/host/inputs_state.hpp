@@ -402,7 +402,8 @@ template <class F> struct FeatCand {
 };
 
 struct fsh_feature {
-    int is64 = 0;
+    int is64 = 0; // T is 64 bits wide: the candidates are in c64, else in c32
+    int kind = 0; // T: 0 HDRFloat<float>, 1 HDRFloat<double>, 2 float, 3 double
     uint32_t iter_bytes = 4;
     uint64_t max_iters = 0;
     uint64_t prec_bits = 0;

@@ -307,6 +307,33 @@ class GPURenderer:
         """fs_exact_drop_kept: frees the kept set."""
         return self._lib.fs_exact_drop_kept(self._h)
 
+    def FeatureEvalPlain(self, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
+        """fs_feature_eval_plain: the Feature Finder's perturbation evaluator for T = T_F32 / T_F64 on the resident plain orbit
+        of that type (InitializePerturbPlain), in whichever form it is held (orbit_form).  radius = R as a one-element float32 /
+        float64 array; records = features.FEATURE_IN_F32 / _F64, FEATURE_OUT_F32 / _F64.  Otherwise FeatureEval.  Synchronous."""
+        return self._feature_eval_plain(self._lib.fs_feature_eval_plain, T, iter_bytes, mode, radius, max_iters, records_in,
+                                        records_out)
+
+    def FeatureEvalPlainDirect(self, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
+        """fs_feature_eval_plain_direct: the Direct evaluator for T = T_F32 / T_F64; the arguments of FeatureEvalPlain.  Needs no
+        orbit and no InitializeMemory.  Synchronous."""
+        return self._feature_eval_plain(self._lib.fs_feature_eval_plain_direct, T, iter_bytes, mode, radius, max_iters,
+                                        records_in, records_out)
+
+    def _feature_eval_plain(self, entry, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
+        from . import features
+        n = len(records_in)
+        radius = np.ascontiguousarray(radius)
+        if T in (T_F32, T_F64):
+            din, dout, dreal = features.records_plain(T == T_F64)
+            if records_in.dtype != din or records_out.dtype != dout or radius.dtype != dreal:
+                raise ValueError("records and radius must be the features.FEATURE_*_%s dtypes and float%d of T"
+                                 % (("F64", 64) if T == T_F64 else ("F32", 32)))
+        if len(records_out) < n or not (records_in.flags.c_contiguous and records_out.flags.c_contiguous):
+            raise ValueError("records_out must be contiguous and hold at least as many records as records_in")
+        return entry(self._h, int(T), int(iter_bytes), int(mode), radius.ctypes.data, int(max_iters),
+                     records_in.ctypes.data if n else None, records_out.ctypes.data if n else None, n)
+
     def _feature_eval(self, entry, T, iter_bytes, mode, radius, max_iters, records_in, records_out):
         from . import features
         din, dout, dreal = features.records(T == T_HDR64)

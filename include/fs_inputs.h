@@ -263,6 +263,22 @@ fsh_feature *fsh_feature_begin_direct_at(const fsh_view *v, int is64, uint32_t p
  * not per point), *radius = its R.  in = nx * ny fs_feature_in_hdr32 / _hdr64, radius = fs_real_hdr32 / _hdr64 by is64.
  * 0, or -1 for bad arguments. */
 int fsh_feature_direct_grid(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, void *in, void *radius);
+/* The same scans with the reference's plain T = float / double (the Feature Finder of the render algorithms whose MainType is
+ * plain, FeatureFinder.cpp:2740-2795): records fs_feature_in_f32 / _f64 and fs_feature_out_f32 / _f64, R one float / double; the
+ * batches are the arguments of fs_feature_eval_plain / fs_feature_eval_plain_direct calls.  T{HighPrecision} is mpf_get_d -- which
+ * truncates -- and then the cast; R, SqrRadius = R * R and the tolerances are in T; Div and the intrinsic radius go through
+ * HDRFloat<double> as for the HDR types; dc = T{cX_hp - HiX} with HiX, HiY the fsh_plain orbit's point.  As in the reference,
+ * SqrRadius underflows to 0 in float for views narrower than about 1e-21 (double: about 1e-160), and every candidate is then
+ * rejected.  kind = fsh_plain_kind's: 0 float, 1 double.  After a begin, next_batch / consume / found / result / destroy as above.
+ * fsh_feature_kind: T of a scan -- 0 HDRFloat<float>, 1 HDRFloat<double>, 2 float, 3 double. */
+fsh_feature *fsh_feature_begin_plain(const fsh_view *v, const fsh_plain *p, uint32_t nx, uint32_t ny, uint32_t iter_bytes,
+                                     uint64_t max_iters);
+fsh_feature *fsh_feature_begin_plain_direct(const fsh_view *v, int kind, uint32_t nx, uint32_t ny, uint32_t iter_bytes,
+                                            uint64_t max_iters);
+fsh_feature *fsh_feature_begin_plain_direct_at(const fsh_view *v, int kind, uint32_t px, uint32_t py, uint32_t iter_bytes,
+                                               uint64_t max_iters);
+int fsh_feature_plain_direct_grid(const fsh_view *v, int kind, uint32_t nx, uint32_t ny, void *in, void *radius);
+int fsh_feature_kind(const fsh_feature *f);
 
 #ifdef __cplusplus
 }

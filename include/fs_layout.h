@@ -479,6 +479,42 @@ typedef struct fs_feature_out_hdr64 {
     fs_real_hdr64 residual2;
 } fs_feature_out_hdr64;
 
+/* fs_feature_eval_plain / fs_feature_eval_plain_direct (fsmi355.h): the same two records for T = float (f32) and double (f64),
+ * C = FloatComplex<T>: {re, im} pairs.  dc = T{cX_hp - HiX} + i T{cY_hp - HiY}, c = T{cX_hp} + i T{cY_hp}; a rejected
+ * candidate's record is all zero bits. */
+typedef struct fs_feature_in_f32 {
+    float dc[2];
+    float c[2];
+    uint64_t period;
+} fs_feature_in_f32;
+
+typedef struct fs_feature_in_f64 {
+    double dc[2];
+    double c[2];
+    uint64_t period;
+} fs_feature_in_f64;
+
+typedef struct fs_feature_out_f32 {
+    uint32_t status;
+    uint32_t pad0_;
+    uint64_t period;
+    float diff[2];
+    float dzdc[2];
+    float zcoeff[2];
+    float residual2;
+    uint32_t pad1_;
+} fs_feature_out_f32;
+
+typedef struct fs_feature_out_f64 {
+    uint32_t status;
+    uint32_t pad0_;
+    uint64_t period;
+    double diff[2];
+    double dzdc[2];
+    double zcoeff[2];
+    double residual2;
+} fs_feature_out_f64;
+
 /* fs_autozoom_pick (fsmi355.h).  Per heuristic (fields not named are zero):
  *   Max          target = first pixel at max_iter; max_iter, sum_iters, avg = sum / (W H) over the frame; num_at_limit = pixels at
  *                max_iter; num_at_max = pixels >= n_iterations.
@@ -543,6 +579,9 @@ static_assert(sizeof(fs_audit_offender) == 24 && sizeof(fs_audit_result) == 568,
 static_assert(sizeof(fs_feature_in_hdr32) == 32&& sizeof(fs_feature_in_hdr64) == 56 && sizeof(fs_feature_out_hdr32) == 64 &&
                   sizeof(fs_feature_out_hdr64) == 104,
               "Feature Finder records");
+static_assert(sizeof(fs_feature_in_f32) == 24 && sizeof(fs_feature_in_f64) == 40 && sizeof(fs_feature_out_f32) == 48 &&
+                  sizeof(fs_feature_out_f64) == 72,
+              "Feature Finder records, plain types");
 static_assert(sizeof(fs_orbit_hdr32) == 16, "orbit entry");
 static_assert(sizeof(fs_orbit_hdr32_rc) == 24 && sizeof(fs_orbit_hdr64_rc) == 40, "compressed orbit entry");
 static_assert(sizeof(fs_orbit_f32_rc) == 16 && sizeof(fs_orbit_f64_rc) == 24 && sizeof(fs_orbit_p2x32_rc) == 24 &&

@@ -213,6 +213,27 @@ int fs_orbit_form(const fs_renderer *r);
  * FS_FEATURE_FIND / FS_FEATURE_FIXED.  hipErrorInvalidValue: a fixed period that a 4-byte IterType cannot hold. */
 uint32_t fs_feature_eval_direct(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius,
                                 uint64_t max_iters, const void *in, void *out, uint64_t n);
+/* The Feature Finder for the plain numeric types, T = float (FS_T_F32) / double (FS_T_F64): what the reference runs when the
+ * render algorithm's MainType is plain (FeatureFinderOrchestrator.cpp:457-469, FeatureFinder.cpp:2740-2795), Gpu1x32PerturbedLAv2*
+ * -- its automatic choice below a zoom factor of 1e34 -- among them.  C = FloatComplex<T>, every operation one IEEE operation.
+ * The calls above keep refusing these two tags; these two refuse every other.
+ *   fs_feature_eval_plain         PTEvaluator::Eval<true | false> against the resident plain orbit of that type (fs_upload_orbit /
+ *                                 fs_upload_orbit_compressed with FS_T_F32 / FS_T_F64) in whichever form it is held
+ *                                 (fs_orbit_form): expanded, one lane per candidate; waypoints only
+ *                                 (fs_set_compressed_orbit_mode(r, 1)), a decompression cursor per lane with positions as wide as
+ *                                 iter_bytes.  Both forms give the same records byte for byte.
+ *   fs_feature_eval_plain_direct  DirectEvaluator::Eval; needs no orbit and no fs_init_memory.
+ * radius = R as one float / double (HdrSqrt(SqrRadius), computed by the host); in / out = fs_feature_in_f32 / _f64,
+ * fs_feature_out_f32 / _f64 (fs_layout.h); modes, statuses and iter_bytes as fs_feature_eval.  Synchronous on the compute stream;
+ * slices through fs_set_feature_slice; n = 0 returns 0 without a launch; frame state, caches and kernel-time history are left
+ * as they were.
+ * FS_ERR_UNSUPPORTED: another type tag, iter_bytes not 4 or 8, mode FS_FEATURE_LA or unknown, a waypoint-resident orbit of 2^32
+ * entries and more with iter_bytes = 4.  FS_ERR_6 (fs_feature_eval_plain only): no orbit of this type resident.
+ * hipErrorInvalidValue: a NULL argument, or a fixed period that a 4-byte IterType cannot hold. */
+uint32_t fs_feature_eval_plain(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius,
+                               uint64_t max_iters, const void *in, void *out, uint64_t n);
+uint32_t fs_feature_eval_plain_direct(fs_renderer *r, int type_tag, uint32_t iter_bytes, int mode, const void *radius,
+                                      uint64_t max_iters, const void *in, void *out, uint64_t n);
 
 /* The AutoZoomer's choice of the next zoom target (AutoZoomer::Run, AutoZoomer.cpp:74-393) on the device, from the iteration
  * buffer the render kernels wrote: the frame is never read back.  W x H below = the frame of fs_init_memory (antialiasing
