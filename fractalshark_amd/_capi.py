@@ -332,6 +332,8 @@ def inputs_lib():
     _decl(lib, "fsh_feature_begin_direct", vp, [vp, C.c_int, u32, u32, u32, u64])
     _decl(lib, "fsh_feature_begin_direct_at", vp, [vp, C.c_int, u32, u32, u32, u64])
     _decl(lib, "fsh_feature_direct_grid", C.c_int, [vp, C.c_int, u32, u32, vp, vp])
+    _decl(lib, "fsh_feature_pt_axes", C.c_int, [vp, vp, C.c_int, u32, u32, vp, vp, vp, vp, vp])
+    _decl(lib, "fsh_feature_pt_grid", C.c_int, [vp, vp, C.c_int, u32, u32, vp, vp])
     _decl(lib, "fsh_feature_begin_plain", vp, [vp, vp, u32, u32, u32, u64])
     _decl(lib, "fsh_feature_begin_plain_direct", vp, [vp, C.c_int, u32, u32, u32, u64])
     _decl(lib, "fsh_feature_begin_plain_direct_at", vp, [vp, C.c_int, u32, u32, u32, u64])

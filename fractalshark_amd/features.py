@@ -7,7 +7,9 @@ candidate (libfsinputs: fsh_feature_*) and each round evaluates all candidates s
 GPU lane per candidate (fs_feature_eval_resident where only the orbit's waypoints are resident).
 
 The Direct / DirectScan modes (scan_direct, find_periodic_points_direct) are the same scan without a reference orbit, through
-fs_feature_eval_direct; period_map is their period search alone over a dense grid of the view.
+fs_feature_eval_direct; period_map is their period search alone over a dense grid of the view.  pt_grid makes the PT scan's
+period-search round over a dense grid as records, without the state machine (the arguments of one fs_feature_eval call, which
+sees a deep view where Direct sees one constant c); pt_axes the same grid as its four axes.
 
 T is the reference's RenderAlg::MainType: HDRFloat<float> / HDRFloat<double> with an inputs.Orbit (T_HDR32 / T_HDR64), plain float /
 double with an inputs.PlainInputs orbit (T_F32 / T_F64: fs_feature_eval_plain, fs_feature_eval_plain_direct) -- what the reference
@@ -192,6 +194,44 @@ def direct_grid(view, is64, nx, ny, plain=False):
     grid = lib.fsh_feature_plain_direct_grid if plain else lib.fsh_feature_direct_grid
     if grid(view._h, 1 if is64 else 0, int(nx), int(ny), rin.ctypes.data, rad.ctypes.data) != 0:
         raise ValueError("fsh_feature_direct_grid: bad arguments")
+    return rin, rad
+
+
+def _hdr_orbit_is64(orbit, what):
+    """is64 of an inputs.Orbit; ValueError for an inputs.PlainInputs (the PT grid is built for the HDR types only)."""
+    if getattr(orbit, "kind", None) is not None:
+        raise ValueError("%s: an inputs.Orbit is needed, not an inputs.PlainInputs" % what)
+    return bool(orbit.is64)
+
+
+def pt_axes(view, orbit, nx, ny):
+    """The find round of a PT scan over the view's nx x ny grid points as four axes: (dc_re[nx], dc_im[ny], c_re[nx], c_im[ny],
+    radius) -- REAL_HDR32 / REAL_HDR64 records by the orbit's type, un-combined: grid point (gx, gy) has dc = C(dc_re[gx],
+    dc_im[gy]) and c = C(c_re[gx], c_im[gy]), reduced: 2 (nx + ny) values describe the nx * ny records of pt_grid."""
+    is64 = _hdr_orbit_is64(orbit, "pt_axes")
+    dreal = records(is64)[2]
+    nx, ny = int(nx), int(ny)
+    if nx <= 0 or ny <= 0:
+        raise ValueError("fsh_feature_pt_axes: bad arguments")
+    ax = [np.zeros(n, dreal) for n in (nx, ny, nx, ny)]
+    rad = np.zeros(1, dreal)
+    if _capi.inputs_lib().fsh_feature_pt_axes(view._h, orbit._h, 1 if is64 else 0, nx, ny, *[a.ctypes.data for a in ax],
+                                              rad.ctypes.data) != 0:
+        raise ValueError("fsh_feature_pt_axes: bad arguments")
+    return (*ax, rad)
+
+
+def pt_grid(view, orbit, nx, ny):
+    """(records_in, radius) of a PT scan's period-search round over the view's nx x ny grid points, row-major: the first batch of
+    scan(view, orbit, ...), built without its state machine (the high-precision arithmetic once per column and row)."""
+    is64 = _hdr_orbit_is64(orbit, "pt_grid")
+    din, _, dreal = records(is64)
+    nx, ny = int(nx), int(ny)
+    if nx <= 0 or ny <= 0:
+        raise ValueError("fsh_feature_pt_grid: bad arguments")
+    rin, rad = np.zeros(nx * ny, din), np.zeros(1, dreal)
+    if _capi.inputs_lib().fsh_feature_pt_grid(view._h, orbit._h, 1 if is64 else 0, nx, ny, rin.ctypes.data, rad.ctypes.data) != 0:
+        raise ValueError("fsh_feature_pt_grid: bad arguments")
     return rin, rad
 
 

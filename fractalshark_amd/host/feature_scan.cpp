@@ -348,6 +348,100 @@ extern "C" int fsh_feature_direct_grid(const fsh_view *v, int is64, uint32_t nx,
     return 0;
 }
 
+namespace {
+
+// The PT scan's find round over the grid, taken apart: feature_next's dc = ct_from_mp(cx - HiX, cy - HiY) and c = ct_from_mp(cx, cy)
+// read cx of the column and cy of the row only, so T{..} of the four is made once per column and once per row.
+template <class F> struct PtAxes {
+    std::vector<hreal<F>> dc_re, dc_im, c_re, c_im;
+    hreal<F> R;
+};
+
+template <class F> PtAxes<F> feature_pt_axes(const fsh_view &v, const Mp &hiX, const Mp &hiY, uint32_t nx, uint32_t ny)
+{
+    mpf_set_default_prec(v.prec_bits);
+    fsh_feature f; // for its search radius only
+    f.prec_bits = v.prec_bits;
+    feature_begin<F>(f, v, 1, 1);
+    PtAxes<F> a;
+    a.R = feature_eval_radius<F>(f);
+    const FeatScreen scr(v);
+    a.dc_re.resize(nx), a.c_re.resize(nx), a.dc_im.resize(ny), a.c_im.resize(ny);
+    for (uint32_t gx = 0; gx < nx; ++gx) {
+        const Mp cx = scr.X(feat_grid_px(v.width, gx, nx));
+        a.c_re[gx] = hr_from_mpf<F>(cx.v);
+        a.dc_re[gx] = hr_from_mpf<F>((cx - hiX).v);
+    }
+    for (uint32_t gy = 0; gy < ny; ++gy) {
+        const Mp cy = scr.Y(feat_grid_px(v.height, gy, ny));
+        a.c_im[gy] = hr_from_mpf<F>(cy.v);
+        a.dc_im[gy] = hr_from_mpf<F>((cy - hiY).v);
+    }
+    return a;
+}
+
+template <class F, class Real> void store_axis(const std::vector<hreal<F>> &a, void *out)
+{
+    for (size_t k = 0; k < a.size(); ++k) {
+        Real r{};
+        r.m = a[k].m, r.e = a[k].e;
+        ((Real *)out)[k] = r;
+    }
+}
+
+template <class F, class Real>
+void feature_pt_axes_out(const fsh_view &v, const Mp &hiX, const Mp &hiY, uint32_t nx, uint32_t ny, void *dc_re, void *dc_im,
+                         void *c_re, void *c_im, void *radius)
+{
+    const PtAxes<F> a = feature_pt_axes<F>(v, hiX, hiY, nx, ny);
+    store_axis<F, Real>(a.dc_re, dc_re);
+    store_axis<F, Real>(a.dc_im, dc_im);
+    store_axis<F, Real>(a.c_re, c_re);
+    store_axis<F, Real>(a.c_im, c_im);
+    store_axis<F, Real>({a.R}, radius);
+}
+
+template <class F, class In, class Real>
+void feature_pt_grid(const fsh_view &v, const Mp &hiX, const Mp &hiY, uint32_t nx, uint32_t ny, In *in, void *radius)
+{
+    const PtAxes<F> a = feature_pt_axes<F>(v, hiX, hiY, nx, ny);
+    store_axis<F, Real>({a.R}, radius);
+    for (uint32_t gy = 0; gy < ny; ++gy)
+        for (uint32_t gx = 0; gx < nx; ++gx) {
+            const hcplx<F> dc = hc_reduced(hc_from_hr(a.dc_re[gx], a.dc_im[gy]));
+            const hcplx<F> cc = hc_reduced(hc_from_hr(a.c_re[gx], a.c_im[gy]));
+            In r{};
+            r.dc.re = dc.re, r.dc.im = dc.im, r.dc.e = dc.e;
+            r.c.re = cc.re, r.c.im = cc.im, r.c.e = cc.e;
+            in[(size_t)gy * nx + gx] = r;
+        }
+}
+
+} // namespace
+
+extern "C" int fsh_feature_pt_axes(const fsh_view *v, const fsh_orbit *o, int is64, uint32_t nx, uint32_t ny, void *dc_re,
+                                   void *dc_im, void *c_re, void *c_im, void *radius)
+{
+    if (!v || !o || nx == 0 || ny == 0 || !dc_re || !dc_im || !c_re || !c_im || !radius || (is64 != 0) != (o->is64 != 0))
+        return -1;
+    if (o->is64)
+        feature_pt_axes_out<double, fs_real_hdr64>(*v, o->d.cx, o->d.cy, nx, ny, dc_re, dc_im, c_re, c_im, radius);
+    else
+        feature_pt_axes_out<float, fs_real_hdr32>(*v, o->f.cx, o->f.cy, nx, ny, dc_re, dc_im, c_re, c_im, radius);
+    return 0;
+}
+
+extern "C" int fsh_feature_pt_grid(const fsh_view *v, const fsh_orbit *o, int is64, uint32_t nx, uint32_t ny, void *in, void *radius)
+{
+    if (!v || !o || nx == 0 || ny == 0 || !in || !radius || (is64 != 0) != (o->is64 != 0))
+        return -1;
+    if (o->is64)
+        feature_pt_grid<double, fs_feature_in_hdr64, fs_real_hdr64>(*v, o->d.cx, o->d.cy, nx, ny, (fs_feature_in_hdr64 *)in, radius);
+    else
+        feature_pt_grid<float, fs_feature_in_hdr32, fs_real_hdr32>(*v, o->f.cx, o->f.cy, nx, ny, (fs_feature_in_hdr32 *)in, radius);
+    return 0;
+}
+
 // ------------------------------------------------------------------ T = float / double (fsh_feature_begin_plain*)
 // The same machine with the reference's plain T: C = FloatComplex<T>, HdrReduce empty, compares the plain operators,
 // T{HighPrecision} = mpf_get_d (which truncates) and then the cast (HighPrecision.h:497-506), HighPrecision{T} = mpf_set_d at the

@@ -263,6 +263,18 @@ fsh_feature *fsh_feature_begin_direct_at(const fsh_view *v, int is64, uint32_t p
  * not per point), *radius = its R.  in = nx * ny fs_feature_in_hdr32 / _hdr64, radius = fs_real_hdr32 / _hdr64 by is64.
  * 0, or -1 for bad arguments. */
 int fsh_feature_direct_grid(const fsh_view *v, int is64, uint32_t nx, uint32_t ny, void *in, void *radius);
+/* The find-round arguments of a PT scan over an nx x ny grid against orbit o, without the state machine.  is64 = the orbit's type
+ * (HDRFloat<double> / HDRFloat<float>), which selects the records as above.  The record of grid point (gx, gy) is separable:
+ * dc = C(T{cX(gx) - HiX}, T{cY(gy) - HiY}) reduced and c = C(T{cX(gx)}, T{cY(gy)}) reduced, so the high-precision arithmetic is
+ * done once per column and once per row.
+ * fsh_feature_pt_axes: the four axes as un-combined T values (fs_real_hdr32 / _hdr64): dc_re[nx], dc_im[ny], c_re[nx], c_im[ny];
+ * C(re, im) reduced (hc_from_hr, hc_reduced of csrc/hdr_math.hpp) of a column's and a row's values is the point's record.
+ * fsh_feature_pt_grid: in[gy * nx + gx] = the full record fsh_feature_begin's first batch holds for that grid point (period 0).
+ * *radius = the R fsh_feature_next_batch reports for the view.  0; -1 for a NULL argument, nx or ny zero, or an is64 that is
+ * not the orbit's type. */
+int fsh_feature_pt_axes(const fsh_view *v, const fsh_orbit *o, int is64, uint32_t nx, uint32_t ny, void *dc_re, void *dc_im,
+                        void *c_re, void *c_im, void *radius);
+int fsh_feature_pt_grid(const fsh_view *v, const fsh_orbit *o, int is64, uint32_t nx, uint32_t ny, void *in, void *radius);
 /* The same scans with the reference's plain T = float / double (the Feature Finder of the render algorithms whose MainType is
  * plain, FeatureFinder.cpp:2740-2795): records fs_feature_in_f32 / _f64 and fs_feature_out_f32 / _f64, R one float / double; the
  * batches are the arguments of fs_feature_eval_plain / fs_feature_eval_plain_direct calls.  T{HighPrecision} is mpf_get_d -- which
