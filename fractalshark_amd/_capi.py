@@ -255,6 +255,7 @@ def render_lib():
     _decl(lib, "fs_display_stream", vp, [vp])
     _decl(lib, "fs_colorize_frame", u32, [vp, vp, u64, vp, vp, vp])
     _decl(lib, "fs_color_buffer_elements", u64, [vp])
+    _decl(lib, "fs_read_color_buffer", u32, [vp, vp])
     _decl(lib, "fs_group_sync", u32, [vp])
     _decl(lib, "fs_group_wait_current", u32, [vp, u32])
     _decl(lib, "fs_group_gather_ms", C.c_float, [vp])
@@ -288,7 +289,7 @@ RENDER_SYMBOLS = [
     "fs_group_upload_orbit", "fs_group_upload_orbit_compressed", "fs_group_upload_la", "fs_group_upload_bla",
     "fs_group_upload_orbit_scaled", "fs_group_render_lav2", "fs_group_render_bla", "fs_group_render_scaled",
     "fs_group_render_direct", "fs_group_clear", "fs_group_render_current", "fs_group_render_current_colors", "fs_group_sync_display", "fs_display_stream", "fs_colorize_frame",
-    "fs_color_buffer_elements", "fs_group_sync", "fs_group_wait_current", "fs_group_gather_ms",
+    "fs_color_buffer_elements", "fs_read_color_buffer", "fs_group_sync", "fs_group_wait_current", "fs_group_gather_ms",
     "fs_group_plan", "fs_group_set_host_path", "fs_group_host_path", "fs_copy_bands_to_host", "fs_host_register", "fs_host_unregister",
 ]
 

@@ -108,6 +108,17 @@ uint32_t fs_colorize_frame(fs_renderer *r, const void *device_iters, uint64_t n_
 }
 uint64_t fs_color_buffer_elements(const fs_renderer *r) { return r->n_color_cu; }
 
+uint32_t fs_read_color_buffer(fs_renderer *r, fs_color16 *out)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (!r->memory_initialized() || !r->colors || !out)
+        return FS_ERR_6;
+    FS_TRY(hipMemcpyAsync(out, r->colors, r->n_color_cu * sizeof(fs_color16), hipMemcpyDeviceToHost, r->compute));
+    FS_TRY(hipStreamSynchronize(r->compute));
+    return 0;
+}
+
 // The renderer's bands -> their rows of a WHOLE-FRAME host buffer, over THIS device's own PCIe link (round 6; the sharded
 // read-back of the row-tiled frame: GPURenderer::ExtractItersAndColors, GPU_Render.cu:1760-1805, copies N_cu counts per frame
 // through one device).  The local buffer holds the owned bands back to back and band k belongs at frame row

@@ -152,6 +152,10 @@ uint32_t fs_read_ndz_bounds(fs_renderer *r, float *bounds_out, float *entries_ou
  * kernels over the current iteration buffer: ms_out[0] = antialias + palette, ms_out[1] = min / max / sum.  Needs a
  * palette (fs_init_memory) and the whole frame on this renderer.  tools/bench_render_current.py turns them into GB/s. */
 uint32_t fs_time_render_current(fs_renderer *r, uint64_t n_iterations, uint32_t repeats, float ms_out[2]);
+/* Test read-back: the renderer's own colour buffer as it stands (fs_color_buffer_elements Color16) to the host, without running
+ * the colour kernel first as fs_render_current does -- what an earlier call left in it (tests/current/torch_current.py:
+ * fs_colorize_frame with device_colors leaves it alone).  Synchronises the compute stream. */
+uint32_t fs_read_color_buffer(fs_renderer *r, fs_color16 *out);
 
 
 /* ---- read-backs of device-built tables (tests, tools) */

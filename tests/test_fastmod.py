@@ -1,6 +1,7 @@
 """CPU: the remainder shortcut of the palette lookup (fast_mod, fractalshark_amd/csrc/kernels_current.hip) restated in
 numpy with the same binary32 / uint32 operations, checked against the exact remainder over its whole contract
-(n < 2^32, 2^8 <= d < 2^24).  The GPU side is pinned by the colour tests (tests/test_gpu_goldens.py step 3)."""
+(n < 2^32, 2^8 <= d < 2^24).  The device fast_mod itself is pinned by tests/test_gpu_current.py: colour frames through
+k_antialias with palettes of 256, 257, 1792, 65536 and 2^24 - 1 entries and samples up to 2^32 - 1, against an exact model."""
 import numpy as np
 import pytest
 
