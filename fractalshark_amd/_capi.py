@@ -193,6 +193,10 @@ def render_lib():
     _decl(lib, "fs_render_exact_continue", u32, [vp, u64])
     _decl(lib, "fs_exact_kept_info", u32, [vp, C.POINTER(ExactKept)])
     _decl(lib, "fs_exact_drop_kept", u32, [vp])
+    _decl(lib, "fs_set_exact_periods", u32, [vp, C.c_int])
+    _decl(lib, "fs_read_exact_atom_periods", u32, [vp, vp, u64])
+    _decl(lib, "fs_read_exact_cycle_lengths", u32, [vp, vp, u64])
+    _decl(lib, "fs_set_exact_atom_key_bits", u32, [vp, u32])
     _decl(lib, "fs_render_bla", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_render_direct", u32, [vp, C.c_int, vp, u64])
     _decl(lib, "fs_upload_orbit_scaled", u32, [vp, C.c_int, u32, vp, vp, u64, u64])
@@ -279,6 +283,7 @@ RENDER_SYMBOLS = [
     "fs_exact_sample_counts", "fs_render_exact_wide", "fs_exact_wide_state", "fs_exact_audit",
     "fs_set_exact_cycle_check", "fs_read_exact_proved", "fs_read_exact_cycle_stats", "fs_set_exact_cycle_fingerprint_bits",
     "fs_set_exact_keep", "fs_render_exact_continue", "fs_exact_kept_info", "fs_exact_drop_kept",
+    "fs_set_exact_periods", "fs_read_exact_atom_periods", "fs_read_exact_cycle_lengths", "fs_set_exact_atom_key_bits",
     "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
     "fs_render_direct_lp", "fs_clear",

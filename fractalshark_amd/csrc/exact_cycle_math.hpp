@@ -33,8 +33,10 @@
 // stride and the slot pins the arithmetic behind it; it holds no instruction.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define FSX_PIN(v) asm volatile("" : "+v"(v))
+#define FSX_IN_ORDER() __builtin_amdgcn_sched_barrier(0) // the instruction scheduler moves nothing across this line; no instruction
 #else
 #define FSX_PIN(v) ((void)0)
+#define FSX_IN_ORDER() ((void)0)
 #endif
 
 namespace fsx {

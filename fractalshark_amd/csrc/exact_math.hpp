@@ -188,8 +188,10 @@ template <int L> FSX_HD void shift_floor(const uint32_t (&d)[2 * L], const Param
 }
 
 // The escape test on z = (x, y) and, when it has not escaped, the step to its successor.  Returns true (z unchanged) on escape.
-template <int L>
-FSX_HD bool step(uint32_t (&x)[L], uint32_t (&y)[L], const uint32_t (&cx)[L], const uint32_t (&cy)[L], const Params &P)
+// norm(xx, yy, w) is handed the untruncated 2L-limb squares and their sum w = x^2 + y^2 of a z that has passed the test, before w's
+// registers are used again (exact_atom_math.hpp keeps the smallest sum).
+template <int L, class F>
+FSX_HD bool step_with(uint32_t (&x)[L], uint32_t (&y)[L], const uint32_t (&cx)[L], const uint32_t (&cy)[L], const Params &P, F &&norm)
 {
     uint32_t ax[L], ay[L];
     const uint32_t sx = magnitude<L>(x, ax), sy = magnitude<L>(y, ay);
@@ -202,6 +204,7 @@ FSX_HD bool step(uint32_t (&x)[L], uint32_t (&y)[L], const uint32_t (&cx)[L], co
         w[i] = addc(xx[i], yy[i], c);
     if (exceeds<L>(w, P))
         return true;
+    norm(xx, yy, w);
     // x' = floor((x^2 - y^2) / 2^F) + cx
     c = 1; // xx + ~yy + 1
     FSX_UNROLL
@@ -225,6 +228,12 @@ FSX_HD bool step(uint32_t (&x)[L], uint32_t (&y)[L], const uint32_t (&cx)[L], co
     for (int i = 0; i < L; i++)
         y[i] = addc(y[i], cy[i], c);
     return false;
+}
+
+template <int L>
+FSX_HD bool step(uint32_t (&x)[L], uint32_t (&y)[L], const uint32_t (&cx)[L], const uint32_t (&cy)[L], const Params &P)
+{
+    return step_with<L>(x, y, cx, cy, P, [](const uint32_t (&)[2 * L], const uint32_t (&)[2 * L], const uint32_t (&)[2 * L]) {});
 }
 
 // The first n in 1 .. limit with |z_n|^2 > R (>= R), z_1 = c; 0 when there is none.  (Host loops and tests; the kernel keeps n itself.)

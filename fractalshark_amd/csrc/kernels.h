@@ -524,6 +524,9 @@ void fsk_az_tip_gather(const FsAzFrame &F, double max_dist, uint32_t ya, uint32_
 
 // ---- exact renderer (kernels_exact.hip): one slice of a frame's fixed-point iteration.  The running samples live in lists between
 // slices; the wide renderer below has the same lists.
+namespace fsx {
+struct AtomPlanes; // exact_atom_math.hpp
+}
 struct FsExactList {
     uint32_t *xy; // limb planes of x, then of y (stride slots each)
     uint64_t *n;  // (lane kernels without compaction: 0 = finished)
@@ -555,11 +558,16 @@ struct FsExactArgs {
     FsExactList park;
     uint32_t *park_count;
     uint32_t resume;
+    // the period planes (read by the P = true kernels only; fs_set_exact_periods, exact_atom_math.hpp), all per PIXEL y * W + x:
+    // where they are is a small block in device memory, so that the step loop carries one pointer and not four
+    const fsx::AtomPlanes *periods;
+    uint32_t atom_key_shift; // low bits the minimum's key drops (a test narrows the key), 0 = none
 };
 // samples: the list is W == H runs of their own, run e at cx[l * W + e], cy[l * W + e], and iters = uint64 counts[W] (fs_exact_audit)
-// cycle: the kernels with the cycle check.  keep: the kernels that park (frames only).  false: `limbs` is not an instantiated limb
-// count (nothing launched)
-bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, bool keep, hipStream_t s);
+// cycle: the kernels with the cycle check.  keep: the kernels that park (frames only).  periods: the kernels that leave the period
+// planes (frames only, not with keep).  false: `limbs` is not an instantiated limb count, or the combination has no kernel (nothing
+// launched)
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, bool keep, bool periods, hipStream_t s);
 // the pixels with proved[y * W + x] != 0 become `value` in a frame of `pitch` elements per row
 void fsk_exact_set_proved(void *iters, int iter_u64, const uint8_t *proved, uint32_t W, uint32_t H, uint32_t pitch, uint64_t value,
                           hipStream_t s);

@@ -29,9 +29,16 @@
 // one and the same slice, the last one, which has no survivor, and the host hands that slice's unused destination list in as the
 // park list (without compaction, a list of its own).  A.resume: the source list holds parked samples, which make their deferred n++
 // and cycle check (fsx::cycle_resume) before the step loop.  K = false compiles to what it was without the parameter.
+//
+// Period planes (P = true; fs_set_exact_periods, frames only, never with K; exact_atom_math.hpp holds the rule): every state that
+// passes the escape test with n <= cap hands its norm x^2 + y^2 -- the sum the escape test was made on -- to the rule, which keeps the
+// smallest per PIXEL: 2L limb planes of W * H, a key plane and the plane of the index it was taken at, A.atom.  State per pixel, not
+// per slot: the lists carry nothing new and compaction copies nothing new.  The lane holds the minimum's 64-bit key in two registers
+// (reloaded from the key plane at the start of a slice) and touches memory only when it takes a new minimum or the keys are equal.
+// With C, a proved sample also leaves n - t in A.cyclen.  P = false compiles to what it was without the parameter.
 #include <hip/hip_runtime.h>
 
-#include "exact_cycle_math.hpp"
+#include "exact_atom_math.hpp"
 #include "kernels.h"
 
 namespace {
@@ -45,7 +52,7 @@ template <bool S> __device__ __forceinline__ void write_count(const FsExactArgs 
         ((uint32_t *)A.iters)[out_idx] = (uint32_t)v;
 }
 
-template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
+template <int L, bool S, bool C, bool K, bool P> __global__ void __launch_bounds__(64) k_exact_slice(const FsExactArgs A)
 {
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     bool alive = i < A.n_src;
@@ -89,6 +96,17 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
         }
     }
 
+    // the key of the pixel's smallest norm so far (first slice: none yet, and the take at n = 1 asks for none)
+    uint64_t kmin = 0, cap1 = 0;
+    uint32_t atom_compares = 0, key_shift = 0; // (the read-backs are not reported)
+    if constexpr (P) {
+        if (!A.first)
+            kmin = A.periods->keys[pix];
+        key_shift = A.atom_key_shift, cap1 = A.cap + 1;
+        FSX_PIN(key_shift); // (vector registers: the scalar ones are what the largest instantiations run out of)
+        FSX_PIN(cap1);
+    }
+
     const size_t out_idx = S ? (size_t)pix : (size_t)row * A.rounded_width + col;
     uint32_t my_steps = 0, wave_steps = 0;
     bool parked = false;
@@ -108,8 +126,29 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
         wave_steps++;
         if (alive) {
             my_steps++;
-            const bool escaped = fsx::step<L>(x, y, cx, cy, A.P);
-            if (escaped || n == A.cap + 1) {
+            bool escaped;
+            if constexpr (P) {
+                // The limb offset of the floor shift in a vector register, made anew every step: as a loop invariant its L
+                // comparisons are L scalar register pairs held across the whole loop, and with this rule's own conditions the
+                // instantiations from L = 18 then spill scalar registers.  From there on the limb position of the bailout goes the
+                // same way (2L more invariants, the limbs the norm is compared with).
+                fsx::Params Pq = A.P;
+                FSX_PIN(Pq.q);
+                if constexpr (L >= 18) {
+                    FSX_PIN(Pq.bail_q);
+                    FSX_PIN(Pq.bail_lo);
+                    FSX_PIN(Pq.bail_hi);
+                    FSX_PIN(Pq.r);
+                }
+                escaped = fsx::step_with<L>(
+                    x, y, cx, cy, Pq, [&](const uint32_t(&xx)[2 * L], const uint32_t(&yy)[2 * L], const uint32_t(&w)[2 * L]) {
+                        // (z_{cap+1} is tested, not tracked)
+                        fsx::atom_track<L>(xx, yy, w, n, n != cap1, A.periods, pix, kmin, key_shift, atom_compares);
+                    });
+            } else {
+                escaped = fsx::step<L>(x, y, cx, cy, A.P);
+            }
+            if (escaped || n == (P ? cap1 : A.cap + 1)) {
                 write_count<S>(A, out_idx, escaped ? n - 1 : A.cap);
                 alive = false;
                 if constexpr (K)
@@ -122,6 +161,11 @@ template <int L, bool S, bool C, bool K> __global__ void __launch_bounds__(64) k
                         uint32_t p = pix;
                         FSX_PIN(p); // (the address is made here, not kept across the loop)
                         A.proved[p] = 1;
+                        if constexpr (P) {
+                            const fsx::AtomPlanes *planes = A.periods;
+                            FSX_PIN(planes);
+                            planes->cyclen[p] = fsx::cycle_length(n);
+                        }
                         my_proved = 1;
                         alive = false;
                     }
@@ -236,26 +280,30 @@ __global__ void __launch_bounds__(256) k_exact_mask(const T *__restrict__ centre
 
 } // namespace
 
-bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, bool keep, hipStream_t s)
+bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, bool keep, bool periods, hipStream_t s)
 {
-    if (keep && samples)
+    if ((keep && samples) || (periods && (keep || samples)))
         return false;
     const dim3 grid((A.n_src + 63u) / 64u), block(64);
     switch (limbs) {
 #define FS_EXACT_CASE(L)                                                                                                \
     case L:                                                                                                             \
-        if (keep && cycle)                                                                                              \
-            hipLaunchKernelGGL((k_exact_slice<L, false, true, true>), grid, block, 0, s, A);                            \
+        if (periods && cycle)                                                                                           \
+            hipLaunchKernelGGL((k_exact_slice<L, false, true, false, true>), grid, block, 0, s, A);                     \
+        else if (periods)                                                                                               \
+            hipLaunchKernelGGL((k_exact_slice<L, false, false, false, true>), grid, block, 0, s, A);                    \
+        else if (keep && cycle)                                                                                         \
+            hipLaunchKernelGGL((k_exact_slice<L, false, true, true, false>), grid, block, 0, s, A);                     \
         else if (keep)                                                                                                  \
-            hipLaunchKernelGGL((k_exact_slice<L, false, false, true>), grid, block, 0, s, A);                           \
+            hipLaunchKernelGGL((k_exact_slice<L, false, false, true, false>), grid, block, 0, s, A);                    \
         else if (cycle && samples)                                                                                      \
-            hipLaunchKernelGGL((k_exact_slice<L, true, true, false>), grid, block, 0, s, A);                            \
+            hipLaunchKernelGGL((k_exact_slice<L, true, true, false, false>), grid, block, 0, s, A);                     \
         else if (cycle)                                                                                                 \
-            hipLaunchKernelGGL((k_exact_slice<L, false, true, false>), grid, block, 0, s, A);                           \
+            hipLaunchKernelGGL((k_exact_slice<L, false, true, false, false>), grid, block, 0, s, A);                    \
         else if (samples)                                                                                               \
-            hipLaunchKernelGGL((k_exact_slice<L, true, false, false>), grid, block, 0, s, A);                           \
+            hipLaunchKernelGGL((k_exact_slice<L, true, false, false, false>), grid, block, 0, s, A);                    \
         else                                                                                                            \
-            hipLaunchKernelGGL((k_exact_slice<L, false, false, false>), grid, block, 0, s, A);                          \
+            hipLaunchKernelGGL((k_exact_slice<L, false, false, false, false>), grid, block, 0, s, A);                   \
         return true;
         FS_EXACT_FOR_EACH_L(FS_EXACT_CASE)
 #undef FS_EXACT_CASE

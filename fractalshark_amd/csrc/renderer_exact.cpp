@@ -1,6 +1,6 @@
 #include "renderer_state.hpp"
 
-#include "exact_cycle_math.hpp"
+#include "exact_atom_math.hpp"
 
 using namespace fsr;
 
@@ -8,21 +8,37 @@ using namespace fsr;
 // The device block of one call: [counter, statistics | cx | cy | `lists` lists of running samples], a list being the limb planes of
 // x and y, then n, then the sample's id; with the cycle check (`cycle`) a list ends with the limb planes of the checkpoints, and
 // the block with the byte plane of the proved samples (n_proved of them when that is not the lists' n: a continuation's lists hold
-// the kept samples, its plane the frame).
+// the kept samples, its plane the frame).  With the period planes (`periods` pixels, fs_set_exact_periods; 0: none) the block goes on,
+// per pixel: [2 * limbs limb planes of the smallest norm | its key | the atom period | with the cycle check, the cycle length];
+// the kernels find them through an fsx::AtomPlanes in the block's head.
 struct ExactLayout {
     static constexpr size_t head = 256;
     uint32_t slots; // of a list
     bool cycle;
     size_t cx_bytes, cy_bytes, xy_bytes, n_bytes, id_bytes, list_bytes, proved_bytes;
-    ExactLayout(uint32_t limbs, uint32_t nx, uint32_t ny, uint32_t n, bool cycle_ = false, uint32_t n_proved = 0) : slots(n), cycle(cycle_)
+    size_t min_bytes, plane_bytes; // the period planes: the minimum's limb planes, one uint64 plane; 0 without them
+    ExactLayout(uint32_t limbs, uint32_t nx, uint32_t ny, uint32_t n, bool cycle_ = false, uint32_t n_proved = 0, uint32_t periods = 0)
+        : slots(n), cycle(cycle_)
     {
         auto up = [](size_t b) { return (b + 255) / 256 * 256; };
         cx_bytes = up((size_t)limbs * nx * 4), cy_bytes = up((size_t)limbs * ny * 4);
         xy_bytes = up((size_t)2 * limbs * n * 4), n_bytes = up((size_t)n * 8), id_bytes = up((size_t)n * 4);
         list_bytes = xy_bytes + n_bytes + id_bytes + (cycle ? xy_bytes : 0);
         proved_bytes = cycle ? up(n_proved ? n_proved : n) : 0;
+        min_bytes = periods ? up((size_t)2 * limbs * periods * 4) : 0, plane_bytes = periods ? up((size_t)periods * 8) : 0;
     }
-    size_t bytes(int lists) const { return head + cx_bytes + cy_bytes + (size_t)lists * list_bytes + proved_bytes; }
+    size_t bytes(int lists) const
+    {
+        return head + cx_bytes + cy_bytes + (size_t)lists * list_bytes + proved_bytes + min_bytes + (cycle ? 3 : 2) * plane_bytes;
+    }
+    static constexpr size_t planes_at = 128; // (behind the counters and the statistics)
+    fsx::AtomPlanes *period_planes(char *blk) const { return (fsx::AtomPlanes *)(blk + planes_at); }
+    uint32_t *atom_min(char *blk, int lists) const { return (uint32_t *)(list_base(blk, lists) + proved_bytes); }
+    // k = 0: the keys, 1: the atom periods, 2: the cycle lengths
+    uint64_t *period_plane(char *blk, int lists, int k) const
+    {
+        return (uint64_t *)(list_base(blk, lists) + proved_bytes + min_bytes + (size_t)k * plane_bytes);
+    }
     // the parts of the list that starts at `base`
     FsExactList at(char *base) const
     {
@@ -114,6 +130,7 @@ struct ExactRun {
     uint64_t cap;
     bool cycle;              // the cycle check (lane path only): the C = true kernels run and the lists carry the checkpoints
     bool read_proved;        // with the check: the call's proved mask becomes the one fs_read_exact_proved returns
+    bool periods;            // fs_render_exact with fs_set_exact_periods: the P = true kernels run and the period planes come back
     ExactMode mode;          // frames only
 };
 
@@ -169,7 +186,7 @@ static void exact_add_stats(fs_renderer::Exact &X, const unsigned long long st[4
 }
 static bool exact_lane_launch(const ExactRun &R, const FsExactArgs &A, bool cycle, bool keep, hipStream_t s)
 {
-    return fsk_exact_slice(A, R.limbs, R.W == 0, cycle, keep, s);
+    return fsk_exact_slice(A, R.limbs, R.W == 0, cycle, keep, R.periods, s);
 }
 static const ExactPath kExactLane = {exact_lane_launch, exact_default_slice, exact_add_stats, true, false};
 
@@ -229,7 +246,8 @@ static ExactResult exact_run(fs_renderer *r, const ExactRun &R)
     const bool keep = R.mode != kExactPlain, resume = R.mode == kExactResume, cycle = R.cycle;
     const fs_renderer::ExactKept K0 = X.kept;
     const uint32_t n = R.n, npix = R.W ? R.nx * R.ny : n;
-    const ExactLayout Y = resume ? K0.layout() : ExactLayout(R.limbs, R.nx, R.ny, n, cycle, npix);
+    const bool periods = R.periods && !keep && R.W != 0;
+    const ExactLayout Y = resume ? K0.layout() : ExactLayout(R.limbs, R.nx, R.ny, n, cycle, npix, periods ? npix : 0);
     const bool compact = !(P.fixed_slots && X.no_compaction);
     const int n_lists = compact || keep ? 2 : 1;
     char *blk = nullptr;
@@ -260,10 +278,23 @@ static ExactResult exact_run(fs_renderer *r, const ExactRun &R)
         A.proved = resume ? Y.proved(K0.blk, 1) : Y.proved(blk, n_lists);
         fsx::cycle_masks(X.cycle_fp_bits, A.fp_mx, A.fp_my);
     }
+    static_assert(ExactLayout::planes_at + sizeof(fsx::AtomPlanes) <= ExactLayout::head && ExactLayout::planes_at >= 16 + 4 * 8, "the head");
+    fsx::AtomPlanes planes{}; // (read by the copy below, which the first slice's synchronisation ends)
+    if (periods) {
+        planes.mn = Y.atom_min(blk, n_lists), planes.keys = Y.period_plane(blk, n_lists, 0);
+        planes.atom = Y.period_plane(blk, n_lists, 1), planes.cyclen = cycle ? Y.period_plane(blk, n_lists, 2) : nullptr;
+        planes.stride = npix;
+        A.periods = Y.period_planes(blk);
+        A.atom_key_shift = fsx::atom_key_shift(X.atom_key_bits);
+    }
 
     e = hipMemsetAsync(blk, 0, Y.head, s);
     if (e == hipSuccess && cycle && !resume)
         e = hipMemsetAsync(A.proved, 0, npix, s);
+    if (e == hipSuccess && periods) // (the atom plane and, behind it, the cycle lengths)
+        e = hipMemsetAsync(planes.atom, 0, (cycle ? 2 : 1) * Y.plane_bytes, s);
+    if (e == hipSuccess && periods)
+        e = hipMemcpyAsync(Y.period_planes(blk), &planes, sizeof planes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && resume && K0.proved != 0) { // (a sample the continuation proves writes the new cap itself)
         fsk_exact_set_proved(R.out, (int)R.out_u64, A.proved, R.nx, R.ny, R.out_pitch, R.cap, s);
         e = hipGetLastError();
@@ -309,8 +340,18 @@ static ExactResult exact_run(fs_renderer *r, const ExactRun &R)
         X.proved.resize(npix);
         e = hipMemcpyAsync(X.proved.data(), A.proved, npix, hipMemcpyDeviceToHost, s);
     }
+    if (e == hipSuccess && periods) {
+        X.atom.resize(npix);
+        e = hipMemcpyAsync(X.atom.data(), planes.atom, (size_t)npix * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && cycle) {
+            X.cyclen.resize(npix);
+            e = hipMemcpyAsync(X.cyclen.data(), planes.cyclen, (size_t)npix * 8, hipMemcpyDeviceToHost, s);
+        }
+    }
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);
+    if (periods)
+        X.atom_valid = e == hipSuccess, X.cyclen_valid = cycle && e == hipSuccess;
     P.add_stats(X, st);
     X.stats[2] += slices, X.stats[3] += after_first;
     if (cycle && R.read_proved)
@@ -480,6 +521,46 @@ uint32_t fs_read_exact_proved(const fs_renderer *r, uint8_t *out, uint64_t n)
     return 0;
 }
 
+uint32_t fs_set_exact_periods(fs_renderer *r, int enable)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    r->exact.periods = enable != 0;
+    return 0;
+}
+
+uint32_t fs_set_exact_atom_key_bits(fs_renderer *r, uint32_t bits)
+{
+    if (!r)
+        return hipErrorInvalidValue;
+    r->exact.atom_key_bits = bits;
+    return 0;
+}
+
+static uint32_t exact_read_plane(const std::vector<uint64_t> &plane, bool valid, uint64_t *out, uint64_t n)
+{
+    if (!valid)
+        return FS_ERR_6;
+    if (n != plane.size())
+        return hipErrorInvalidValue;
+    memcpy(out, plane.data(), (size_t)n * 8);
+    return 0;
+}
+
+uint32_t fs_read_exact_atom_periods(const fs_renderer *r, uint64_t *out, uint64_t n)
+{
+    if (!r || !out)
+        return hipErrorInvalidValue;
+    return exact_read_plane(r->exact.atom, r->exact.atom_valid, out, n);
+}
+
+uint32_t fs_read_exact_cycle_lengths(const fs_renderer *r, uint64_t *out, uint64_t n)
+{
+    if (!r || !out)
+        return hipErrorInvalidValue;
+    return exact_read_plane(r->exact.cyclen, r->exact.cyclen_valid, out, n);
+}
+
 uint32_t fs_render_exact(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
                          uint32_t bailout, int inclusive, uint64_t n_iterations)
 {
@@ -492,10 +573,14 @@ uint32_t fs_render_exact(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits
         return (uint32_t)hipErrorInvalidValue;
     if (!exact_axes_in_range(cx, r->width, cy, r->height, limbs, frac_bits))
         return FS_ERR_UNSUPPORTED;
+    if (r->exact.periods && r->exact.keep) // (a kept sample's minimum would have to travel with it: not built)
+        return FS_ERR_UNSUPPORTED;
     r->exact.reset_stats();
+    r->exact.atom_valid = r->exact.cyclen_valid = false;
     exact_drop_kept(r);
     ExactRun R = exact_frame_run(r, kExactLane, frac_bits, limbs, cx, cy, bailout, inclusive, n_iterations, r->iters());
     R.cycle = r->exact.cycle_check, R.read_proved = true, R.mode = r->exact.keep ? kExactKeep : kExactPlain;
+    R.periods = r->exact.periods;
     return exact_run(r, R).rc;
 }
 

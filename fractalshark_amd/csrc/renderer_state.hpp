@@ -209,6 +209,10 @@ struct fs_renderer {
         bool proved_valid = false;   // ... when the last exact call ran with the check on
         bool keep = false;           // fs_set_exact_keep: the two exact renderers leave a kept set for fs_render_exact_continue
         ExactKept kept;
+        bool periods = false;        // fs_set_exact_periods: fs_render_exact leaves the period planes (read by no other entry point)
+        uint32_t atom_key_bits = 0;  // fs_set_exact_atom_key_bits (tests): top bits the minimum's key keeps, 0 = all 64
+        std::vector<uint64_t> atom, cyclen; // fs_read_exact_atom_periods, fs_read_exact_cycle_lengths: the planes of the last ...
+        bool atom_valid = false, cyclen_valid = false; // ... fs_render_exact, when it ran with the switch (and the cycle check) on
         // What every exact entry point does to the statistics before it starts.  keep_proved: the call leaves the mask of
         // fs_read_exact_proved as it is (the shifted frames of fs_exact_stable_mask with the check on).
         void reset_stats(bool keep_proved = false)

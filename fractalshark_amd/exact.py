@@ -111,6 +111,46 @@ def render(renderer, view, bailout=4, frac_bits=None, iter_bytes=4, inclusive=Fa
     return _proved(renderer).reshape(cy.shape[1], cx.shape[1]) if prove_interior else None
 
 
+class _periods:
+    """The period planes on for the duration of a call, off again behind it."""
+
+    def __init__(self, renderer):
+        self.renderer = renderer
+
+    def __enter__(self):
+        _check(self.renderer, self.renderer.SetExactPeriods(True), "fs_set_exact_periods")
+
+    def __exit__(self, *exc):
+        self.renderer.SetExactPeriods(False)
+
+
+def render_periods(renderer, view, bailout=4, frac_bits=None, iter_bytes=4, inclusive=False, prove_interior=False, cap=None):
+    """render with the period planes (fs_set_exact_periods; DESIGN.md 6.3 "Period planes"): the exact family's own period map, at any
+    depth up to 24 limbs with no reference orbit.  Returns (frame, atom) or, with prove_interior, (frame, atom, cycle_length), numpy
+    arrays [H, W]: the frame as read from the iteration buffer -- byte for byte render's -- the atom period of every pixel (uint64:
+    the index n at which |z_n| is smallest among the states that passed the escape test within the cap, ties to the earliest; 0 where
+    c itself escapes) and the cycle length of every pixel the cycle check proved (uint64, 0 elsewhere; a multiple of the cycle's
+    period).  cap: in place of view.num_iterations.  Not the Feature Finder's trigger: see features.period_map / pt_grid for that."""
+    F = view.precision_bits + GUARD_BITS if frac_bits is None else int(frac_bits)
+    if uses_wide(limbs_for(F)):
+        raise ValueError("render_periods: %d fractional bits need more than %d limbs; the wide path has no period planes" % (F, MAX_LIMBS))
+    cap = view.num_iterations if cap is None else int(cap)
+    with _periods(renderer):
+        render(renderer, view, bailout, F, iter_bytes, inclusive, prove_interior, n_iterations=cap)
+    h, w = renderer.GetHeight(), renderer.GetWidth()
+    out = renderer.new_iter_buffer()
+    _check(renderer, renderer.RenderCurrent(cap, out), "fs_render_current")
+    _check(renderer, renderer.SyncComputeStream(), "fs_sync_compute")
+    err, atom = renderer.ExactAtomPeriods()
+    _check(renderer, err, "fs_read_exact_atom_periods")
+    planes = (out[:h, :w].copy(), atom.reshape(h, w))
+    if prove_interior:
+        err, lengths = renderer.ExactCycleLengths()
+        _check(renderer, err, "fs_read_exact_cycle_lengths")
+        planes += (lengths.reshape(h, w),)
+    return planes
+
+
 def continue_render(renderer, n_iterations):
     """The kept frame in the iteration buffer raised to the cap n_iterations (fs_render_exact_continue): afterwards the buffer is
     what render writes with that cap, and the kept set is that cap's, so calls chain.  Path, number format, bailout and cycle check
@@ -263,6 +303,7 @@ def stable_mask(renderer, view, level, bailout=4, frac_bits=None, prove_interior
     return mask.astype(bool)
 
 
-__all__ = ["GUARD_BITS", "MAX_FRAC_BITS", "MAX_WIDE_LIMBS", "MAX_WIDE_FRAC_BITS", "limbs_for", "axes", "render", "continue_render",
+__all__ = ["GUARD_BITS", "MAX_FRAC_BITS", "MAX_WIDE_LIMBS", "MAX_WIDE_FRAC_BITS", "limbs_for", "axes", "render", "render_periods",
+           "continue_render",
            "render_progressive", "uses_wide",
            "sample_counts", "stable_mask", "lattice", "audit", "AuditReport"]

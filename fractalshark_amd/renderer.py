@@ -283,6 +283,30 @@ class GPURenderer:
         """Test hook (fs_set_exact_cycle_fingerprint_bits): low bits of the checkpoint's fingerprint, 0 = all 64."""
         return self._lib.fs_set_exact_cycle_fingerprint_bits(self._h, int(bits))
 
+    def SetExactPeriods(self, enable):
+        """fs_set_exact_periods: RenderExact leaves the atom-period plane and, with the cycle check on, the cycle-length plane
+        besides the frame; off by default.  Changes no pixel.  FS_ERR_UNSUPPORTED from RenderExact when keeping is on as well."""
+        return self._lib.fs_set_exact_periods(self._h, 1 if enable else 0)
+
+    def _exact_plane(self, read, n):
+        n = self.GetWidth() * self.GetHeight() if n is None else int(n)
+        out = np.zeros(n, np.uint64)
+        return read(self._h, out.ctypes.data, n), out
+
+    def ExactAtomPeriods(self, n=None):
+        """fs_read_exact_atom_periods: (error code, uint64[n]) -- per pixel of the last RenderExact (n = W * H, the default,
+        row-major) the index of the smallest |z_n|; FS_ERR_6 when that call ran with the periods switch off."""
+        return self._exact_plane(self._lib.fs_read_exact_atom_periods, n)
+
+    def ExactCycleLengths(self, n=None):
+        """fs_read_exact_cycle_lengths: (error code, uint64[n]) -- per pixel of the last RenderExact the cycle length its proof
+        showed, 0 where it was not proved; FS_ERR_6 unless that call ran with the periods switch and the cycle check on."""
+        return self._exact_plane(self._lib.fs_read_exact_cycle_lengths, n)
+
+    def SetExactAtomKeyBits(self, bits):
+        """Test hook (fs_set_exact_atom_key_bits): top bits the key of a pixel's smallest norm keeps, 0 = all 64."""
+        return self._lib.fs_set_exact_atom_key_bits(self._h, int(bits))
+
     def SetExactKeep(self, enable):
         """fs_set_exact_keep: RenderExact and RenderExactWide leave the samples that reach the cap on the device, for
         RenderExactContinue; off by default."""

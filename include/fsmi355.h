@@ -443,6 +443,27 @@ uint32_t fs_render_exact_continue(fs_renderer *r, uint64_t n_iterations);
 uint32_t fs_exact_kept_info(const fs_renderer *r, fs_exact_kept *out);
 uint32_t fs_exact_drop_kept(fs_renderer *r);
 
+/* Period planes: the exact family's own period map (DESIGN.md 6.3 "Period planes").  n is the index of the z a sample holds,
+ * z_1 = c; a pixel's value is v = min(E - 1, n_iterations).  Both planes are integers defined on the exact recurrence; they are NOT
+ * the Feature Finder's trigger |z|^2 < R^2 |dzdc|^2 and claim no equality with its evaluators.
+ * Atom period A: the n in 1 .. v with the smallest untruncated norm x_n^2 + y_n^2 (the 2 * limbs-limb sum the escape test is made
+ * on), ties to the earliest n; 0 when v = 0.  Only states that passed the escape test with n <= n_iterations are tracked, so
+ * A <= v.  Inside the atom domain of a period-p nucleus it is p.  A does not depend on the cycle check, the slices or compaction.
+ * Cycle length: for a sample the cycle check proves at index n, n - t, t the index its checkpoint was taken at (the largest power
+ * of two below n): a multiple of the cycle's period.  0 for a sample that is not proved.
+ * fs_set_exact_periods: enable = 1 makes fs_render_exact (up to 24 limbs) leave the atom plane and, with the cycle check on, the
+ * cycle-length plane besides the frame, which is byte for byte the frame without the switch; the call's device block grows by
+ * 2 * limbs + 4 (+ 2 with the cycle check) words per pixel.  0, the default: the same kernels run as without this function and
+ * nothing more is allocated.  With the switch AND fs_set_exact_keep on, fs_render_exact returns FS_ERR_UNSUPPORTED before it touches
+ * the frame or the kept set.  Every other exact entry point -- fs_exact_stable_mask, fs_exact_sample_counts, fs_exact_audit,
+ * fs_render_exact_wide, fs_render_exact_continue -- ignores the switch and leaves the planes of the last fs_render_exact alone.
+ * fs_read_exact_atom_periods / fs_read_exact_cycle_lengths: out[n] (host), n = W * H of fs_init_memory, row-major.  FS_ERR_6: the
+ * last fs_render_exact ran with the switch off (the cycle lengths: with the switch or the cycle check off), failed, or there was
+ * none; hipErrorInvalidValue: NULL, or n is not the plane's size. */
+uint32_t fs_set_exact_periods(fs_renderer *r, int enable);
+uint32_t fs_read_exact_atom_periods(const fs_renderer *r, uint64_t *out, uint64_t n);
+uint32_t fs_read_exact_cycle_lengths(const fs_renderer *r, uint64_t *out, uint64_t n);
+
 /* GPURenderer::ClearMemory<IterType> (GPU_Render.cu:212-225). */
 uint32_t fs_clear(fs_renderer *r);
 

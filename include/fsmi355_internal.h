@@ -128,6 +128,11 @@ uint32_t fs_exact_wide_state(fs_renderer *r, uint32_t frac_bits, uint32_t limbs,
  * one step in 2^bits; 0 = the default, all 64.  Changes no result. */
 uint32_t fs_read_exact_cycle_stats(const fs_renderer *r, uint64_t out[2]);
 uint32_t fs_set_exact_cycle_fingerprint_bits(fs_renderer *r, uint32_t bits);
+/* The period planes of the exact renderer (fs_set_exact_periods of fsmi355.h).
+ * fs_set_exact_atom_key_bits (test hook): a lane reads a pixel's smallest norm back only when the 64-bit key of the new norm equals
+ * the key of the minimum.  bits = 6 .. 63 keeps that many top bits of the key (below 6: 6, the index of the highest limb that is not
+ * zero alone) and makes the full compare run, and answer "not less", often; 0 = the default, all 64.  Changes no result. */
+uint32_t fs_set_exact_atom_key_bits(fs_renderer *r, uint32_t bits);
 uint32_t fs_enable_step_count(fs_renderer *r, int enable);
 uint32_t fs_read_step_count(fs_renderer *r, uint64_t counts[8]);
 /* The whole statistics buffer (measurement builds append per-wave trace records behind the 8 counters: library built
