@@ -26,6 +26,10 @@
 // of the minimum is kept in a plane of its own (keys[pix]) so that a slice reloads two registers, not 2L limbs.  `shift` drops the
 // key's low bits (monotone still): 0 in the product; a test raises it, at most to kAtomMaxKeyShift where only h is left, to make the
 // full compare run -- and answer "not less" -- often.
+//
+// Point runs (DESIGN.md 6.3 "Point runs"; fs_exact_eval_points, the S = true, P = true instantiations): the same rule on a list of
+// runs with a length each in place of the cap, the period state per run, and the state z_len of every run that reaches its length
+// left in end planes (point_end; the host loop is point_run).
 #ifndef FS_EXACT_ATOM_MATH_HPP
 #define FS_EXACT_ATOM_MATH_HPP
 
@@ -41,6 +45,7 @@ struct AtomPlanes {
     uint64_t *atom;   // [stride]: the index the minimum was taken at; zeroed by the caller
     uint64_t *cyclen; // [stride], with the cycle check: n - t of a proved sample; zeroed by the caller
     uint32_t stride;  // pixels
+    uint32_t *end;    // point runs only (fs_exact_eval_points): 2L limb planes of `stride` runs, x then y: z_len; zeroed by the caller
 };
 
 // the shift that leaves the `bits` top bits of the key; 0 (and anything from 64 up) = all of them, below 6 = 6
@@ -141,6 +146,22 @@ FSX_HD bool atom_track(const uint32_t (&xx)[2 * L], const uint32_t (&yy)[2 * L],
     return take;
 }
 
+// Point runs (fs_exact_eval_points; the S = true, P = true instantiations): run e has a length of its own, len[e], where a frame has its
+// cap, and leaves the state it holds when it passes the escape test with n == len[e] -- z_len, before the step advances it -- in the
+// end planes.  A run that escapes at or before len[e] leaves them as the caller zeroed them.
+template <int L> FSX_HD void point_end(const uint32_t (&x)[L], const uint32_t (&y)[L], const AtomPlanes *planes, uint32_t e)
+{
+    FSX_PIN(planes); // (as atom_take: what is read through it stays out of the scalar registers)
+    FSX_PIN(e);
+    uint32_t *end = planes->end;
+    const uint32_t stride = planes->stride;
+    FSX_UNROLL
+    for (int l = 0; l < L; l++) {
+        end[(size_t)l * stride + e] = x[l];
+        end[(size_t)(L + l) * stride + e] = y[l];
+    }
+}
+
 struct AtomRun {
     uint32_t outcome;  // kCycleEscaped: value = E - 1; kCycleCapped, kCycleProved: value = cap
     uint64_t value;
@@ -184,6 +205,44 @@ FSX_HD AtomRun atom_run(const uint32_t (&cx)[L], const uint32_t (&cy)[L], const 
         }
     }
     R.atom = atom, R.compares = compares;
+    return R;
+}
+
+struct PointRun {
+    uint64_t value; // v = min(E - 1, len)
+    uint64_t atom;  // A over z_1 .. z_v
+    uint64_t steps; // calls of step()
+};
+
+// One point run from z_1 = c to its end: the loop of k_exact_slice<L, true, false, false, true> without the slices.  end: the 2L
+// limbs of z_len, x then y, all zero when v < len.  (Host loops and tests.)
+template <int L>
+FSX_HD PointRun point_run(const uint32_t (&cx)[L], const uint32_t (&cy)[L], const Params &P, uint64_t len, uint32_t shift,
+                          uint32_t (&end)[2 * L])
+{
+    uint32_t x[L], y[L], mn[2 * L], compares = 0;
+    uint64_t n = 1, kmin = 0, key_plane = 0, atom = 0;
+    const AtomPlanes planes{mn, &key_plane, &atom, nullptr, 1, end};
+    const uint64_t cap1 = len + 1;
+    PointRun R{len, 0, 0};
+    FSX_UNROLL
+    for (int i = 0; i < L; i++)
+        x[i] = cx[i], y[i] = cy[i], end[i] = end[L + i] = 0;
+    for (;;) {
+        R.steps++;
+        const bool escaped =
+            step_with<L>(x, y, cx, cy, P, [&](const uint32_t (&xx)[2 * L], const uint32_t (&yy)[2 * L], const uint32_t (&w)[2 * L]) {
+                if (n + 1 == cap1)
+                    point_end<L>(x, y, &planes, 0);
+                atom_track<L>(xx, yy, w, n, n != cap1, &planes, 0, kmin, shift, compares);
+            });
+        if (escaped || n == cap1) {
+            R.value = escaped ? n - 1 : len;
+            break;
+        }
+        n++;
+    }
+    R.atom = atom;
     return R;
 }
 

@@ -562,11 +562,14 @@ struct FsExactArgs {
     // where they are is a small block in device memory, so that the step loop carries one pointer and not four
     const fsx::AtomPlanes *periods;
     uint32_t atom_key_shift; // low bits the minimum's key drops (a test narrows the key), 0 = none
+    // point runs (read by the S = true, P = true kernels only; fs_exact_eval_points): run e stops at lengths[e] >= 1 instead of cap,
+    // its period state is per run (periods->stride = W), and z_lengths[e] goes to periods->end
+    const uint64_t *lengths;
 };
 // samples: the list is W == H runs of their own, run e at cx[l * W + e], cy[l * W + e], and iters = uint64 counts[W] (fs_exact_audit)
 // cycle: the kernels with the cycle check.  keep: the kernels that park (frames only).  periods: the kernels that leave the period
-// planes (frames only, not with keep).  false: `limbs` is not an instantiated limb count, or the combination has no kernel (nothing
-// launched)
+// planes (not with keep); with samples, the point runs of fs_exact_eval_points (not with cycle).  false: `limbs` is not an
+// instantiated limb count, or the combination has no kernel (nothing launched)
 bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, bool keep, bool periods, hipStream_t s);
 // the pixels with proved[y * W + x] != 0 become `value` in a frame of `pitch` elements per row
 void fsk_exact_set_proved(void *iters, int iter_u64, const uint8_t *proved, uint32_t W, uint32_t H, uint32_t pitch, uint64_t value,

@@ -36,6 +36,12 @@
 // per slot: the lists carry nothing new and compaction copies nothing new.  The lane holds the minimum's 64-bit key in two registers
 // (reloaded from the key plane at the start of a slice) and touches memory only when it takes a new minimum or the keys are equal.
 // With C, a proved sample also leaves n - t in A.cyclen.  P = false compiles to what it was without the parameter.
+//
+// Point runs (S = true and P = true, never with C or K; fs_exact_eval_points): a list of runs, the period state per RUN (sample
+// mode's addressing, W = H = n runs), and two things more.  Run e stops at A.lengths[e] where a frame stops at A.cap: cap + 1, which
+// the P kernels hold in a vector register, is lengths[e] + 1.  And the state that passes the escape test with n == lengths[e] goes to
+// the end planes (fsx::point_end): plain vector stores, once per run, before the step advances the state.  Runs of different lengths
+// leave the list at different slices; the compaction closes the gaps as it does behind escapes.
 #include <hip/hip_runtime.h>
 
 #include "exact_atom_math.hpp"
@@ -102,7 +108,7 @@ template <int L, bool S, bool C, bool K, bool P> __global__ void __launch_bounds
     if constexpr (P) {
         if (!A.first)
             kmin = A.periods->keys[pix];
-        key_shift = A.atom_key_shift, cap1 = A.cap + 1;
+        key_shift = A.atom_key_shift, cap1 = (S ? A.lengths[pix] : A.cap) + 1;
         FSX_PIN(key_shift); // (vector registers: the scalar ones are what the largest instantiations run out of)
         FSX_PIN(cap1);
     }
@@ -142,6 +148,10 @@ template <int L, bool S, bool C, bool K, bool P> __global__ void __launch_bounds
                 }
                 escaped = fsx::step_with<L>(
                     x, y, cx, cy, Pq, [&](const uint32_t(&xx)[2 * L], const uint32_t(&yy)[2 * L], const uint32_t(&w)[2 * L]) {
+                        if constexpr (S) {
+                            if (n + 1 == cap1)
+                                fsx::point_end<L>(x, y, A.periods, pix);
+                        }
                         // (z_{cap+1} is tested, not tracked)
                         fsx::atom_track<L>(xx, yy, w, n, n != cap1, A.periods, pix, kmin, key_shift, atom_compares);
                     });
@@ -149,7 +159,7 @@ template <int L, bool S, bool C, bool K, bool P> __global__ void __launch_bounds
                 escaped = fsx::step<L>(x, y, cx, cy, A.P);
             }
             if (escaped || n == (P ? cap1 : A.cap + 1)) {
-                write_count<S>(A, out_idx, escaped ? n - 1 : A.cap);
+                write_count<S>(A, out_idx, escaped ? n - 1 : (S && P ? cap1 - 1 : A.cap));
                 alive = false;
                 if constexpr (K)
                     parked = !escaped;
@@ -282,13 +292,15 @@ __global__ void __launch_bounds__(256) k_exact_mask(const T *__restrict__ centre
 
 bool fsk_exact_slice(const FsExactArgs &A, uint32_t limbs, bool samples, bool cycle, bool keep, bool periods, hipStream_t s)
 {
-    if ((keep && samples) || (periods && (keep || samples)))
+    if ((keep && samples) || (periods && keep) || (periods && samples && cycle))
         return false;
     const dim3 grid((A.n_src + 63u) / 64u), block(64);
     switch (limbs) {
 #define FS_EXACT_CASE(L)                                                                                                \
     case L:                                                                                                             \
-        if (periods && cycle)                                                                                           \
+        if (periods && samples)                                                                                         \
+            hipLaunchKernelGGL((k_exact_slice<L, true, false, false, true>), grid, block, 0, s, A);                     \
+        else if (periods && cycle)                                                                                      \
             hipLaunchKernelGGL((k_exact_slice<L, false, true, false, true>), grid, block, 0, s, A);                     \
         else if (periods)                                                                                               \
             hipLaunchKernelGGL((k_exact_slice<L, false, false, false, true>), grid, block, 0, s, A);                    \

@@ -10,14 +10,17 @@ using namespace fsr;
 // the block with the byte plane of the proved samples (n_proved of them when that is not the lists' n: a continuation's lists hold
 // the kept samples, its plane the frame).  With the period planes (`periods` pixels, fs_set_exact_periods; 0: none) the block goes on,
 // per pixel: [2 * limbs limb planes of the smallest norm | its key | the atom period | with the cycle check, the cycle length];
-// the kernels find them through an fsx::AtomPlanes in the block's head.
+// the kernels find them through an fsx::AtomPlanes in the block's head.  Point runs (`points`, fs_exact_eval_points; their period
+// planes are per run) add behind those: [the runs' lengths | 2 * limbs limb planes of the endpoints].
 struct ExactLayout {
     static constexpr size_t head = 256;
     uint32_t slots; // of a list
     bool cycle;
     size_t cx_bytes, cy_bytes, xy_bytes, n_bytes, id_bytes, list_bytes, proved_bytes;
     size_t min_bytes, plane_bytes; // the period planes: the minimum's limb planes, one uint64 plane; 0 without them
-    ExactLayout(uint32_t limbs, uint32_t nx, uint32_t ny, uint32_t n, bool cycle_ = false, uint32_t n_proved = 0, uint32_t periods = 0)
+    size_t len_bytes, end_bytes;   // point runs: the lengths, the endpoints' limb planes; 0 without them
+    ExactLayout(uint32_t limbs, uint32_t nx, uint32_t ny, uint32_t n, bool cycle_ = false, uint32_t n_proved = 0, uint32_t periods = 0,
+                bool points = false)
         : slots(n), cycle(cycle_)
     {
         auto up = [](size_t b) { return (b + 255) / 256 * 256; };
@@ -26,10 +29,12 @@ struct ExactLayout {
         list_bytes = xy_bytes + n_bytes + id_bytes + (cycle ? xy_bytes : 0);
         proved_bytes = cycle ? up(n_proved ? n_proved : n) : 0;
         min_bytes = periods ? up((size_t)2 * limbs * periods * 4) : 0, plane_bytes = periods ? up((size_t)periods * 8) : 0;
+        len_bytes = points ? up((size_t)n * 8) : 0, end_bytes = points ? up((size_t)2 * limbs * n * 4) : 0;
     }
     size_t bytes(int lists) const
     {
-        return head + cx_bytes + cy_bytes + (size_t)lists * list_bytes + proved_bytes + min_bytes + (cycle ? 3 : 2) * plane_bytes;
+        return head + cx_bytes + cy_bytes + (size_t)lists * list_bytes + proved_bytes + min_bytes + (cycle ? 3 : 2) * plane_bytes +
+               len_bytes + end_bytes;
     }
     static constexpr size_t planes_at = 128; // (behind the counters and the statistics)
     fsx::AtomPlanes *period_planes(char *blk) const { return (fsx::AtomPlanes *)(blk + planes_at); }
@@ -39,6 +44,8 @@ struct ExactLayout {
     {
         return (uint64_t *)(list_base(blk, lists) + proved_bytes + min_bytes + (size_t)k * plane_bytes);
     }
+    uint64_t *lengths(char *blk, int lists) const { return period_plane(blk, lists, cycle ? 3 : 2); }
+    uint32_t *ends(char *blk, int lists) const { return (uint32_t *)((char *)lengths(blk, lists) + len_bytes); }
     // the parts of the list that starts at `base`
     FsExactList at(char *base) const
     {
@@ -132,6 +139,12 @@ struct ExactRun {
     bool read_proved;        // with the check: the call's proved mask becomes the one fs_read_exact_proved returns
     bool periods;            // fs_render_exact with fs_set_exact_periods: the P = true kernels run and the period planes come back
     ExactMode mode;          // frames only
+    // point runs (fs_exact_eval_points; samples on the lane path, no cycle check): run e stops at lengths[e] instead of cap, the
+    // S = true, P = true kernels run, and the runs' atom periods and endpoints (x planes, y planes: [limbs][n] each) go to the
+    // caller's host arrays -- not to the renderer's planes, which stay the last frame's
+    const uint64_t *lengths;
+    uint64_t *atoms_out;
+    uint32_t *end_x_out, *end_y_out;
 };
 
 static ExactRun exact_frame_run(const fs_renderer *r, const ExactPath &path, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx,
@@ -186,7 +199,7 @@ static void exact_add_stats(fs_renderer::Exact &X, const unsigned long long st[4
 }
 static bool exact_lane_launch(const ExactRun &R, const FsExactArgs &A, bool cycle, bool keep, hipStream_t s)
 {
-    return fsk_exact_slice(A, R.limbs, R.W == 0, cycle, keep, R.periods, s);
+    return fsk_exact_slice(A, R.limbs, R.W == 0, cycle, keep, R.periods || R.lengths, s);
 }
 static const ExactPath kExactLane = {exact_lane_launch, exact_default_slice, exact_add_stats, true, false};
 
@@ -246,8 +259,9 @@ static ExactResult exact_run(fs_renderer *r, const ExactRun &R)
     const bool keep = R.mode != kExactPlain, resume = R.mode == kExactResume, cycle = R.cycle;
     const fs_renderer::ExactKept K0 = X.kept;
     const uint32_t n = R.n, npix = R.W ? R.nx * R.ny : n;
-    const bool periods = R.periods && !keep && R.W != 0;
-    const ExactLayout Y = resume ? K0.layout() : ExactLayout(R.limbs, R.nx, R.ny, n, cycle, npix, periods ? npix : 0);
+    const bool points = R.lengths != nullptr;
+    const bool periods = points || (R.periods && !keep && R.W != 0);
+    const ExactLayout Y = resume ? K0.layout() : ExactLayout(R.limbs, R.nx, R.ny, n, cycle, npix, periods ? npix : 0, points);
     const bool compact = !(P.fixed_slots && X.no_compaction);
     const int n_lists = compact || keep ? 2 : 1;
     char *blk = nullptr;
@@ -284,6 +298,8 @@ static ExactResult exact_run(fs_renderer *r, const ExactRun &R)
         planes.mn = Y.atom_min(blk, n_lists), planes.keys = Y.period_plane(blk, n_lists, 0);
         planes.atom = Y.period_plane(blk, n_lists, 1), planes.cyclen = cycle ? Y.period_plane(blk, n_lists, 2) : nullptr;
         planes.stride = npix;
+        if (points)
+            planes.end = Y.ends(blk, n_lists), A.lengths = Y.lengths(blk, n_lists);
         A.periods = Y.period_planes(blk);
         A.atom_key_shift = fsx::atom_key_shift(X.atom_key_bits);
     }
@@ -295,6 +311,10 @@ static ExactResult exact_run(fs_renderer *r, const ExactRun &R)
         e = hipMemsetAsync(planes.atom, 0, (cycle ? 2 : 1) * Y.plane_bytes, s);
     if (e == hipSuccess && periods)
         e = hipMemcpyAsync(Y.period_planes(blk), &planes, sizeof planes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && points)
+        e = hipMemsetAsync(planes.end, 0, (size_t)2 * R.limbs * n * 4, s);
+    if (e == hipSuccess && points)
+        e = hipMemcpyAsync(Y.lengths(blk, n_lists), R.lengths, (size_t)n * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && resume && K0.proved != 0) { // (a sample the continuation proves writes the new cap itself)
         fsk_exact_set_proved(R.out, (int)R.out_u64, A.proved, R.nx, R.ny, R.out_pitch, R.cap, s);
         e = hipGetLastError();
@@ -340,7 +360,13 @@ static ExactResult exact_run(fs_renderer *r, const ExactRun &R)
         X.proved.resize(npix);
         e = hipMemcpyAsync(X.proved.data(), A.proved, npix, hipMemcpyDeviceToHost, s);
     }
-    if (e == hipSuccess && periods) {
+    if (e == hipSuccess && points) {
+        e = hipMemcpyAsync(R.atoms_out, planes.atom, (size_t)n * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(R.end_x_out, planes.end, (size_t)R.limbs * n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(R.end_y_out, planes.end + (size_t)R.limbs * n, (size_t)R.limbs * n * 4, hipMemcpyDeviceToHost, s);
+    } else if (e == hipSuccess && periods) {
         X.atom.resize(npix);
         e = hipMemcpyAsync(X.atom.data(), planes.atom, (size_t)npix * 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess && cycle) {
@@ -350,7 +376,7 @@ static ExactResult exact_run(fs_renderer *r, const ExactRun &R)
     }
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);
-    if (periods)
+    if (periods && !points)
         X.atom_valid = e == hipSuccess, X.cyclen_valid = cycle && e == hipSuccess;
     P.add_stats(X, st);
     X.stats[2] += slices, X.stats[3] += after_first;
@@ -646,6 +672,43 @@ uint32_t fs_exact_sample_counts(fs_renderer *r, uint32_t frac_bits, uint32_t lim
     uint32_t rc = exact_run(r, exact_sample_run(kExactWide, frac_bits, limbs, cx, cy, n_samples, bailout, inclusive, n_iterations, d_out)).rc;
     if (rc == 0)
         rc = (uint32_t)hipMemcpyAsync(counts_out, d_out, (size_t)n_samples * 8, hipMemcpyDeviceToHost, r->compute);
+    if (rc == 0)
+        rc = (uint32_t)hipStreamSynchronize(r->compute);
+    (void)r_free(r, d_out);
+    return rc;
+}
+
+uint32_t fs_exact_eval_points(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                              const uint64_t *lengths, uint32_t n_runs, uint32_t bailout, int inclusive, uint64_t *values_out,
+                              uint64_t *atoms_out, uint32_t *end_x_out, uint32_t *end_y_out)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (uint32_t e = exact_format_check(frac_bits, limbs, fsx::kMaxLimbs, bailout))
+        return e;
+    if (n_runs == 0)
+        return 0;
+    if (!cx || !cy || !lengths || !values_out || !atoms_out || !end_x_out || !end_y_out || n_runs > kWideMaxSamples)
+        return (uint32_t)hipErrorInvalidValue;
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < n_runs; i++) {
+        if (lengths[i] == 0 || lengths[i] == ~0ull)
+            return (uint32_t)hipErrorInvalidValue;
+        longest = lengths[i] > longest ? lengths[i] : longest;
+    }
+    if (!exact_axes_in_range(cx, n_runs, cy, n_runs, limbs, frac_bits))
+        return FS_ERR_UNSUPPORTED;
+    if (uint32_t e = ensure_streams(r)) // no fs_init_memory needed
+        return e;
+    uint64_t *d_out = nullptr;
+    FS_TRY(r_alloc(r, (void **)&d_out, (size_t)n_runs * 8, kFrame));
+    r->exact.reset_stats();
+    // (the cycle-check, keep and periods switches are not read: no check, nothing kept, and the renderer's planes stay the frame's)
+    ExactRun R = exact_sample_run(kExactLane, frac_bits, limbs, cx, cy, n_runs, bailout, inclusive, longest, d_out);
+    R.lengths = lengths, R.atoms_out = atoms_out, R.end_x_out = end_x_out, R.end_y_out = end_y_out;
+    uint32_t rc = exact_run(r, R).rc;
+    if (rc == 0)
+        rc = (uint32_t)hipMemcpyAsync(values_out, d_out, (size_t)n_runs * 8, hipMemcpyDeviceToHost, r->compute);
     if (rc == 0)
         rc = (uint32_t)hipStreamSynchronize(r->compute);
     (void)r_free(r, d_out);

@@ -206,6 +206,139 @@ def sample_counts(renderer, view, xs, ys, bailout=4, frac_bits=None, levels=(), 
     return values, stable
 
 
+def _to_limbs(values, limbs):
+    """uint32[limbs, n]: Python integers as two's-complement numbers of `limbs` limbs, limb-major."""
+    mask = (1 << (32 * limbs)) - 1
+    raw = b"".join((int(v) & mask).to_bytes(4 * limbs, "little") for v in values)
+    return np.ascontiguousarray(np.frombuffer(raw, "<u4").reshape(len(values), limbs).T)
+
+
+def _from_limbs(arr):
+    """Python integers of a limb-major uint32[limbs, n], two's complement."""
+    limbs = arr.shape[0]
+    raw = np.ascontiguousarray(arr.T.astype("<u4")).tobytes()
+    return [int.from_bytes(raw[4 * limbs * i:4 * limbs * (i + 1)], "little", signed=True) for i in range(arr.shape[1])]
+
+
+def points(values, frac_bits, limbs=None):
+    """(ints, array): floor(value * 2^frac_bits) of every value -- decimal strings or Fractions, read as exact rationals -- as Python
+    integers and as the limb-major uint32[limbs, n] the exact entry points take (limbs defaults to limbs_for(frac_bits))."""
+    from fractions import Fraction
+    F = int(frac_bits)
+    limbs = limbs_for(F) if limbs is None else int(limbs)
+    ints = []
+    for v in values:
+        q = Fraction(v)
+        ints.append((q.numerator << F) // q.denominator)
+    for v in ints:
+        if not -(1 << (32 * limbs - 1)) <= v < 1 << (32 * limbs - 1):
+            raise ValueError("points: a value does not fit %d limbs at %d fractional bits" % (limbs, F))
+    return ints, _to_limbs(ints, limbs)
+
+
+def eval_points(renderer, cxs, cys, lengths, frac_bits, bailout=256, inclusive=False):
+    """Point runs on the GPU (fs_exact_eval_points; DESIGN.md 6.3 "Point runs"): run e iterates c = (cxs[e] + i cys[e]) / 2^frac_bits
+    -- Python integers -- from z_1 = c up to n = lengths[e].  Returns (values, atoms, ends), lists of Python integers:
+    values[e] = v = min(E - 1, lengths[e]); atoms[e] = the n in 1 .. v with the smallest x_n^2 + y_n^2, the earliest on ties, 0 when
+    v = 0; ends[e] = (x_p, y_p) * 2^frac_bits at p = lengths[e] when v == p, else None.  Equal to the recurrence on Python integers.
+    Up to 758 fractional bits (24 limbs); ValueError beyond: the wide path has no point runs."""
+    F = int(frac_bits)
+    L = limbs_for(F)
+    if uses_wide(L):
+        raise ValueError("eval_points: %d fractional bits need more than %d limbs; the wide path has no point runs" % (F, MAX_LIMBS))
+    cxs, cys, lengths = list(cxs), list(cys), [int(p) for p in lengths]
+    if not (len(cxs) == len(cys) == len(lengths)):
+        raise ValueError("eval_points: cxs, cys and lengths must have one length")
+    if not cxs:
+        return [], [], []
+    err, values, atoms, end_x, end_y = renderer.ExactEvalPoints(F, L, _to_limbs(cxs, L), _to_limbs(cys, L),
+                                                                np.array(lengths, np.uint64), bailout, inclusive)
+    _check(renderer, err, "fs_exact_eval_points")
+    values, atoms = [int(v) for v in values], [int(a) for a in atoms]
+    xs, ys = _from_limbs(end_x), _from_limbs(end_y)
+    return values, atoms, [(x, y) if v == p else None for x, y, v, p in zip(xs, ys, values, lengths)]
+
+
+def refine_points(evaluate, c0s, deltas, periods, frac_bits, rounds=16):
+    """Found points to nuclei by a derivative-free secant iteration on z_p(c), on Python integers (DESIGN.md 6.3 "Point runs").
+    evaluate(cxs, cys, lengths) -> (values, atoms, ends) is eval_points' contract with the renderer bound (or any model of it);
+    c0s = [(cx, cy)] as integers c * 2^frac_bits, deltas = the real offset of every point's second starting point, periods = p.
+    Every round puts all points still running into ONE evaluate call; the first call holds both starting points of every point.
+    Per point (`//` and `>>` floor):
+        c1 = c0 + (delta, 0); either start short of p: "escaped", no result
+        at most `rounds` times: d = f1 - f0 (the endpoints); d == 0: "stalled"
+            q = floor(f1 conj(d) 2^F / |d|^2), s = (q (c1 - c0)) >> F, c2 = c1 - s; c2 == c1: "fixed"
+            evaluate c2; short of p: "escaped"; else (c0, f0, c1, f1) = (c1, f1, c2, f2)
+        otherwise "rounds"
+    Returns one dict per point: status; c = (cx, cy) of the evaluated iterate with the smallest |z_p|, the earliest on ties (None
+    when no iterate reached p); atom = the atom period there; converged = atom == p; evaluations; log2 = log2 |z_p| of every iterate
+    that reached p, in order (floats, for reading only)."""
+    import math
+    F = int(frac_bits)
+    n = len(c0s)
+    periods = [int(p) for p in periods]
+    c0 = [(int(c[0]), int(c[1])) for c in c0s]
+    c1 = [(c[0] + int(d), c[1]) for c, d in zip(c0, deltas)]
+    status, n_eval = [None] * n, [2] * n
+    evals = [[] for _ in range(n)]  # (c, atom, endpoint) of every iterate that reached p
+
+    def run(items):
+        """items = [(point, c)]: one evaluate call; the endpoint (or None) per item."""
+        values, atoms, ends = evaluate([c[0] for _, c in items], [c[1] for _, c in items], [periods[k] for k, _ in items])
+        out = []
+        for (k, c), v, a, end in zip(items, values, atoms, ends):
+            reached = int(v) == periods[k] and end is not None
+            if reached:
+                evals[k].append((c, int(a), (int(end[0]), int(end[1]))))
+            out.append(evals[k][-1][2] if reached else None)
+        return out
+
+    f0, f1 = [None] * n, [None] * n
+    if n:
+        first = run([(k, c0[k]) for k in range(n)] + [(k, c1[k]) for k in range(n)])
+        f0, f1 = first[:n], first[n:]
+    short_start = {k for k in range(n) if f0[k] is None or f1[k] is None}
+    for k in short_start:
+        status[k] = "escaped"
+    for _ in range(int(rounds)):
+        items = []
+        for k in range(n):
+            if status[k] is not None:
+                continue
+            dx, dy = f1[k][0] - f0[k][0], f1[k][1] - f0[k][1]
+            if dx == 0 and dy == 0:
+                status[k] = "stalled"
+                continue
+            dd = dx * dx + dy * dy
+            qx = ((f1[k][0] * dx + f1[k][1] * dy) << F) // dd
+            qy = ((f1[k][1] * dx - f1[k][0] * dy) << F) // dd
+            ex, ey = c1[k][0] - c0[k][0], c1[k][1] - c0[k][1]
+            c2 = (c1[k][0] - ((qx * ex - qy * ey) >> F), c1[k][1] - ((qx * ey + qy * ex) >> F))
+            if c2 == c1[k]:
+                status[k] = "fixed"
+                continue
+            items.append((k, c2))
+        if not items:
+            break
+        for (k, c2), f2 in zip(items, run(items)):
+            n_eval[k] += 1
+            if f2 is None:
+                status[k] = "escaped"
+            else:
+                c0[k], f0[k], c1[k], f1[k] = c1[k], f1[k], c2, f2
+    out = []
+    for k in range(n):
+        norm = lambda e: e[2][0] * e[2][0] + e[2][1] * e[2][1]
+        res = {"status": status[k] or "rounds", "c": None, "atom": None, "converged": False, "evaluations": n_eval[k],
+               "log2": [0.5 * math.log2(norm(e)) - F if norm(e) else -math.inf for e in evals[k]]}
+        if k not in short_start:
+            best = min(range(len(evals[k])), key=lambda j: (norm(evals[k][j]), j))
+            res["c"], res["atom"] = evals[k][best][0], evals[k][best][1]
+            res["converged"] = res["atom"] == periods[k]
+        out.append(res)
+    return out
+
+
 def lattice(view, cols, rows):
     """(xs, ys) = uint32[n] each: `cols` x `rows` samples spread evenly over the view's antialiased frame, the first and the last
     row and column included, row-major (rounded positions that coincide are taken once)."""
@@ -306,4 +439,4 @@ def stable_mask(renderer, view, level, bailout=4, frac_bits=None, prove_interior
 __all__ = ["GUARD_BITS", "MAX_FRAC_BITS", "MAX_WIDE_LIMBS", "MAX_WIDE_FRAC_BITS", "limbs_for", "axes", "render", "render_periods",
            "continue_render",
            "render_progressive", "uses_wide",
-           "sample_counts", "stable_mask", "lattice", "audit", "AuditReport"]
+           "sample_counts", "points", "eval_points", "refine_points", "stable_mask", "lattice", "audit", "AuditReport"]

@@ -245,3 +245,34 @@ def period_map(renderer, view, nx, ny, T=T_HDR64, iter_bytes=4, max_iters=None):
     rout = np.zeros(len(rin), (records_plain if plain else records)(is64)[1])
     evaluate(FIND, rad, view.num_iterations if max_iters is None else int(max_iters), rin, rout)
     return np.where(rout["status"] == OK_DIRECT, rout["period"], 0).astype(np.uint64).reshape(int(ny), int(nx))
+
+
+def _decimal(v, frac_bits):
+    """v / 2^frac_bits as an exact finite decimal string (v a Python integer)."""
+    digits = str(abs(v) * 5 ** frac_bits).rjust(frac_bits + 1, "0")
+    whole, frac = digits[:-frac_bits] if frac_bits else digits, (digits[-frac_bits:] if frac_bits else "").rstrip("0")
+    return ("-" if v < 0 else "") + whole + ("." + frac if frac else "")
+
+
+def refine_found(renderer, found, frac_bits=None, rounds=16):
+    """The points find_periodic_points returns, refined to nuclei of their period on the exact recurrence (DESIGN.md 6.3 "Point
+    runs"): exact.refine_points with the GPU evaluator exact.eval_points (bailout 256, strict), every point started at its printed
+    (cx, cy) with the offset delta = max(1, floor(intrinsic_radius * 2^F) >> 30), F = frac_bits (default exact.MAX_FRAC_BITS = 758;
+    ValueError beyond).  Needs no orbit and no InitializeMemory.  Returns one dict per point, in order: status ("fixed", "rounds",
+    "stalled", "escaped"), c = (cx, cy) as integers c * 2^F and cx, cy as exact decimal strings (None where no iterate reached the
+    period), atom (the atom period at c), converged (atom == period), period, evaluations, and log2 (log2 |z_p| of every iterate that
+    reached the period, floats)."""
+    from . import exact
+    F = exact.MAX_FRAC_BITS if frac_bits is None else int(frac_bits)
+    if exact.uses_wide(exact.limbs_for(F)):
+        raise ValueError("refine_found: %d fractional bits need more than %d limbs" % (F, exact.MAX_LIMBS))
+    cxs, _ = exact.points([p["cx"] for p in found], F)
+    cys, _ = exact.points([p["cy"] for p in found], F)
+    radii, _ = exact.points([p["intrinsic_radius"] for p in found], F)
+    periods = [int(p["period"]) for p in found]
+    res = exact.refine_points(lambda a, b, n: exact.eval_points(renderer, a, b, n, F), list(zip(cxs, cys)),
+                              [max(1, r >> 30) for r in radii], periods, F, rounds)
+    for q, p in zip(res, periods):
+        q["period"] = p
+        q["cx"], q["cy"] = (None, None) if q["c"] is None else (_decimal(q["c"][0], F), _decimal(q["c"][1], F))
+    return res

@@ -201,6 +201,22 @@ class GPURenderer:
                                                int(bailout), 1 if inclusive else 0, int(n_iterations), out.ctypes.data)
         return err, out
 
+    def ExactEvalPoints(self, frac_bits, limbs, cx, cy, lengths, bailout, inclusive):
+        """fs_exact_eval_points: (error code, values uint64[n], atoms uint64[n], end_x uint32[limbs, n], end_y uint32[limbs, n]) of
+        n point runs, cx, cy = uint32[limbs, n] (limb-major per run), lengths = uint64[n]: run e stops at lengths[e].  Needs no
+        InitializeMemory.  Synchronous."""
+        cx, cy = np.ascontiguousarray(cx, np.uint32), np.ascontiguousarray(cy, np.uint32)
+        lengths = np.ascontiguousarray(lengths, np.uint64)
+        if cx.ndim != 2 or cx.shape[0] != limbs or cy.shape != cx.shape or lengths.shape != (cx.shape[1],):
+            raise ValueError("cx, cy must both be uint32[limbs, n] and lengths uint64[n]")
+        n = cx.shape[1]
+        values, atoms = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        end_x, end_y = np.zeros_like(cx), np.zeros_like(cy)
+        err = self._lib.fs_exact_eval_points(self._h, int(frac_bits), int(limbs), cx.ctypes.data, cy.ctypes.data, lengths.ctypes.data,
+                                             n, int(bailout), 1 if inclusive else 0, values.ctypes.data, atoms.ctypes.data,
+                                             end_x.ctypes.data, end_y.ctypes.data)
+        return err, values, atoms, end_x, end_y
+
     def ExactAudit(self, frac_bits, limbs, xs, ys, cx_runs, cy_runs, bailout, inclusive, n_iterations, device_iters=None,
                    per_sample=True):
         """fs_exact_audit: the frame in the iteration buffer (device_iters: another device buffer of the frame's geometry, raw

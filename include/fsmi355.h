@@ -372,6 +372,23 @@ uint32_t fs_exact_sample_counts(fs_renderer *r, uint32_t frac_bits, uint32_t lim
                                 uint32_t n_samples, uint32_t bailout, int inclusive, uint64_t n_iterations, uint64_t *counts_out);
 uint32_t fs_render_exact_wide(fs_renderer *r, uint32_t iter_bytes, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx,
                               const uint32_t *cy, uint32_t bailout, int inclusive, uint64_t n_iterations);
+/* Point runs: the exact recurrence on a list of points with a length each, the state at the end of every run and the period rule
+ * (DESIGN.md 6.3 "Point runs"; what exact.refine_points refines the Feature Finder's found points with).  One lane per run,
+ * limbs = 2 .. 24.  Run e: c = (cx[l * n_runs + e], cy[l * n_runs + e]) (limb-major per RUN, as fs_exact_sample_counts) and
+ * p = lengths[e] >= 1.  With z_1 = c, N_n = x_n^2 + y_n^2 untruncated and E the first n at which z_n escapes:
+ *   values_out[e] = v = min(E - 1, p);
+ *   atoms_out[e]  = the n in 1 .. v with the smallest N_n, ties to the earliest n; 0 when v = 0;
+ *   end_x_out[l * n_runs + e], end_y_out[l * n_runs + e] = limb l of x_p, y_p when v == p, else 0 on every limb.
+ * All four are host memory; every value equals the recurrence on integers, whatever the slices and the compaction (runs of
+ * different lengths leave the list at different slices).  Synchronous.  Needs no frame and no fs_init_memory; the iteration buffer,
+ * the orbit and LA caches, the kept set and the period planes of the last fs_render_exact are left alone.  The cycle-check, keep and
+ * periods switches are not read.  fs_set_exact_slice applies (default: as for the lists of fs_exact_audit); fs_read_exact_stats
+ * reports the call.  n_runs == 0: 0.
+ * FS_ERR_UNSUPPORTED: limbs outside 2 .. 24 or 32 * limbs < frac_bits + 10; bailout outside 1 .. 256; a c outside [-32, 32).
+ * hipErrorInvalidValue: a NULL pointer; a length of 0 or 2^64 - 1; more than 2^31 - 1 runs. */
+uint32_t fs_exact_eval_points(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                              const uint64_t *lengths, uint32_t n_runs, uint32_t bailout, int inclusive, uint64_t *values_out,
+                              uint64_t *atoms_out, uint32_t *end_x_out, uint32_t *end_y_out);
 /* The exact audit: the project's definition of a correct frame -- equal to the exact count on every sample that is stable at a
  * stated level -- as one call on the frame in the iteration buffer (device_iters: another device buffer of the same
  * geometry and IterType, NULL = the current one).  n_samples sample pixels (xs[i], ys[i]) of the W x H of fs_init_memory and a
