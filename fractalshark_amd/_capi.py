@@ -207,6 +207,8 @@ def render_lib():
     _decl(lib, "fs_bla_lm2", i32, [vp])
     _decl(lib, "fs_bla_level_size", u64, [vp, i32])
     _decl(lib, "fs_read_bla_level", u32, [vp, i32, vp, u64])
+    _decl(lib, "fs_bla_lookup_probe", u32, [vp, C.c_int, vp, vp, u32, vp])
+    _decl(lib, "fs_read_bla_native", u32, [vp, C.c_int, vp, u64, vp])
     _decl(lib, "fs_render_direct_lp", u32, [vp, C.c_int, vp, u64, C.c_int])
     _decl(lib, "fs_clear", u32, [vp])
     _decl(lib, "fs_render_current", u32, [vp, u64, vp, vp, vp, C.c_int])
@@ -287,6 +289,7 @@ RENDER_SYMBOLS = [
     "fs_set_exact_periods", "fs_read_exact_atom_periods", "fs_read_exact_cycle_lengths", "fs_set_exact_atom_key_bits",
     "fs_render_bla", "fs_render_direct", "fs_upload_orbit_scaled",
     "fs_render_scaled", "fs_build_bla", "fs_bla_num_levels", "fs_bla_lm2", "fs_bla_level_size", "fs_read_bla_level",
+    "fs_bla_lookup_probe", "fs_read_bla_native",
     "fs_render_direct_lp", "fs_clear",
     "fs_render_current", "fs_sync_compute", "fs_compute_stream", "fs_sync_display", "fs_query_compute", "fs_enqueue_done_callback",
     "fs_host_fallback_bytes", "fs_idle_device_bytes", "fs_release_idle_device_memory", "fs_set_compressed_orbit_mode", "fs_orbit_device_bytes", "fs_get_width", "fs_get_height", "fs_last_kernel_ms", "fs_set_kernel_variant", "fs_kernel_ms_history", "fs_kernel_ms_split_history", "fs_forget_tile_costs", "fs_last_frame_tile_ordered", "fs_last_frame_sampled_tile_order", "fs_read_tile_costs", "fs_read_tile_order", "fs_seq_cursor_probe", "fs_enable_step_count", "fs_read_step_count",
@@ -390,6 +393,7 @@ def inputs_lib():
     _decl(lib, "fsh_la_at", None, [vp, vp])
     _decl(lib, "fsh_bla_create_hdr32", vp, [vp])
     _decl(lib, "fsh_bla_create", vp, [vp])
+    _decl(lib, "fsh_bla_create_ex", vp, [vp, vp])
     _decl(lib, "fsh_bla_destroy", None, [vp])
     _decl(lib, "fsh_bla_num_levels", i32, [vp])
     _decl(lib, "fsh_bla_lm2", i32, [vp])

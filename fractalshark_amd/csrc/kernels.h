@@ -459,6 +459,11 @@ void fsk_bla_make_heap(const FsBlaRec *rec, const int4 *lad, const long long *km
                        const uint64_t *epl, int n_levels, int32_t lm2, const float4 *zref, uint32_t orbit_count, FsBlaRec *hrec,
                        int4 *hlad, int4 *hq, float4 *zb, hipStream_t s);
 void fsk_bla_hdr32_fast(const FsBlaArgs32 &A, bool pool, hipStream_t s);
+// test probe (fs_bla_lookup_probe): which = 0 bla_lookup<float>, 1 bla_lookup<double> (both on `levels`), 2 bla_lookup_native (on
+// nlad / nkmax / level_off); m, z2, out are device arrays of n_padded questions, n_padded a multiple of 256 (full waves)
+void fsk_bla_lookup_probe(int which, const void *const *levels, const int4 *nlad, const long long *nkmax, const uint32_t *level_off,
+                          const uint64_t *epl, int n_levels, int32_t lm2, const uint32_t *m, const void *z2, uint32_t n_padded,
+                          uint32_t *out, hipStream_t s);
 // pixel order from a frame's counts (kernels_order.hip): n = elements of the iteration buffer; work = 2 n words; order = n words
 // An order for a view's FIRST frame (kernels_tile_sample.hip): PerformAT's loop for one pixel per 8 x 8 tile, in binary64.
 struct FsTileSampleArgs {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstring>
 #include <type_traits>
 
 #include "../../include/fs_layout.h"
@@ -1519,4 +1520,93 @@ void fsk_perturb_scalar_hdr32(const FsBlaArgs32 &A, bool use_bla, bool stats, in
 void fsk_perturb_scalar_hdr64(const FsBlaArgsT<double> &A, bool use_bla, bool stats, int variant, hipStream_t s)
 {
     launch_perturb_scalar<double>(A, use_bla, stats, variant, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Test probe (fs_bla_lookup_probe): the three texts of BLAS::LookupBackwards above, asked directly.  One lane per question
+// (orbit index m, |dz|^2); out[2 i], out[2 i + 1] = level and element index of the record the lookup returns, ~0u twice when
+// it returns none.  The launch is made of full waves (the caller pads the questions with m = 0): bla_lookup_native votes.
+namespace {
+
+struct BlaProbeGeom {
+    uint32_t level_off[kBlaMaxLevels];
+    uint32_t level_n[kBlaMaxLevels];
+    int32_t n_levels;
+    int32_t lm2;
+};
+
+template <class F>
+__global__ void __launch_bounds__(256) k_bla_lookup_probe(const typename FsDev<F>::BLA *const *__restrict__ levels, BlaProbeGeom G,
+                                                          const uint32_t *__restrict__ m,
+                                                          const decltype(FsDev<F>::BLA::r2) *__restrict__ z2,
+                                                          uint32_t *__restrict__ out)
+{
+    using B = typename FsDev<F>::BLA;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const B *t = bla_lookup<F>(levels, G.lm2, m[i], hreal<F>{z2[i].m, z2[i].e});
+    uint32_t lv = 0xFFFFFFFFu, ix = 0xFFFFFFFFu;
+    if (t != nullptr)
+        for (int32_t l = 2; l < G.n_levels; l++) {
+            const B *base = levels[l];
+            if (G.level_n[l] != 0u && t >= base && t < base + G.level_n[l])
+                lv = (uint32_t)l, ix = (uint32_t)(t - base);
+        }
+    out[2 * (size_t)i] = lv;
+    out[2 * (size_t)i + 1] = ix;
+}
+
+__global__ void __launch_bounds__(256) k_bla_lookup_probe_native(const int4 *__restrict__ lad, const long long *__restrict__ kmax,
+                                                                 BlaProbeGeom G, const uint32_t *__restrict__ m,
+                                                                 const fs_real_hdr32 *__restrict__ z2, uint32_t *__restrict__ out)
+{
+    __shared__ uint32_t s_off[64];
+    if (threadIdx.x < 64u)
+        s_off[threadIdx.x] = threadIdx.x < (uint32_t)kBlaMaxLevels ? G.level_off[threadIdx.x] : 0u;
+    __syncthreads();
+    const int4 e20 = lad[2u * (size_t)G.level_off[2]];
+    const long long key20 = (long long)(((unsigned long long)(unsigned)e20.y << 32) | (unsigned)e20.x);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const long long zkey = (long long)(((unsigned long long)(unsigned)z2[i].e << 32) | (unsigned)__float_as_int(z2[i].m));
+    const uint32_t pos = bla_lookup_native(lad, kmax, s_off, G.lm2, m[i], zkey, key20);
+    uint32_t lv = 0xFFFFFFFFu, ix = 0xFFFFFFFFu;
+    if (pos != 0xFFFFFFFFu) {
+        int32_t L = 2;
+        for (int32_t l = 3; l < G.n_levels; l++)
+            if (G.level_n[l] != 0u && pos >= G.level_off[l])
+                L = l;
+        lv = (uint32_t)L, ix = pos - G.level_off[L];
+    }
+    out[2 * (size_t)i] = lv;
+    out[2 * (size_t)i + 1] = ix;
+}
+
+BlaProbeGeom probe_geom(const uint32_t *level_off, const uint64_t *epl, int n_levels, int32_t lm2)
+{
+    BlaProbeGeom G;
+    memset(&G, 0, sizeof(G));
+    G.n_levels = n_levels < kBlaMaxLevels ? n_levels : kBlaMaxLevels;
+    G.lm2 = lm2;
+    for (int l = 2; l < G.n_levels; l++) {
+        G.level_off[l] = level_off ? level_off[l] : 0u;
+        G.level_n[l] = (uint32_t)epl[l];
+    }
+    return G;
+}
+
+} // namespace
+
+void fsk_bla_lookup_probe(int which, const void *const *levels, const int4 *nlad, const long long *nkmax, const uint32_t *level_off,
+                          const uint64_t *epl, int n_levels, int32_t lm2, const uint32_t *m, const void *z2, uint32_t n_padded,
+                          uint32_t *out, hipStream_t s)
+{
+    const BlaProbeGeom G = probe_geom(level_off, epl, n_levels, lm2);
+    const dim3 g(n_padded / 256u), b(256);
+    if (which == 0)
+        hipLaunchKernelGGL(k_bla_lookup_probe<float>, g, b, 0, s, (const fs_bla_hdr32 *const *)levels, G, m, (const fs_real_hdr32 *)z2,
+                           out);
+    else if (which == 1)
+        hipLaunchKernelGGL(k_bla_lookup_probe<double>, g, b, 0, s, (const fs_bla_hdr64 *const *)levels, G, m,
+                           (const fs_real_hdr64 *)z2, out);
+    else
+        hipLaunchKernelGGL(k_bla_lookup_probe_native, g, b, 0, s, nlad, nkmax, G, m, (const fs_real_hdr32 *)z2, out);
 }

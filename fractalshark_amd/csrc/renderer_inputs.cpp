@@ -770,6 +770,121 @@ uint32_t fs_read_bla_level(fs_renderer *r, int32_t level, void *out, uint64_t ma
     return (uint32_t)hipStreamSynchronize(r->compute);
 }
 
+// The device-native forms of the installed HDRFloat<float> table, made first when they are stale (as fs_render_bla does).
+static uint32_t bla_native_current(fs_renderer *r)
+{
+    if (r->bla_native_stale && r->bla_n_levels > 2 && r->bla_levels_dev != nullptr && r->bla_type == FS_T_HDR32)
+        return bla_make_native(r, r->bla_n_levels);
+    return 0;
+}
+
+uint32_t fs_read_bla_native(fs_renderer *r, int part, void *out, uint64_t max_bytes, uint64_t *bytes)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (!r->compute || r->bla_type != FS_T_HDR32)
+        return FS_ERR_6;
+    if (uint32_t e = bla_native_current(r))
+        return e;
+    const bool native = r->bla_native_ok && !r->bla_native_stale && r->bla_n_levels > 2, heap = native && r->bla_heap_ok;
+    const uint64_t total = native ? r->bla_native_total : 0, hn = heap ? r->bla_heap_positions : 0;
+    const uint64_t n_q = (uint64_t)(r->orbit_uncompressed / 4u) + 2u; // (bla_make_native's n_kmax)
+    uint32_t geom[16 + 2 * kBlaMaxLevels];
+    memset(geom, 0, sizeof(geom));
+    const void *src = nullptr;
+    uint64_t n = 0;
+    const char *nat = r->bla_native.as<const char>() + 256, *hp = r->bla_heap.as<const char>();
+    switch (part) {
+        case FS_BLA_PART_GEOMETRY: {
+            geom[0] = native, geom[1] = heap, geom[2] = (uint32_t)r->bla_n_levels, geom[3] = (uint32_t)r->bla_lm2;
+            geom[4] = (uint32_t)total, geom[6] = (uint32_t)hn, geom[7] = native ? (uint32_t)n_q : 0u;
+            geom[8] = (uint32_t)r->orbit_uncompressed;
+            for (uint64_t h = hn; h != 0; h >>= 1) // positions = 2^(H - 1)
+                geom[5]++;
+            for (int32_t l = 2; native && l < r->bla_n_levels && l < kBlaMaxLevels; l++) {
+                geom[16 + l] = r->bla_level_off[l];
+                geom[16 + kBlaMaxLevels + l] = (uint32_t)r->bla_level_sizes[(size_t)l];
+            }
+            if (bytes)
+                *bytes = sizeof(geom);
+            if (out)
+                memcpy(out, geom, max_bytes < sizeof(geom) ? (size_t)max_bytes : sizeof(geom));
+            return 0;
+        }
+        case FS_BLA_PART_RECORDS: src = nat, n = total * sizeof(FsBlaRec); break;
+        case FS_BLA_PART_LADDER: src = nat + total * sizeof(FsBlaRec), n = total * 2 * sizeof(int4); break;
+        case FS_BLA_PART_PRETEST:
+            src = nat + total * (sizeof(FsBlaRec) + 2 * sizeof(int4)), n = native ? n_q * sizeof(long long) : 0;
+            break;
+        case FS_BLA_PART_HEAP_RECORDS: src = hp, n = hn * sizeof(FsBlaRec); break;
+        case FS_BLA_PART_HEAP_LADDER: src = hp + hn * sizeof(FsBlaRec), n = hn * 2 * sizeof(int4); break;
+        case FS_BLA_PART_Q: src = hp + hn * (sizeof(FsBlaRec) + 2 * sizeof(int4)), n = heap ? n_q * 3 * sizeof(int4) : 0; break;
+        case FS_BLA_PART_ZB:
+            src = hp + hn * (sizeof(FsBlaRec) + 2 * sizeof(int4)) + n_q * 3 * sizeof(int4);
+            n = heap ? (r->orbit_uncompressed + 2u) * sizeof(float4) : 0;
+            break;
+        default: return FS_ERR_7;
+    }
+    if (part >= FS_BLA_PART_HEAP_RECORDS ? !heap : !native)
+        return FS_ERR_6;
+    if (bytes)
+        *bytes = n;
+    const uint64_t c = n < max_bytes ? n : max_bytes;
+    if (out && c)
+        FS_TRY(hipMemcpyAsync(out, src, (size_t)c, hipMemcpyDeviceToHost, r->compute));
+    return (uint32_t)hipStreamSynchronize(r->compute);
+}
+
+uint32_t fs_bla_lookup_probe(fs_renderer *r, int which, const uint32_t *m, const void *z2, uint32_t n, uint32_t *level_ix_out)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (which < 0 || which > 2 || !m || !z2 || !level_ix_out || n > 0x7FFFFF00u)
+        return hipErrorInvalidValue;
+    if (!r->compute || r->bla_n_levels <= 2 || r->bla_levels_dev == nullptr || r->bla_type != (which == 1 ? FS_T_HDR64 : FS_T_HDR32) ||
+        r->bla_level_sizes.size() < 3 || r->bla_level_sizes[2] == 0)
+        return FS_ERR_6;
+    // every index a walk forms stays inside its level when (m - 1) >> 2 names an element of level 2
+    for (uint32_t i = 0; i < n; i++)
+        if (m[i] != 0u && (uint64_t)(m[i] - 1u) >= 4u * r->bla_level_sizes[2])
+            return FS_ERR_7;
+    if (which == 2) {
+        if (uint32_t e = bla_native_current(r))
+            return e;
+        if (!r->bla_native_ok || r->bla_native_stale)
+            return FS_ERR_6;
+    }
+    if (n == 0)
+        return 0;
+    const size_t zb = which == 1 ? sizeof(fs_real_hdr64) : sizeof(fs_real_hdr32);
+    const uint32_t np = (n + 255u) & ~255u; // full waves: the native lookup votes across the wave
+    char *dev = nullptr;
+    const size_t m_bytes = (size_t)np * sizeof(uint32_t), z_bytes = (size_t)np * zb, o_bytes = (size_t)np * 2 * sizeof(uint32_t);
+    FS_TRY(r_alloc(r, &dev, m_bytes + z_bytes + o_bytes, kFrame));
+    uint32_t *dm = (uint32_t *)(dev + z_bytes + o_bytes), *dout = (uint32_t *)(dev + z_bytes); // (z2 first: 8-byte aligned)
+    hipError_t err = hipMemsetAsync(dev, 0, m_bytes + z_bytes + o_bytes, r->compute); // the padding asks m = 0
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(dm, m, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, r->compute);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(dev, z2, (size_t)n * zb, hipMemcpyHostToDevice, r->compute);
+    if (err == hipSuccess) {
+        const char *nat = r->bla_native.as<const char>() + 256;
+        const int4 *nlad = (const int4 *)(nat + (size_t)r->bla_native_total * sizeof(FsBlaRec));
+        fsk_bla_lookup_probe(which, (const void *const *)r->bla_levels_dev, nlad,
+                             (const long long *)(nlad + 2 * (size_t)r->bla_native_total), which == 2 ? r->bla_level_off : nullptr,
+                             r->bla_level_sizes.data(), r->bla_n_levels, r->bla_lm2, dm, dev, np, dout, r->compute);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(level_ix_out, dout, (size_t)n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, r->compute);
+    if (err == hipSuccess)
+        err = hipStreamSynchronize(r->compute);
+    else
+        (void)hipStreamSynchronize(r->compute);
+    (void)r_free(r, dev);
+    return (uint32_t)err;
+}
+
 uint32_t fs_set_compressed_orbit_mode(fs_renderer *r, int mode)
 {
     if (mode != 0 && mode != 1)

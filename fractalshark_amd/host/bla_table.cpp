@@ -10,9 +10,8 @@ template <class F> struct BlaBuilder {
     std::vector<std::vector<BlaRec<F>>> B;
     int32_t LM2 = 0;
 
-    explicit BlaBuilder(const OrbitT<F> &ob)
+    BlaBuilder(const OrbitT<F> &ob, hreal<F> blaSize) // (BLAS::Init's blaSize: the reference passes GetMaxRadius())
     {
-        const hreal<F> blaSize = ob.maxRadius;
         const hreal<F> precision = hr_div(hr_from_number<F>(F(1)), hr_from_mant<F>(F(8388608))); // T(1)/T{1L<<23}
         // BLAS::CreateOneStep, BLAS.cpp:74-93, and BLAS::MergeTwoBlas, BLAS.cpp:25-47
         auto one_step = [&](size_t m) { return bla_one_step<F>(hc_from_hr(ob.x[m], ob.y[m]), precision); };
@@ -22,10 +21,12 @@ template <class F> struct BlaBuilder {
 };
 
 // the table in the ABI's records (Rec = fs_bla_hdr32 / fs_bla_hdr64; their padding members are zeroed by the aggregate form)
-template <class F, class Rec> void pack_bla(const OrbitT<F> &ob, std::vector<std::vector<Rec>> &levels, fsh_bla &r)
+template <class F, class Rec>
+void pack_bla(const OrbitT<F> &ob, const void *bla_size, std::vector<std::vector<Rec>> &levels, fsh_bla &r)
 {
     using Real = decltype(Rec::r2);
-    const BlaBuilder<F> b(ob);
+    const Real *given = (const Real *)bla_size;
+    const BlaBuilder<F> b(ob, given ? hreal<F>{given->m, given->e} : ob.maxRadius);
     r.lm2 = b.LM2;
     levels.resize(b.B.size());
     for (size_t l = 0; l < b.B.size(); l++) {
@@ -41,16 +42,18 @@ template <class F, class Rec> void pack_bla(const OrbitT<F> &ob, std::vector<std
 
 } // namespace
 
-extern "C" fsh_bla *fsh_bla_create(const fsh_orbit *o)
+// bla_size: NULL = the orbit's own maxRadius, else an fs_real_hdr32 / fs_real_hdr64 (the orbit's type) taken in its place
+extern "C" fsh_bla *fsh_bla_create_ex(const fsh_orbit *o, const void *bla_size)
 {
     auto r = std::make_unique<fsh_bla>();
     r->is64 = o->is64;
     if (!o->is64)
-        pack_bla(o->f, r->levels32, *r);
+        pack_bla(o->f, bla_size, r->levels32, *r);
     else
-        pack_bla(o->d, r->levels64, *r);
+        pack_bla(o->d, bla_size, r->levels64, *r);
     return r.release();
 }
+extern "C" fsh_bla *fsh_bla_create(const fsh_orbit *o) { return fsh_bla_create_ex(o, nullptr); }
 extern "C" fsh_bla *fsh_bla_create_hdr32(const fsh_orbit *o) { return o->is64 ? nullptr : fsh_bla_create(o); }
 extern "C" void fsh_bla_destroy(fsh_bla *b) { delete b; }
 extern "C" int32_t fsh_bla_num_levels(const fsh_bla *b) { return (int32_t)b->ptrs.size(); }

@@ -452,11 +452,12 @@ class LATable:
 class BLATable:
     """BLA table (BLAS<uint32_t, HDRFloat<float>>)."""
 
-    def __init__(self, orbit):
+    def __init__(self, orbit, bla_size=None):
+        """bla_size: None = orbit.max_radius() (what the reference passes to BLAS::Init), else a record of that form."""
         self._lib = _capi.inputs_lib()
         self.orbit = orbit
         self.is64 = orbit.is64
-        self._h = self._lib.fsh_bla_create(orbit._h)
+        self._h = self._lib.fsh_bla_create_ex(orbit._h, None if bla_size is None else bla_size.ctypes.data)
         if not self._h:
             raise RuntimeError("fsh_bla_create failed")
         self.num_levels = self._lib.fsh_bla_num_levels(self._h)

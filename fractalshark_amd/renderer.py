@@ -465,11 +465,12 @@ class GPURenderer:
             co = self._pack_coords(T, [dx, dy, centerX, centerY])
         return self._lib.fs_render_scaled(self._h, T, co.ctypes.data, int(n_iterations))
 
-    def BuildBLAOnDevice(self, orbit, T=None):
-        """BLAS::Init(count, maxRadius) on the device for the orbit last uploaded (fs_build_bla): the table stays in HBM."""
+    def BuildBLAOnDevice(self, orbit, T=None, bla_size=None):
+        """BLAS::Init(count, maxRadius) on the device for the orbit last uploaded (fs_build_bla): the table stays in HBM.
+        bla_size: a record of the form of orbit.max_radius() taken in its place."""
         if T is None:
             T = T_HDR64 if orbit.is64 else T_HDR32
-        mr = orbit.max_radius()
+        mr = orbit.max_radius() if bla_size is None else bla_size
         return self._lib.fs_build_bla(self._h, T, mr.ctypes.data)
 
     def BuildLAOnDevice(self, orbit, use_small_exponents=False, T=None, host_fallback=True, host_threads=1):
@@ -518,6 +519,44 @@ class GPURenderer:
             if err:
                 raise RuntimeError(self.ConvertErrorToString(err))
             out.append(a)
+        return out
+
+    BLA_NATIVE_PARTS = ("geometry", "records", "ladder", "pretest", "heap_records", "heap_ladder", "q", "zb")
+
+    def read_bla_native(self):
+        """The device-native forms of the HDRFloat<float> BLA table (fs_read_bla_native; made first when stale) -> dict: the
+        geometry words by name, and every part that is made as a uint8 array (tests / tools)."""
+        g = np.zeros(16 + 2 * 40, np.uint32)
+        err = self._lib.fs_read_bla_native(self._h, 0, g.ctypes.data, g.nbytes, None)
+        if err:
+            raise RuntimeError(self.ConvertErrorToString(err))
+        out = {"native_ok": bool(g[0]), "heap_ok": bool(g[1]), "n_levels": int(g[2]), "lm2": int(np.int32(g[3])),
+               "total": int(g[4]), "H": int(g[5]), "heap_positions": int(g[6]), "n_q": int(g[7]), "orbit_count": int(g[8]),
+               "level_off": [int(x) for x in g[16:56]], "level_n": [int(x) for x in g[56:96]]}
+        for part, name in enumerate(self.BLA_NATIVE_PARTS):
+            if part == 0 or not out["native_ok"] or (part >= 4 and not out["heap_ok"]):
+                continue
+            n = C.c_uint64(0)
+            err = self._lib.fs_read_bla_native(self._h, part, None, 0, C.byref(n))
+            if err:
+                raise RuntimeError(self.ConvertErrorToString(err))
+            a = np.zeros(n.value, np.uint8)
+            err = self._lib.fs_read_bla_native(self._h, part, a.ctypes.data if n.value else None, n.value, None)
+            if err:
+                raise RuntimeError(self.ConvertErrorToString(err))
+            out[name] = a
+        return out
+
+    def bla_lookup_probe(self, which, m, z2):
+        """fs_bla_lookup_probe: which = 0 / 1 the reference-layout lookup in HDRFloat<float> / <double>, 2 the native lookup;
+        m uint32[n], z2 a REAL_HDR32 / REAL_HDR64 array[n] -> uint32[n, 2] = (level, index), 0xFFFFFFFF twice for none."""
+        m = np.ascontiguousarray(m, np.uint32)
+        z2 = np.ascontiguousarray(z2)
+        assert z2.shape == m.shape and z2.dtype.itemsize == (16 if which == 1 else 8)
+        out = np.zeros((m.size, 2), np.uint32)
+        err = self._lib.fs_bla_lookup_probe(self._h, int(which), m.ctypes.data, z2.ctypes.data, m.size, out.ctypes.data)
+        if err:
+            raise RuntimeError(self.ConvertErrorToString(err))
         return out
 
     def Render(self, algorithm, cx, cy, dx, dy, n_iterations, iteration_precision=1, T=T_F64):

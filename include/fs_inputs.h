@@ -166,6 +166,9 @@ void fsh_la_at(const fsh_la *l, void *out); /* fs_at_hdr32_u32 or fs_at_hdr64_u3
  * materialised (m_FirstLevel = 2): their pointers are NULL and sizes 0. */
 fsh_bla *fsh_bla_create(const fsh_orbit *o);       /* type follows the orbit */
 fsh_bla *fsh_bla_create_hdr32(const fsh_orbit *o); /* NULL for an hdr64 orbit */
+/* bla_size: NULL = the orbit's own GetMaxRadius() (what fsh_bla_create passes to BLAS::Init), else an fs_real_hdr32 /
+ * fs_real_hdr64 of the orbit's type taken in its place */
+fsh_bla *fsh_bla_create_ex(const fsh_orbit *o, const void *bla_size);
 void fsh_bla_destroy(fsh_bla *b);
 int32_t fsh_bla_num_levels(const fsh_bla *b); /* m_B.size() */
 int32_t fsh_bla_lm2(const fsh_bla *b);        /* m_LM2 */

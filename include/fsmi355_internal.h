@@ -170,6 +170,22 @@ int32_t fs_bla_num_levels(const fs_renderer *r);
 int32_t fs_bla_lm2(const fs_renderer *r);
 uint64_t fs_bla_level_size(const fs_renderer *r, int32_t level);
 uint32_t fs_read_bla_level(fs_renderer *r, int32_t level, void *out, uint64_t max_records);
+/* Test hook: BLAS::LookupBackwards as the device has it, asked directly.  which = 0: the lookup on the reference-layout levels in
+ * HDRFloat<float> (HDRFloat<double> kernels, 64-bit counters, FS_VARIANT_LITERAL share its text), 1: the same in HDRFloat<double>,
+ * 2: the lookup on the ladder and pre-test keys of the device-native form (the compiled kernel of variant 2; made first when stale,
+ * which needs the HDRFloat<float> orbit).  Question i = (orbit index m[i], |dz|^2 = z2[i] as fs_real_hdr32, fs_real_hdr64 for
+ * which = 1); level_ix_out[2 i], [2 i + 1] = level and element index of the record found, 0xFFFFFFFF twice for none.  Host arrays.
+ * FS_ERR_6: no table of that type with more than two levels (no lookup can apply); FS_ERR_7: an m beyond the table. */
+uint32_t fs_bla_lookup_probe(fs_renderer *r, int which, const uint32_t *m, const void *z2, uint32_t n, uint32_t *level_ix_out);
+/* Read-back of the device-native forms of the HDRFloat<float> table (kernels.h: FsBlaRec, ladder, pre-test keys; kernels_bla_fast.hip:
+ * heap records, heap ladder, Q, zb), made first when they are stale, as fs_render_bla does.  *bytes = size of the part; at most
+ * max_bytes are copied (out may be NULL).  FS_BLA_PART_GEOMETRY: 16 + 2 x 40 uint32 -- [0] native form made, [1] heap form made,
+ * [2] levels, [3] lm2, [4] native positions, [5] heap height H, [6] heap positions, [7] pre-test keys / Q entries, [8] orbit entries,
+ * [16 + L] offset of level L, [56 + L] elements of level L.  FS_ERR_6: the part is not made (FS_BLA_PART_RECORDS .. PRETEST need
+ * [0], the later parts [1]). */
+enum { FS_BLA_PART_GEOMETRY = 0, FS_BLA_PART_RECORDS = 1, FS_BLA_PART_LADDER = 2, FS_BLA_PART_PRETEST = 3,
+       FS_BLA_PART_HEAP_RECORDS = 4, FS_BLA_PART_HEAP_LADDER = 5, FS_BLA_PART_Q = 6, FS_BLA_PART_ZB = 7 };
+uint32_t fs_read_bla_native(fs_renderer *r, int part, void *out, uint64_t max_bytes, uint64_t *bytes);
 uint32_t fs_la_counts(const fs_renderer *r, uint32_t *n_las, uint32_t *n_stages, int *use_at, int *is_valid);
 uint32_t fs_read_la(fs_renderer *r, void *las_out, uint32_t max_las, void *stages_out, uint32_t max_stages, void *at_out);
 

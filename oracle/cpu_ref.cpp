@@ -697,6 +697,23 @@ void lav2_impl(uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, const 
     }
 }
 
+// LookupBackwards above -- the text the BLA render functions call -- as a function of (table, m, z2): out[2 i], [2 i + 1] = level
+// and element index of the record returned for question i, 0xFFFFFFFF twice for none (tests/test_bla_model_cpu.py).
+template <class F>
+void bla_lookup_export(const typename Rec<F>::BLA *const *levels, const uint64_t *sizes, int32_t n_levels, int32_t lm2,
+                              const uint32_t *m, const typename Rec<F>::Real *z2, uint64_t n, uint32_t *out)
+{
+    const BlaTable<F> B{levels, sizes, n_levels, lm2};
+    for (uint64_t i = 0; i < n; i++) {
+        const typename Rec<F>::BLA *t = LookupBackwards<F>(B, m[i], ld(z2[i]));
+        out[2 * i] = out[2 * i + 1] = 0xFFFFFFFFu;
+        for (int32_t l = B.firstLevel; t != nullptr && l < n_levels; l++)
+            if (levels[l] != nullptr && t >= levels[l] && t < levels[l] + sizes[l]) {
+                out[2 * i] = (uint32_t)l;
+                out[2 * i + 1] = (uint32_t)(t - levels[l]);
+            }
+    }
+}
 } // namespace
 
 extern "C" {
@@ -880,6 +897,18 @@ void orc_bla_hdr64(uint32_t width, uint32_t height, uint32_t y0, uint32_t y1, co
 {
     bla_impl<double>(width, height, y0, y1, orbit, orbit_count, coords, n_iterations, bla_levels, bla_level_sizes,
                      bla_n_levels, bla_lm2, out, stride, threads);
+}
+
+// BLAS::LookupBackwards as the render functions above call it, asked directly (bla_lookup_export).
+void orc_bla_lookup_hdr32(const fs_bla_hdr32 *const *levels, const uint64_t *sizes, int32_t n_levels, int32_t lm2,
+                          const uint32_t *m, const fs_real_hdr32 *z2, uint64_t n, uint32_t *out)
+{
+    bla_lookup_export<float>(levels, sizes, n_levels, lm2, m, z2, n, out);
+}
+void orc_bla_lookup_hdr64(const fs_bla_hdr64 *const *levels, const uint64_t *sizes, int32_t n_levels, int32_t lm2,
+                          const uint32_t *m, const fs_real_hdr64 *z2, uint64_t n, uint32_t *out)
+{
+    bla_lookup_export<double>(levels, sizes, n_levels, lm2, m, z2, n, out);
 }
 
 // stage_test / mode / stats: see lav2_impl.

@@ -98,6 +98,9 @@ def lib():
         l.orc_gpu_scaled_f64.argtypes = [vp, u32, u32, u32, u32, vp, vp, u32, vp, u32, C.c_float, C.c_int, vp]
         l.orc_set_row_step.restype = None
         l.orc_set_row_step.argtypes = [u32]
+        for name in ("orc_bla_lookup_hdr32", "orc_bla_lookup_hdr64"):
+            getattr(l, name).restype = None
+            getattr(l, name).argtypes = [vp, vp, i32, i32, vp, vp, u64, vp]
         _lib = l
     return _lib
 
@@ -218,6 +221,20 @@ def bla_hdr32(view, orbit, bla=None, aa=1, rows=None, threads=8, n_iterations=No
     else:
         lib().orc_bla_hdr32(w, h, y0, y1, orbit.data_ptr, orbit.count, co.ctypes.data, n, bla.level_ptrs,
                             bla.level_sizes, bla.num_levels, bla.lm2, out.ctypes.data, out.shape[1], threads)
+    return out
+
+
+def bla_lookup(bla, m, z2):
+    """BLAS::LookupBackwards as the BLA render functions of the oracle call it, on the host table `bla` (inputs.BLATable, more
+    than two levels: the reference's text reads the first record of level 2 at m = 1): m uint32[n], z2 REAL_HDR32 / REAL_HDR64[n]
+    -> uint32[n, 2] = (level, index), 0xFFFFFFFF twice for none."""
+    assert bla.num_levels > 2
+    m = np.ascontiguousarray(m, np.uint32)
+    z2 = np.ascontiguousarray(z2)
+    assert z2.shape == m.shape and z2.dtype.itemsize == (16 if bla.is64 else 8)
+    out = np.zeros((m.size, 2), np.uint32)
+    fn = lib().orc_bla_lookup_hdr64 if bla.is64 else lib().orc_bla_lookup_hdr32
+    fn(bla.level_ptrs, bla.level_sizes, bla.num_levels, bla.lm2, m.ctypes.data, z2.ctypes.data, m.size, out.ctypes.data)
     return out
 
 
