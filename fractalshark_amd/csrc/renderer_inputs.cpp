@@ -756,6 +756,45 @@ uint32_t fs_read_ndz_bounds(fs_renderer *r, float *bounds_out, float *entries_ou
     return (uint32_t)hipStreamSynchronize(r->compute);
 }
 
+uint32_t fs_read_quiet_orbit(fs_renderer *r, int part, void *out, uint64_t max_bytes, uint64_t *bytes)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (!r->compute)
+        return FS_ERR_6;
+    const bool expanded = r->orbit_ok && !r->orbit_seq;
+    const bool hdr32 = expanded && r->orbit_type == FS_T_HDR32 && r->zref && r->zq && r->zq_n;
+    const uint64_t m = r->zq_n, slack = kQuietSlack;
+    const void *src = nullptr;
+    uint64_t n = 0;
+    bool made = hdr32;
+    switch (part) {
+        case FS_QUIET_PART_PREPARED: src = r->zref, n = m * sizeof(float4); break;
+        case FS_QUIET_PART_FIRST: src = r->zq, n = m * sizeof(float4); break;
+        case FS_QUIET_PART_SECOND: src = r->zq + m, n = m * sizeof(float4); break;
+        case FS_QUIET_PART_ZS2: src = r->zs2, n = (m + slack) * sizeof(float2); break;
+        case FS_QUIET_PART_ZQB: src = r->zqb, n = (m + slack) * sizeof(float4); break;
+        case FS_QUIET_PART_ZNZ: src = r->znz, n = (m + slack) * sizeof(float2); break;
+        case FS_QUIET_PART_PREPARED64:
+            made = expanded && r->orbit_type == FS_T_HDR64 && r->zref64;
+            src = r->zref64, n = (r->orbit_uncompressed + 2) * sizeof(FsZ64);
+            break;
+        case FS_QUIET_PART_SCALED_F32:
+            made = r->scaled_f && r->scaled_count;
+            src = r->scaled_f, n = r->scaled_count * sizeof(fs_orbit_f32_bad);
+            break;
+        default: return FS_ERR_7;
+    }
+    if (!made)
+        return FS_ERR_6;
+    if (bytes)
+        *bytes = n;
+    const uint64_t c = n < max_bytes ? n : max_bytes;
+    if (out && c)
+        FS_TRY(hipMemcpyAsync(out, src, (size_t)c, hipMemcpyDeviceToHost, r->compute));
+    return (uint32_t)hipStreamSynchronize(r->compute);
+}
+
 uint32_t fs_read_bla_level(fs_renderer *r, int32_t level, void *out, uint64_t max_records)
 {
     if (uint32_t e = use_device(r))

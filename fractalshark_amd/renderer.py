@@ -547,6 +547,37 @@ class GPURenderer:
             out[name] = a
         return out
 
+    QUIET_PARTS = (("prepared", np.float32, 4), ("first", np.float32, 4), ("second", np.float32, 4), ("zs2", np.float32, 2),
+                   ("zqb", np.float32, 4), ("znz", np.float32, 2))
+
+    def _read_quiet_part(self, part, dtype, width):
+        n = C.c_uint64(0)
+        err = self._lib.fs_read_quiet_orbit(self._h, part, None, 0, C.byref(n))
+        if err:
+            raise RuntimeError(self.ConvertErrorToString(err))
+        a = np.zeros(n.value // np.dtype(dtype).itemsize, dtype)
+        err = self._lib.fs_read_quiet_orbit(self._h, part, a.ctypes.data if n.value else None, n.value, None)
+        if err:
+            raise RuntimeError(self.ConvertErrorToString(err))
+        return a.reshape(-1, width) if width > 1 else a
+
+    def read_quiet_orbit(self):
+        """What the upload of the current HDRFloat<float> orbit left on the device for the tuned loops (fs_read_quiet_orbit) -> dict of
+        float32 arrays, a row per entry, the orbit's two spare entries included: prepared, first, second (n, 4); zs2 (n + 32, 2),
+        zqb (n + 32, 4) and znz (n + 32, 2) with their slack (tests / tools)."""
+        return {name: self._read_quiet_part(part, dt, w) for part, (name, dt, w) in enumerate(self.QUIET_PARTS)}
+
+    def read_prepared_orbit64(self):
+        """The prepared form of the current HDRFloat<double> orbit (FsZ64: re, im, e, pad, w), its two spare entries included."""
+        dt = np.dtype([("re", "<f8"), ("im", "<f8"), ("e", "<i4"), ("pad", "<i4"), ("w", "<f8")])
+        return self._read_quiet_part(6, dt, 1)
+
+    def read_scaled_orbit(self):
+        """The binary32 entries of the orbit last uploaded for the scaled kernels (fs_upload_orbit_scaled), their bound word in
+        `padding` as a bit pattern."""
+        dt = np.dtype([("bad", "<u4"), ("padding", "<u4"), ("x", "<f4"), ("y", "<f4")])
+        return self._read_quiet_part(7, dt, 1)
+
     def bla_lookup_probe(self, which, m, z2):
         """fs_bla_lookup_probe: which = 0 / 1 the reference-layout lookup in HDRFloat<float> / <double>, 2 the native lookup;
         m uint32[n], z2 a REAL_HDR32 / REAL_HDR64 array[n] -> uint32[n, 2] = (level, index), 0xFFFFFFFF twice for none."""

@@ -153,6 +153,18 @@ uint32_t fs_test_ndz_threshold(fs_renderer *r, const int32_t *bound_bits, const 
  * block bound} as the loop reads them; either may be NULL.  At most max_entries entries; *n_out = entries the orbit has (its two spare
  * entries included).  Synchronises the compute stream.  tests/test_gpu_lav2_ndz_tight.py holds the bounds against their definition. */
 uint32_t fs_read_ndz_bounds(fs_renderer *r, float *bounds_out, float *entries_out, uint64_t max_entries, uint64_t *n_out);
+/* Read-back of everything an orbit's upload leaves on the device for the tuned loops, part by part, as the kernels read it (m = the
+ * orbit's entries + its two spare ones; tests/test_gpu_quiet_orbit.py holds every part against tests/_quiet_model.py bit for bit).
+ * Of the current expanded HDRFloat<float> orbit: PREPARED = m float4 {re, im, exp, 2^(8 - 2 exp)}; FIRST = m float4 {re, im, ~exp + 116 or
+ * the poison, 0}; SECOND = m float4 {2Z.re, 2Z.im, own bound, block bound}; ZS2 = (m + 32) float2, ZQB = (m + 32) float4 and ZNZ =
+ * (m + 32) float2, the compact forms of the 16-step body and the NDZ body bounds, each with its 32 entries of slack.  Of the current expanded
+ * HDRFloat<double> orbit: PREPARED64 = m FsZ64 {re, im, exp, 0, 2^(8 - 2 exp)} (32 B).  SCALED_F32: the binary32 entries of the last
+ * fs_upload_orbit_scaled (fs_orbit_f32_bad; no spare entries) with the scaled kernels' bound word in `padding`.  *bytes = size of the
+ * part; at most max_bytes are copied (out may be NULL).  FS_ERR_6: no such orbit is resident; FS_ERR_7: no such part.  Synchronises the
+ * compute stream. */
+enum { FS_QUIET_PART_PREPARED = 0, FS_QUIET_PART_FIRST = 1, FS_QUIET_PART_SECOND = 2, FS_QUIET_PART_ZS2 = 3, FS_QUIET_PART_ZQB = 4,
+       FS_QUIET_PART_ZNZ = 5, FS_QUIET_PART_PREPARED64 = 6, FS_QUIET_PART_SCALED_F32 = 7 };
+uint32_t fs_read_quiet_orbit(fs_renderer *r, int part, void *out, uint64_t max_bytes, uint64_t *bytes);
 /* Average duration (HIP events on the compute stream, `repeats` back-to-back launches, no D2H) of the two RenderCurrent
  * kernels over the current iteration buffer: ms_out[0] = antialias + palette, ms_out[1] = min / max / sum.  Needs a
  * palette (fs_init_memory) and the whole frame on this renderer.  tools/bench_render_current.py turns them into GB/s. */

@@ -33,6 +33,7 @@ import pytest
 
 import _oracle
 import test_gpu_lav2_ndz as base
+from _quiet_model import start_states as _start_states  # (shared with tests/test_quiet_model_cpu.py)
 from fractalshark_amd import GPURenderer, LAV2_FULL, LAV2_PO, PARITY_CPU, PARITY_CPU_GPUSTAGE, T_HDR32, inputs
 
 pytestmark = pytest.mark.gpu
@@ -177,21 +178,6 @@ def _read_bounds(r, name):
     e = np.zeros((n.value, 4), np.float32)
     assert r._lib.fs_read_ndz_bounds(r._h, b.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), n.value, None) == 0
     return b[:ob.count], e[:ob.count]
-
-
-def _start_states(rng):
-    """Rows of (dz.re, dz.im, dc.re, dc.im) in units of the bound on max|dz| (the first two) and on max|dc| (the last two): both parts of dz at +-1 and at +-2^-k against +-1, dc at +-1, all
-    sign combinations; then seeded random states within the bound."""
-    rows = []
-    signs = [(a, b, c, d) for a in (1, -1) for b in (1, -1) for c in (1, -1) for d in (1, -1)]
-    for k in (0, 1, 12, 30):
-        for big_re in ((True,) if k == 0 else (True, False)):
-            x, y = (1.0, 2.0 ** -k) if big_re else (2.0 ** -k, 1.0)
-            rows += [(a * x, b * y, c * 1.0, d * 1.0) for a, b, c, d in signs]
-    rows += [tuple(rng.uniform(-1.0, 1.0, 4)) for _ in range(24)]
-    # (and dc far below dz, the case the add-free runs are in)
-    rows += [(a, b, c * 2.0 ** -40, d * 2.0 ** -40) for a, b, c, d in signs[:8]]
-    return np.array(rows, np.float64)
 
 
 @pytest.mark.parametrize("name", ["view5_64x36"] + CRAFTED)

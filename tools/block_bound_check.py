@@ -3,7 +3,9 @@ the block bound  =>  each of its four arrivals passes its own bound test".  Need
 (FS_VERIFY_BLOCK_BOUND=1 in the environment for the build AND for this run: the hand-scheduled untested loop is compiled out, every
 block runs the tested form, and a block that passes the block test while one of its arrivals fails its bound test is counted).
 Frames: C3's view at 1920x1080 in both parity modes and perturbation only at 480x270 (k_perturb_scalar's float path, C2's
-kernel), every built-in view below two million orbit entries (LAv2 Full and perturbation only) plus generated ones at 96x54.  The count must be zero.  Usage: FS_VERIFY_BLOCK_BOUND=1 python tools/block_bound_check.py"""
+kernel), every built-in view below two million orbit entries (LAv2 Full and perturbation only) plus generated ones at 96x54.  The count must be zero.
+(The tables themselves are held bit for bit against a plain model, and the model against this very property, by
+tests/test_gpu_quiet_orbit.py and tests/test_quiet_model_cpu.py -- no special build.)  Usage: FS_VERIFY_BLOCK_BOUND=1 python tools/block_bound_check.py"""
 import ctypes as C
 import json
 import os
