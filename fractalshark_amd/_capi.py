@@ -183,6 +183,7 @@ def render_lib():
     _decl(lib, "fs_read_exact_stats", u32, [vp, vp])
     _decl(lib, "fs_exact_sample_counts", u32, [vp, u32, u32, vp, vp, u32, u32, C.c_int, u64, vp])
     _decl(lib, "fs_exact_eval_points", u32, [vp, u32, u32, vp, vp, vp, u32, u32, C.c_int, vp, vp, vp, vp])
+    _decl(lib, "fs_exact_eval_points_wide", u32, [vp, u32, u32, vp, vp, vp, u32, u32, C.c_int, vp, vp, vp, vp])
     _decl(lib, "fs_render_exact_wide", u32, [vp, u32, u32, u32, vp, vp, u32, C.c_int, u64])
     _decl(lib, "fs_exact_wide_state", u32, [vp, u32, u32, vp, vp, u32, u32, vp, vp])
     _decl(lib, "fs_exact_audit", u32, [vp, vp, u32, u32, vp, vp, u32, u32, vp, vp, u32, C.c_int, u64, C.POINTER(AuditResult), vp, vp, vp])
@@ -284,7 +285,7 @@ RENDER_SYMBOLS = [
     "fs_feature_eval_resident", "fs_orbit_form", "fs_feature_eval_plain", "fs_feature_eval_plain_direct",
     "fs_autozoom_pick", "fs_set_autozoom_gather_cap",
     "fs_render_exact", "fs_exact_stable_mask", "fs_set_exact_slice", "fs_read_exact_stats",
-    "fs_exact_sample_counts", "fs_exact_eval_points", "fs_render_exact_wide", "fs_exact_wide_state", "fs_exact_audit",
+    "fs_exact_sample_counts", "fs_exact_eval_points", "fs_exact_eval_points_wide", "fs_render_exact_wide", "fs_exact_wide_state", "fs_exact_audit",
     "fs_set_exact_cycle_check", "fs_read_exact_proved", "fs_read_exact_cycle_stats", "fs_set_exact_cycle_fingerprint_bits",
     "fs_set_exact_keep", "fs_render_exact_continue", "fs_exact_kept_info", "fs_exact_drop_kept",
     "fs_set_exact_periods", "fs_read_exact_atom_periods", "fs_read_exact_cycle_lengths", "fs_set_exact_atom_key_bits",

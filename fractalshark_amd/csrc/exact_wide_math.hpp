@@ -100,6 +100,27 @@ FSX_HD bool exceeds_from_masks(uint64_t ne_hi, uint64_t gt_hi, uint64_t ne_lo, u
     return inclusive != 0;
 }
 
+// The period rule of the wide point runs (kernels_exact_wide.hip, the P = true instantiations) compares two unsigned numbers of
+// 128 blocks the same way.  How block a compares with block b: 0 equal, 1 greater, 2 less.
+template <int M> FSX_HD uint32_t block_order(const uint32_t (&a)[M], const uint32_t (&b)[M])
+{
+    uint32_t res = 0;
+    FSX_UNROLL
+    for (int i = 0; i < M; i++) // from the low limb up: a higher limb that differs overrides
+        res = a[i] > b[i] ? 1u : (a[i] < b[i] ? 2u : res);
+    return res;
+}
+
+// strictly less -- false on equality: NE = blocks that differ, LT = blocks that are less; the highest block that differs decides
+FSX_HD bool less_from_masks(uint64_t ne_hi, uint64_t lt_hi, uint64_t ne_lo, uint64_t lt_lo)
+{
+    if (ne_hi)
+        return (lt_hi >> (63 - __builtin_clzll(ne_hi))) & 1u;
+    if (ne_lo)
+        return (lt_lo >> (63 - __builtin_clzll(ne_lo))) & 1u;
+    return false;
+}
+
 } // namespace fsw
 
 #endif

@@ -604,10 +604,15 @@ struct FsExactWideArgs {
     // keeping (read by the K = true kernels only; fs_set_exact_keep): a sample that stops at n == cap + 1 goes to the destination
     // list as a running one does -- no survivor is written there in that slice -- at a slot counted by park_count
     uint32_t *park_count;
+    // point runs (read by the P = true kernels only; fs_exact_eval_points_wide; samples, never kept): run e stops at lengths[e] >= 1
+    // instead of cap, z_lengths[e] goes to periods->end, and the period rule runs on periods->mn and periods->atom, all per RUN
+    // (periods->stride = the runs of the call; periods->keys is not used)
+    const fsx::AtomPlanes *periods;
+    const uint64_t *lengths;
 };
-// one workgroup of 64 per sample; keep: the kernels that park; false: the limb count needs more than 11 limbs per lane (nothing
-// launched)
-bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, bool keep, hipStream_t s);
+// one workgroup of 64 per sample; keep: the kernels that park; points: the point-run kernels (not with keep); false: the limb count
+// needs more than 11 limbs per lane, or the combination has no kernel (nothing launched)
+bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, bool keep, bool points, hipStream_t s);
 
 // ---- fs_exact_audit (kernels_exact_audit.hip, exact_audit_math.hpp): the frame at the samples against their runs' counts.
 // counts[k * n_samples + i] = run k of sample i (run 0 = c, run 1 + 4 j + d = level j's four shifts).  One workgroup of one wave

@@ -1,5 +1,6 @@
-// kernels_exact_wide.hip -- the wide exact renderer (fs_exact_sample_counts, fs_render_exact_wide, fs_exact_wide_state): the
-// recurrence, the counting and the limb bound of exact_math.hpp with ONE WAVE PER SAMPLE, for limb counts no single lane can hold.
+// kernels_exact_wide.hip -- the wide exact renderer (fs_exact_sample_counts, fs_render_exact_wide, fs_exact_eval_points_wide,
+// fs_exact_wide_state): the recurrence, the counting and the limb bound of exact_math.hpp with ONE WAVE PER SAMPLE, for limb counts no
+// single lane can hold.
 //
 // A workgroup is one wave of 64 lanes and one sample.  With M = ceil(L / 64), every number of the recurrence is carried as
 // 64 M limbs (two's complement, sign-extended above limb L - 1), lane t holding limbs t M .. t M + M - 1 ("block t"); a 128 M
@@ -29,8 +30,19 @@
 // again (and counted again), nothing else.  All running samples hold the same n, so they meet the cap in one and the same slice,
 // which has no survivor: the parked samples go to that slice's destination list, at slots counted by a counter of their own.
 // K = false compiles to what it was without the parameter.
+//
+// Point runs (P = true, never with K; fs_exact_eval_points_wide): the point runs of kernels_exact.hip, one wave per run.  Run `id`
+// stops at A.lengths[id] where a sample stops at A.cap.  The state that passes the escape test with n == lengths[id] goes to the
+// end planes, limb g of x and y from the lane that holds it, before the step advances it.  The period rule (exact_atom_math.hpp)
+// compares the norm the escape test has just formed with the run's smallest so far, all 128 blocks of both, as the escape test
+// compares it with the bailout value: block by block in every lane, four ballots, the highest differing block decides
+// (fsw::block_order, fsw::less_from_masks).  The minimum is held in 2 M registers while a slice runs; between slices it lives in
+// the run's own limb planes (AtomPlanes::mn, indexed by id, not by slot: compaction copies nothing new), written by a run that is
+// still running when its slice ends and read back when the next one starts.  No key: the full compare is one round of ballots.
+// P = false compiles to what it was without the parameter.
 #include <hip/hip_runtime.h>
 
+#include "exact_atom_math.hpp"
 #include "kernels.h"
 
 namespace {
@@ -184,8 +196,17 @@ __device__ __forceinline__ void load_blocks(const uint32_t *p, uint32_t stride, 
     }
 }
 
-template <int M, bool K> __global__ void __launch_bounds__(64) k_exact_wide_slice(const FsExactWideArgs A)
+// whether the unsigned 128-block a is strictly below the unsigned 128-block b
+template <int M>
+__device__ __forceinline__ bool wave_below(const uint32_t (&alo)[M], const uint32_t (&ahi)[M], const uint32_t (&blo)[M], const uint32_t (&bhi)[M])
 {
+    const uint32_t c0 = fsw::block_order<M>(alo, blo), c1 = fsw::block_order<M>(ahi, bhi);
+    return fsw::less_from_masks(__ballot(c1 != 0), __ballot(c1 == 2), __ballot(c0 != 0), __ballot(c0 == 2));
+}
+
+template <int M, bool K, bool P> __global__ void __launch_bounds__(64) k_exact_wide_slice(const FsExactWideArgs A)
+{
+    static_assert(!(K && P), "point runs are never kept");
     __shared__ uint32_t lds[128 * M];
     const uint32_t lane = threadIdx.x, slot = blockIdx.x, L = A.limbs;
     const uint32_t nb = (L + M - 1) / M;
@@ -207,6 +228,19 @@ template <int M, bool K> __global__ void __launch_bounds__(64) k_exact_wide_slic
         load_blocks<M>(A.src.xy, A.stride, slot, L, lane, x);
         load_blocks<M>(A.src.xy + (size_t)L * A.stride, A.stride, slot, L, lane, y);
     }
+    // point runs: the run's length in place of the cap, and its smallest norm so far (limbs 2L and up of a norm are zero; the first
+    // slice has none yet, and the take at n = 1 asks for none)
+    uint64_t cap = A.cap;
+    uint32_t mnl[P ? M : 1], mnh[P ? M : 1];
+    if constexpr (P) {
+        cap = A.lengths[id];
+#pragma unroll
+        for (int i = 0; i < M; i++) {
+            const uint32_t g = lane * M + i, gh = (64u + lane) * M + i;
+            mnl[i] = !A.first && g < 2 * L ? A.periods->mn[(size_t)g * A.periods->stride + id] : 0u;
+            mnh[i] = !A.first && gh < 2 * L ? A.periods->mn[(size_t)gh * A.periods->stride + id] : 0u;
+        }
+    }
 
     bool running = true, parked = false;
     uint32_t steps = 0;
@@ -223,9 +257,32 @@ template <int M, bool K> __global__ void __launch_bounds__(64) k_exact_wide_slic
                 break; // beyond the bound the limbs are sized for: this z is kept
         } else {
             steps++;
-            if (escaped || n == A.cap + 1) {
+            if constexpr (P) {
+                if (!escaped && n <= cap) { // (z_{cap+1} is tested, not tracked)
+                    if (n == 1 || wave_below<M>(wl, wh, mnl, mnh)) {
+#pragma unroll
+                        for (int i = 0; i < M; i++)
+                            mnl[i] = wl[i], mnh[i] = wh[i];
+                        if (lane == 0)
+                            A.periods->atom[id] = n;
+                    }
+                    if (n == cap) {
+                        uint32_t *end = A.periods->end;
+                        const uint32_t stride = A.periods->stride;
+#pragma unroll
+                        for (int i = 0; i < M; i++) {
+                            const uint32_t g = lane * M + i;
+                            if (g < L) {
+                                end[(size_t)g * stride + id] = x[i];
+                                end[(size_t)(L + g) * stride + id] = y[i];
+                            }
+                        }
+                    }
+                }
+            }
+            if (escaped || n == cap + 1) {
                 if (lane == 0) {
-                    const uint64_t v = escaped ? n - 1 : A.cap;
+                    const uint64_t v = escaped ? n - 1 : cap;
                     const size_t o = A.W ? (size_t)iy * A.out_pitch + ix : (size_t)id;
                     if (A.out_u64)
                         ((uint64_t *)A.out)[o] = v;
@@ -280,6 +337,16 @@ template <int M, bool K> __global__ void __launch_bounds__(64) k_exact_wide_slic
             A.dst.n[dst] = n;
             A.dst.id[dst] = id;
         }
+        if constexpr (P) {
+#pragma unroll
+            for (int i = 0; i < M; i++) {
+                const uint32_t g = lane * M + i, gh = (64u + lane) * M + i;
+                if (g < 2 * L)
+                    A.periods->mn[(size_t)g * A.periods->stride + id] = mnl[i];
+                if (gh < 2 * L)
+                    A.periods->mn[(size_t)gh * A.periods->stride + id] = mnh[i];
+            }
+        }
     }
     if (lane == 0 && steps != 0)
         atomicAdd(&A.stats[0], (unsigned long long)steps);
@@ -287,16 +354,20 @@ template <int M, bool K> __global__ void __launch_bounds__(64) k_exact_wide_slic
 
 } // namespace
 
-bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, bool keep, hipStream_t s)
+bool fsk_exact_wide_slice(const FsExactWideArgs &A, uint32_t n_src, bool keep, bool points, hipStream_t s)
 {
+    if (points && (keep || A.W != 0 || A.state_only || !A.periods || !A.lengths))
+        return false;
     const dim3 grid(n_src), block(64);
     switch (fsw::block_for(A.limbs)) {
 #define FS_EXACT_WIDE_CASE(M)                                                                                          \
     case M:                                                                                                             \
-        if (keep)                                                                                                       \
-            hipLaunchKernelGGL((k_exact_wide_slice<M, true>), grid, block, 0, s, A);                                    \
+        if (points)                                                                                                     \
+            hipLaunchKernelGGL((k_exact_wide_slice<M, false, true>), grid, block, 0, s, A);                             \
+        else if (keep)                                                                                                  \
+            hipLaunchKernelGGL((k_exact_wide_slice<M, true, false>), grid, block, 0, s, A);                             \
         else                                                                                                            \
-            hipLaunchKernelGGL((k_exact_wide_slice<M, false>), grid, block, 0, s, A);                                   \
+            hipLaunchKernelGGL((k_exact_wide_slice<M, false, false>), grid, block, 0, s, A);                            \
         return true;
         FS_EXACT_WIDE_FOR_EACH_M(FS_EXACT_WIDE_CASE)
 #undef FS_EXACT_WIDE_CASE

@@ -139,9 +139,10 @@ struct ExactRun {
     bool read_proved;        // with the check: the call's proved mask becomes the one fs_read_exact_proved returns
     bool periods;            // fs_render_exact with fs_set_exact_periods: the P = true kernels run and the period planes come back
     ExactMode mode;          // frames only
-    // point runs (fs_exact_eval_points; samples on the lane path, no cycle check): run e stops at lengths[e] instead of cap, the
-    // S = true, P = true kernels run, and the runs' atom periods and endpoints (x planes, y planes: [limbs][n] each) go to the
-    // caller's host arrays -- not to the renderer's planes, which stay the last frame's
+    // point runs (fs_exact_eval_points, fs_exact_eval_points_wide; samples on either path, no cycle check, nothing kept): run e
+    // stops at lengths[e] instead of cap, the path's point-run kernels run (lane: S = true, P = true; wide: P = true), and the runs'
+    // atom periods and endpoints (x planes, y planes: [limbs][n] each) go to the caller's host arrays -- not to the renderer's
+    // planes, which stay the last frame's
     const uint64_t *lengths;
     uint64_t *atoms_out;
     uint32_t *end_x_out, *end_y_out;
@@ -236,7 +237,8 @@ static bool exact_wide_launch(const ExactRun &R, const FsExactArgs &A, bool, boo
     B.cap = A.cap, B.limbs = R.limbs, B.P = A.P;
     B.src = A.src, B.dst = A.dst, B.stride = A.stride, B.first = A.first, B.slice = A.slice;
     B.dst_count = A.dst_count, B.stats = A.stats, B.park_count = A.park_count;
-    return fsk_exact_wide_slice(B, A.n_src, keep, s);
+    B.periods = A.periods, B.lengths = A.lengths;
+    return fsk_exact_wide_slice(B, A.n_src, keep, R.lengths != nullptr, s);
 }
 static const ExactPath kExactWide = {exact_wide_launch, wide_default_slice, wide_add_stats, false, true};
 
@@ -418,7 +420,7 @@ static uint32_t exact_wide_state_run(fs_renderer *r, uint32_t frac_bits, uint32_
     if (e == hipSuccess)
         e = hipMemcpyAsync(Y.cy(blk), cy, plane_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
-        e = fsk_exact_wide_slice(A, n, false, s) ? hipGetLastError() : hipErrorInvalidValue;
+        e = fsk_exact_wide_slice(A, n, false, false, s) ? hipGetLastError() : hipErrorInvalidValue;
     if (e == hipSuccess)
         e = hipMemcpyAsync(out_x, A.dst.xy, plane_bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
@@ -705,6 +707,44 @@ uint32_t fs_exact_eval_points(fs_renderer *r, uint32_t frac_bits, uint32_t limbs
     r->exact.reset_stats();
     // (the cycle-check, keep and periods switches are not read: no check, nothing kept, and the renderer's planes stay the frame's)
     ExactRun R = exact_sample_run(kExactLane, frac_bits, limbs, cx, cy, n_runs, bailout, inclusive, longest, d_out);
+    R.lengths = lengths, R.atoms_out = atoms_out, R.end_x_out = end_x_out, R.end_y_out = end_y_out;
+    uint32_t rc = exact_run(r, R).rc;
+    if (rc == 0)
+        rc = (uint32_t)hipMemcpyAsync(values_out, d_out, (size_t)n_runs * 8, hipMemcpyDeviceToHost, r->compute);
+    if (rc == 0)
+        rc = (uint32_t)hipStreamSynchronize(r->compute);
+    (void)r_free(r, d_out);
+    return rc;
+}
+
+// fs_exact_eval_points on the wide path: its checks in its order with 704 limbs in place of 24, its run with a wave per run
+uint32_t fs_exact_eval_points_wide(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                                   const uint64_t *lengths, uint32_t n_runs, uint32_t bailout, int inclusive, uint64_t *values_out,
+                                   uint64_t *atoms_out, uint32_t *end_x_out, uint32_t *end_y_out)
+{
+    if (uint32_t e = use_device(r))
+        return e;
+    if (uint32_t e = exact_format_check(frac_bits, limbs, fsw::kMaxLimbs, bailout))
+        return e;
+    if (n_runs == 0)
+        return 0;
+    if (!cx || !cy || !lengths || !values_out || !atoms_out || !end_x_out || !end_y_out || n_runs > kWideMaxSamples)
+        return (uint32_t)hipErrorInvalidValue;
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < n_runs; i++) {
+        if (lengths[i] == 0 || lengths[i] == ~0ull)
+            return (uint32_t)hipErrorInvalidValue;
+        longest = lengths[i] > longest ? lengths[i] : longest;
+    }
+    if (!exact_axes_in_range(cx, n_runs, cy, n_runs, limbs, frac_bits))
+        return FS_ERR_UNSUPPORTED;
+    if (uint32_t e = ensure_streams(r)) // no fs_init_memory needed
+        return e;
+    uint64_t *d_out = nullptr;
+    FS_TRY(r_alloc(r, (void **)&d_out, (size_t)n_runs * 8, kFrame));
+    r->exact.reset_stats();
+    // (the keep switch is not read either: nothing is kept, and the kept set stays what it was)
+    ExactRun R = exact_sample_run(kExactWide, frac_bits, limbs, cx, cy, n_runs, bailout, inclusive, longest, d_out);
     R.lengths = lengths, R.atoms_out = atoms_out, R.end_x_out = end_x_out, R.end_y_out = end_y_out;
     uint32_t rc = exact_run(r, R).rc;
     if (rc == 0)

@@ -236,24 +236,28 @@ def points(values, frac_bits, limbs=None):
     return ints, _to_limbs(ints, limbs)
 
 
-def eval_points(renderer, cxs, cys, lengths, frac_bits, bailout=256, inclusive=False):
+def eval_points(renderer, cxs, cys, lengths, frac_bits, bailout=256, inclusive=False, wide=False):
     """Point runs on the GPU (fs_exact_eval_points; DESIGN.md 6.3 "Point runs"): run e iterates c = (cxs[e] + i cys[e]) / 2^frac_bits
     -- Python integers -- from z_1 = c up to n = lengths[e].  Returns (values, atoms, ends), lists of Python integers:
     values[e] = v = min(E - 1, lengths[e]); atoms[e] = the n in 1 .. v with the smallest x_n^2 + y_n^2, the earliest on ties, 0 when
     v = 0; ends[e] = (x_p, y_p) * 2^frac_bits at p = lengths[e] when v == p, else None.  Equal to the recurrence on Python integers.
-    Up to 758 fractional bits (24 limbs); ValueError beyond: the wide path has no point runs."""
+    Up to 758 fractional bits (24 limbs) a lane holds a run; ValueError beyond.  wide=True: a wave holds a run at every limb count
+    (fs_exact_eval_points_wide), up to 22 518 fractional bits (704 limbs), ValueError beyond; the results are the same wherever both
+    run."""
     F = int(frac_bits)
     L = limbs_for(F)
-    if uses_wide(L):
-        raise ValueError("eval_points: %d fractional bits need more than %d limbs; the wide path has no point runs" % (F, MAX_LIMBS))
+    if wide and L > MAX_WIDE_LIMBS:
+        raise ValueError("eval_points: %d fractional bits need more than %d limbs" % (F, MAX_WIDE_LIMBS))
+    if not wide and uses_wide(L):
+        raise ValueError("eval_points: %d fractional bits need more than %d limbs; wide=True runs them on the wide path" % (F, MAX_LIMBS))
     cxs, cys, lengths = list(cxs), list(cys), [int(p) for p in lengths]
     if not (len(cxs) == len(cys) == len(lengths)):
         raise ValueError("eval_points: cxs, cys and lengths must have one length")
     if not cxs:
         return [], [], []
-    err, values, atoms, end_x, end_y = renderer.ExactEvalPoints(F, L, _to_limbs(cxs, L), _to_limbs(cys, L),
-                                                                np.array(lengths, np.uint64), bailout, inclusive)
-    _check(renderer, err, "fs_exact_eval_points")
+    call = renderer.ExactEvalPointsWide if wide else renderer.ExactEvalPoints
+    err, values, atoms, end_x, end_y = call(F, L, _to_limbs(cxs, L), _to_limbs(cys, L), np.array(lengths, np.uint64), bailout, inclusive)
+    _check(renderer, err, "fs_exact_eval_points_wide" if wide else "fs_exact_eval_points")
     values, atoms = [int(v) for v in values], [int(a) for a in atoms]
     xs, ys = _from_limbs(end_x), _from_limbs(end_y)
     return values, atoms, [(x, y) if v == p else None for x, y, v, p in zip(xs, ys, values, lengths)]

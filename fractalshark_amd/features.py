@@ -247,30 +247,45 @@ def period_map(renderer, view, nx, ny, T=T_HDR64, iter_bytes=4, max_iters=None):
     return np.where(rout["status"] == OK_DIRECT, rout["period"], 0).astype(np.uint64).reshape(int(ny), int(nx))
 
 
+def _digits(n):
+    """str(n) of an n >= 0 of any length (Python prints no more than 4300 digits in one go)."""
+    chunk = 4000
+    if n < 10 ** chunk:
+        return str(n)
+    parts = []
+    while n:
+        n, low = divmod(n, 10 ** chunk)
+        parts.append(str(low).rjust(chunk, "0"))
+    return "".join(reversed(parts)).lstrip("0")
+
+
 def _decimal(v, frac_bits):
     """v / 2^frac_bits as an exact finite decimal string (v a Python integer)."""
-    digits = str(abs(v) * 5 ** frac_bits).rjust(frac_bits + 1, "0")
+    digits = _digits(abs(v) * 5 ** frac_bits).rjust(frac_bits + 1, "0")
     whole, frac = digits[:-frac_bits] if frac_bits else digits, (digits[-frac_bits:] if frac_bits else "").rstrip("0")
     return ("-" if v < 0 else "") + whole + ("." + frac if frac else "")
 
 
-def refine_found(renderer, found, frac_bits=None, rounds=16):
+def refine_found(renderer, found, frac_bits=None, rounds=16, wide=False):
     """The points find_periodic_points returns, refined to nuclei of their period on the exact recurrence (DESIGN.md 6.3 "Point
     runs"): exact.refine_points with the GPU evaluator exact.eval_points (bailout 256, strict), every point started at its printed
     (cx, cy) with the offset delta = max(1, floor(intrinsic_radius * 2^F) >> 30), F = frac_bits (default exact.MAX_FRAC_BITS = 758;
-    ValueError beyond).  Needs no orbit and no InitializeMemory.  Returns one dict per point, in order: status ("fixed", "rounds",
+    ValueError beyond).  wide=True: the evaluator is exact.eval_points(wide=True), a wave per run, and F goes up to
+    exact.MAX_WIDE_FRAC_BITS = 22 518 (ValueError beyond); the results are the same wherever both run.  Needs no orbit and no
+    InitializeMemory.  Returns one dict per point, in order: status ("fixed", "rounds",
     "stalled", "escaped"), c = (cx, cy) as integers c * 2^F and cx, cy as exact decimal strings (None where no iterate reached the
     period), atom (the atom period at c), converged (atom == period), period, evaluations, and log2 (log2 |z_p| of every iterate that
     reached the period, floats)."""
     from . import exact
     F = exact.MAX_FRAC_BITS if frac_bits is None else int(frac_bits)
-    if exact.uses_wide(exact.limbs_for(F)):
-        raise ValueError("refine_found: %d fractional bits need more than %d limbs" % (F, exact.MAX_LIMBS))
+    wide = bool(wide)
+    if exact.limbs_for(F) > (exact.MAX_WIDE_LIMBS if wide else exact.MAX_LIMBS):
+        raise ValueError("refine_found: %d fractional bits need more than %d limbs" % (F, exact.MAX_WIDE_LIMBS if wide else exact.MAX_LIMBS))
     cxs, _ = exact.points([p["cx"] for p in found], F)
     cys, _ = exact.points([p["cy"] for p in found], F)
     radii, _ = exact.points([p["intrinsic_radius"] for p in found], F)
     periods = [int(p["period"]) for p in found]
-    res = exact.refine_points(lambda a, b, n: exact.eval_points(renderer, a, b, n, F), list(zip(cxs, cys)),
+    res = exact.refine_points(lambda a, b, n: exact.eval_points(renderer, a, b, n, F, wide=wide), list(zip(cxs, cys)),
                               [max(1, r >> 30) for r in radii], periods, F, rounds)
     for q, p in zip(res, periods):
         q["period"] = p

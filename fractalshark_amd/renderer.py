@@ -205,6 +205,13 @@ class GPURenderer:
         """fs_exact_eval_points: (error code, values uint64[n], atoms uint64[n], end_x uint32[limbs, n], end_y uint32[limbs, n]) of
         n point runs, cx, cy = uint32[limbs, n] (limb-major per run), lengths = uint64[n]: run e stops at lengths[e].  Needs no
         InitializeMemory.  Synchronous."""
+        return self._eval_points(self._lib.fs_exact_eval_points, frac_bits, limbs, cx, cy, lengths, bailout, inclusive)
+
+    def ExactEvalPointsWide(self, frac_bits, limbs, cx, cy, lengths, bailout, inclusive):
+        """fs_exact_eval_points_wide: ExactEvalPoints through the one-wave-per-run kernels, limbs = 2 .. 704.  Synchronous."""
+        return self._eval_points(self._lib.fs_exact_eval_points_wide, frac_bits, limbs, cx, cy, lengths, bailout, inclusive)
+
+    def _eval_points(self, fn, frac_bits, limbs, cx, cy, lengths, bailout, inclusive):
         cx, cy = np.ascontiguousarray(cx, np.uint32), np.ascontiguousarray(cy, np.uint32)
         lengths = np.ascontiguousarray(lengths, np.uint64)
         if cx.ndim != 2 or cx.shape[0] != limbs or cy.shape != cx.shape or lengths.shape != (cx.shape[1],):
@@ -212,9 +219,8 @@ class GPURenderer:
         n = cx.shape[1]
         values, atoms = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         end_x, end_y = np.zeros_like(cx), np.zeros_like(cy)
-        err = self._lib.fs_exact_eval_points(self._h, int(frac_bits), int(limbs), cx.ctypes.data, cy.ctypes.data, lengths.ctypes.data,
-                                             n, int(bailout), 1 if inclusive else 0, values.ctypes.data, atoms.ctypes.data,
-                                             end_x.ctypes.data, end_y.ctypes.data)
+        err = fn(self._h, int(frac_bits), int(limbs), cx.ctypes.data, cy.ctypes.data, lengths.ctypes.data, n, int(bailout),
+                 1 if inclusive else 0, values.ctypes.data, atoms.ctypes.data, end_x.ctypes.data, end_y.ctypes.data)
         return err, values, atoms, end_x, end_y
 
     def ExactAudit(self, frac_bits, limbs, xs, ys, cx_runs, cy_runs, bailout, inclusive, n_iterations, device_iters=None,

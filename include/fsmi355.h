@@ -389,6 +389,17 @@ uint32_t fs_render_exact_wide(fs_renderer *r, uint32_t iter_bytes, uint32_t frac
 uint32_t fs_exact_eval_points(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
                               const uint64_t *lengths, uint32_t n_runs, uint32_t bailout, int inclusive, uint64_t *values_out,
                               uint64_t *atoms_out, uint32_t *end_x_out, uint32_t *end_y_out);
+/* fs_exact_eval_points through the wide kernels: one wave per run at every limb count, limbs = 2 .. 704 (frac_bits <= 22518; DESIGN.md
+ * 6.3 "Point runs on the wide path").  The arguments, the layouts and every value are fs_exact_eval_points': wherever both accept a
+ * call their outputs are equal byte for byte.  Synchronous.  Needs no frame and no fs_init_memory; the iteration buffer, the orbit
+ * and LA caches, the kept set and the period planes of the last fs_render_exact are left alone, and no switch is read.
+ * fs_set_exact_slice applies (default: the wide path's, about 50 ms of a lone wave); fs_read_exact_stats reports the call as the
+ * wide path does, 64 lane slots per step of a wave.  n_runs == 0: 0.
+ * FS_ERR_UNSUPPORTED: limbs outside 2 .. 704 or 32 * limbs < frac_bits + 10; bailout outside 1 .. 256; a c outside [-32, 32).
+ * hipErrorInvalidValue: a NULL pointer; a length of 0 or 2^64 - 1; more than 2^31 - 1 runs. */
+uint32_t fs_exact_eval_points_wide(fs_renderer *r, uint32_t frac_bits, uint32_t limbs, const uint32_t *cx, const uint32_t *cy,
+                                   const uint64_t *lengths, uint32_t n_runs, uint32_t bailout, int inclusive, uint64_t *values_out,
+                                   uint64_t *atoms_out, uint32_t *end_x_out, uint32_t *end_y_out);
 /* The exact audit: the project's definition of a correct frame -- equal to the exact count on every sample that is stable at a
  * stated level -- as one call on the frame in the iteration buffer (device_iters: another device buffer of the same
  * geometry and IterType, NULL = the current one).  n_samples sample pixels (xs[i], ys[i]) of the W x H of fs_init_memory and a

@@ -109,7 +109,7 @@ uint32_t fs_set_autozoom_gather_cap(fs_renderer *r, uint32_t rows);
  * running after each frame's first slice. */
 uint32_t fs_set_exact_slice(fs_renderer *r, uint32_t steps, int no_compaction);
 uint32_t fs_read_exact_stats(const fs_renderer *r, uint64_t out[4]);
-/* The wide path (fs_exact_sample_counts, fs_render_exact_wide) obeys fs_set_exact_slice too (its default: about 50 ms of a lone
+/* The wide path (fs_exact_sample_counts, fs_render_exact_wide, fs_exact_eval_points_wide) obeys fs_set_exact_slice too (its default: about 50 ms of a lone
  * wave's steps at the limb count, divided by the number of times the list fills the chip's 1024 SIMDs, never under 16;
  * no_compaction is ignored: a launch has exactly one wave per running sample) and reports out[1] = steps its samples took (one
  * wave each, so out[0] = 64 x that), [2] = launches, [3] = samples still running after the first launch.
