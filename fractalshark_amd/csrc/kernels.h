@@ -419,17 +419,19 @@ void fsk_tile_order(const uint32_t *probe, uint32_t probe_pitch, uint32_t tiles_
 uint32_t fsk_tile_order_work_words(uint32_t n_tiles);
 void fsk_tile_order_by_cost(const uint32_t *cost, uint32_t n_tiles, uint32_t *tmp, uint32_t *order, uint32_t n_slots,
                             hipStream_t s);
-// wave slots of the fsk_lav2_hdr32 launch for this frame (>= its number of 8 x 8 tiles)
-uint32_t fsk_lav2_hdr32_slots(const FsFrame &f);
+// waves of a tile launch for this frame (>= its number of 8 x 8 tiles): fsl::tile_waves of launch_dispatch.hpp for the host side
+uint32_t fsk_tile_launch_waves(const FsFrame &f);
 void fsk_lav2_hdr32(const FsLav2Args32 &A, int mode, bool stats, int variant, hipStream_t s);
 void fsk_lav2_hdr64(const FsLav2ArgsT<double> &A, int mode, bool stats, hipStream_t s);
 void fsk_at_pass64(const FsLav2ArgsT<double> &A, hipStream_t s); // A.at_res (out), A.at_cost (out, optional), A.pixel_order (optional)
 // IterType = uint64_t with 64-bit iteration counting (iteration caps of 2^32 and above): the literal kernel instantiated
 // with a 64-bit counter; needs a uint64_t iteration buffer (frame.iter_u64)
-void fsk_lav2_wide(const FsLav2Args32 *A32, const FsLav2ArgsT<double> *A64, int mode, bool stats, hipStream_t s);
+void fsk_lav2_wide(const FsLav2Args32 &A, int mode, bool stats, hipStream_t s);
+void fsk_lav2_wide(const FsLav2ArgsT<double> &A, int mode, bool stats, hipStream_t s);
 // PerturbExtras::SimpleCompression with the orbit decompressed IN the kernel (GPUPerturbSingleResults::SeqWorkspace /
 // GetIterSeq / BinarySearch, Perturb.cuh:146-326): only the waypoints are resident (A.wp); the literal kernel walks them
-void fsk_lav2_seq(const FsLav2Args32 *A32, const FsLav2ArgsT<double> *A64, int mode, bool stats, hipStream_t s);
+void fsk_lav2_seq(const FsLav2Args32 &A, int mode, bool stats, hipStream_t s);
+void fsk_lav2_seq(const FsLav2ArgsT<double> &A, int mode, bool stats, hipStream_t s);
 // test hook: one lane's SeqOrbit cursor (32- or 64-bit positions) seeks to `start` and walks n entries on; out[k] = the
 // orbit value at start + k as hcplx<float> (12 B) / hcplx<double> (24 B)
 void fsk_seq_cursor_probe(bool is64, bool wide_pos, const void *wp, uint32_t n_wp, const void *cx, const void *cy,
@@ -482,7 +484,7 @@ void fsk_tile_order_finish(uint32_t *order, uint32_t n_slots, uint32_t n_tiles, 
 size_t fsk_pixel_order_temp_bytes(uint32_t n);
 hipError_t fsk_pixel_order_build(const uint32_t *counts, uint32_t n, uint32_t *work, uint32_t *order, void *temp, size_t temp_bytes,
                                  hipStream_t s);
-void fsk_lav2_lit32(const FsLav2Args32 &A, int mode, bool stats, dim3 g, dim3 b, hipStream_t s); // kernels.hip
+void fsk_lav2_lit32(const FsLav2Args32 &A, int mode, bool stats, hipStream_t s); // kernels_lav2_lit.hip
 void fsk_lav2_hdr64_fast(const FsLav2ArgsT<double> &A, int mode, bool stats, hipStream_t s); // kernels_hdr64.hip
 void fsk_perturb_scalar_hdr64(const FsBlaArgsT<double> &A, bool use_bla, bool stats, int variant, hipStream_t s);
 void fsk_perturb_bla_f64(const FsBlaArgsF64 &A, bool use_bla, bool stats, hipStream_t s);

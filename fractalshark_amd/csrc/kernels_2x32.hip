@@ -19,6 +19,7 @@
 #include "df32_math.hpp"
 #include "kernels.h"
 #include "kernel_common.hpp"
+#include "launch_dispatch.hpp"
 
 using namespace fs;
 
@@ -42,7 +43,7 @@ __device__ __forceinline__ HR orbit_y(const fs_orbit_2x32 *__restrict__ o, uint3
 }
 
 // Sequential access to a SimpleCompression orbit that stays compressed in HBM (fs_set_compressed_orbit_mode 1): the
-// HDRFloat<CudaDblflt> twin of SeqOrbit in kernels.hip (Perturb.cuh:160-326); same operations in the same order as
+// HDRFloat<CudaDblflt> twin of SeqOrbit in seq_orbit.hpp (Perturb.cuh:160-326); same operations in the same order as
 // k_decompress_hdr2x32, which expands the same waypoints once per upload.
 struct Seq2x32 {
     const fs_orbit_2x32_rc *__restrict__ wp;
@@ -501,26 +502,17 @@ __global__ void __launch_bounds__(256) k_lav2_2x32(FsLav2Args2x32 A)
 
 void fsk_lav2_2x32(const FsLav2Args2x32 &A, int mode, bool stats, hipStream_t s)
 {
-    const dim3 b(256);
-    const dim3 g((A.frame.width + 31) / 32, (A.frame.local_rows + 7) / 8); // tile_pixel()
-#define FS_LAUNCH(M)                                                                                                    \
-    do {                                                                                                                \
-        if (A.wp != nullptr && A.frame.wide != 0u)                                                                      \
-            hipLaunchKernelGGL((k_lav2_2x32<M, false, uint64_t, true>), g, b, 0, s, A);                                 \
-        else if (A.wp != nullptr)                                                                                       \
-            hipLaunchKernelGGL((k_lav2_2x32<M, false, uint32_t, true>), g, b, 0, s, A);                                 \
-        else if (A.frame.wide != 0u)                                                                                    \
-            hipLaunchKernelGGL((k_lav2_2x32<M, false, uint64_t>), g, b, 0, s, A);                                       \
-        else if (stats)                                                                                                 \
-            hipLaunchKernelGGL((k_lav2_2x32<M, true>), g, b, 0, s, A);                                                  \
-        else                                                                                                            \
-            hipLaunchKernelGGL((k_lav2_2x32<M, false>), g, b, 0, s, A);                                                 \
-    } while (0)
-    if (mode == FS_MODE_PO)
-        FS_LAUNCH(FS_MODE_PO);
-    else if (mode == FS_MODE_LAO)
-        FS_LAUNCH(FS_MODE_LAO);
-    else
-        FS_LAUNCH(FS_MODE_FULL);
-#undef FS_LAUNCH
+    const dim3 g = fsl::tile_grid(A.frame), b(256);
+    fsl::with_mode(mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (A.wp != nullptr) // waypoint-resident orbit: no step counters
+            fsl::with_bool(A.frame.wide != 0u, [&](auto w) {
+                hipLaunchKernelGGL((k_lav2_2x32<M, false, fsl::iter_t<decltype(w)::value>, true>), g, b, 0, s, A);
+            });
+        else
+            fsl::with_counting(A.frame, stats, [&](auto c) {
+                using C = decltype(c);
+                hipLaunchKernelGGL((k_lav2_2x32<M, C::stats, typename C::Iter>), g, b, 0, s, A);
+            });
+    });
 }

@@ -37,6 +37,7 @@
 #include "hdr_math.hpp"
 #include "kernels.h"
 #include "kernel_common.hpp"
+#include "launch_dispatch.hpp"
 
 using namespace fs;
 
@@ -886,7 +887,7 @@ void fsk_bla_hdr32_fast(const FsBlaArgsT<float> &A_in, bool pool, hipStream_t s)
     // Measured on C5: 140.9 against 132.6 ms at 7680x4320, 39.4 against 37.4 ms at 3840x2160 -- the passes it saves (18 % of the
     // step passes if it were free and perfect, tools/c5_pooling_potential.py) cost less than the checkpoints and the mixed waves
     // (lanes of four tiles at unrelated orbit phases: more lookup and jump passes per trip, fewer all-quiet steps) add.
-    const dim3 g((A.frame.width + 31) / 32, (A.frame.local_rows + 7) / 8, 1), b(256);
+    const dim3 g = fsl::tile_grid(A.frame), b(256);
     if (pool)
         hipLaunchKernelGGL(k_bla_hdr32_fast<true>, g, b, 0, s, A);
     else

@@ -1,12 +1,12 @@
-// kernels_decompress.hip -- PerturbExtras::SimpleCompression orbits for T = float, double, CudaDblflt and
-// HDRFloat<CudaDblflt>: expansion of the waypoint list into the full orbit, once per upload.
+// kernels_decompress.hip -- PerturbExtras::SimpleCompression orbits for T = float, double, CudaDblflt, HDRFloat<CudaDblflt>,
+// HDRFloat<float> and HDRFloat<double>: expansion of the waypoint list into the full orbit, once per upload.
 //
 // The reference's *RC* kernels rebuild each entry while they iterate (GPUPerturbSingleResults::GetCompressedComplex /
 // GetCompressedComplexSeq, FractalSharkGpuLib/Perturb.cuh:272-326): the waypoint at or below the wanted index, advanced
 // with  zx' = zx*zx - zy*zy + OrbitXLow;  zy' = Type{2}*zx_old*zy + OrbitYLow  in T arithmetic, HdrReduce after each
 // (the identity for a non-HDR T).  The value at an index is therefore a pure function of the waypoints, and the
 // expansion below -- one lane per waypoint segment -- hands the uncompressed kernels exactly the entries the
-// reference's kernels would have rebuilt.  (HDRFloat<float> / HDRFloat<double>: k_decompress_orbit_hdr32/64 in kernels.hip.)
+// reference's kernels would have rebuilt (CPU twin: RuntimeDecompressor, PerturbationResultsHelpers.h:46-161).
 // Compiled with -ffp-contract=off: one IEEE operation per source operation, in source order; for float / double that is
 // also what the host's RuntimeDecompressor computes (PerturbationResultsHelpers.h:51-58).
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "df32_math.hpp"
 #include "../../include/fsmi355.h"
 #include "kernels.h"
+#include "lav2_common.hpp"
 
 using namespace fs;
 
@@ -89,6 +90,61 @@ __global__ void k_decompress_hdr2x32(const fs_orbit_2x32_rc *__restrict__ wp, ui
 }
 
 } // namespace
+
+// HDRFloat<float> / HDRFloat<double>: the same expansion into the PREPARED form (zref_pack, as k_prepare_orbit_* makes it), so the
+// iteration kernels stay the uncompressed ones.  An MI355X has 288 GB of HBM: the orbit is expanded once per upload.
+__global__ void k_decompress_orbit_hdr32(const fs_orbit_hdr32_rc *__restrict__ wp, uint64_t n_wp, uint64_t n_uncompressed,
+                                         fs_real_hdr32 cxLow, fs_real_hdr32 cyLow, float4 *__restrict__ out)
+{
+    uint64_t k, i0, i1;
+    if (!segment(wp, n_wp, n_uncompressed, k, i0, i1))
+        return;
+    hreal32 zx{wp[k].mx, wp[k].ex}, zy{wp[k].my, wp[k].ey};
+    const hreal32 cx = ldr(cxLow), cy = ldr(cyLow);
+    const hreal32 Two{1.0f, 1};
+    for (uint64_t i = i0; i < i1; i++) {
+        out[i] = zref_pack(hc_from_hr(zx, zy));
+        // runOneIter, PerturbationResultsHelpers.h:51-58
+        const hreal32 zx_old = zx;
+        zx = hr_add(hr_sub(hr_mul(zx, zx), hr_mul(zy, zy)), cx);
+        hr_reduce(zx);
+        zy = hr_add(hr_mul(hr_mul(Two, zx_old), zy), cy);
+        hr_reduce(zy);
+    }
+}
+
+__global__ void k_decompress_orbit_hdr64(const fs_orbit_hdr64_rc *__restrict__ wp, uint64_t n_wp, uint64_t n_uncompressed,
+                                         fs_real_hdr64 cxLow, fs_real_hdr64 cyLow, FsZ64 *__restrict__ out)
+{
+    uint64_t k, i0, i1;
+    if (!segment(wp, n_wp, n_uncompressed, k, i0, i1))
+        return;
+    hreal64 zx{wp[k].mx, wp[k].ex}, zy{wp[k].my, wp[k].ey};
+    const hreal64 cx = ldr(cxLow), cy = ldr(cyLow);
+    const hreal64 Two{1.0, 1};
+    for (uint64_t i = i0; i < i1; i++) {
+        out[i] = zref_pack(hc_from_hr(zx, zy));
+        const hreal64 zx_old = zx;
+        zx = hr_add(hr_sub(hr_mul(zx, zx), hr_mul(zy, zy)), cx);
+        hr_reduce(zx);
+        zy = hr_add(hr_mul(hr_mul(Two, zx_old), zy), cy);
+        hr_reduce(zy);
+    }
+}
+
+void fsk_decompress_orbit_hdr32(const fs_orbit_hdr32_rc *wp, uint64_t n_wp, uint64_t n_uncompressed, fs_real_hdr32 cxLow,
+                                fs_real_hdr32 cyLow, float4 *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_decompress_orbit_hdr32, dim3((unsigned)((n_wp + 63) / 64)), dim3(64), 0, s, wp, n_wp,
+                       n_uncompressed, cxLow, cyLow, out);
+}
+
+void fsk_decompress_orbit_hdr64(const fs_orbit_hdr64_rc *wp, uint64_t n_wp, uint64_t n_uncompressed, fs_real_hdr64 cxLow,
+                                fs_real_hdr64 cyLow, FsZ64 *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_decompress_orbit_hdr64, dim3((unsigned)((n_wp + 63) / 64)), dim3(64), 0, s, wp, n_wp,
+                       n_uncompressed, cxLow, cyLow, out);
+}
 
 void fsk_decompress_orbit_plain(int type_tag, const void *wp, uint64_t n_wp, uint64_t n_uncompressed, const void *cxLow,
                                 const void *cyLow, void *out, hipStream_t s)

@@ -18,6 +18,7 @@
 #include "dw_math.hpp"
 #include "kernels.h"
 #include "kernel_common.hpp"
+#include "launch_dispatch.hpp"
 
 using fs::q4;
 using fs::q_mul_pwr2;
@@ -221,8 +222,7 @@ template <bool kStats, class IterT = uint32_t> __global__ void __launch_bounds__
 
 bool fsk_direct_lp(const FsDirectLpArgs &A, int kind, int iteration_precision, bool stats, hipStream_t s)
 {
-    const dim3 b(256);
-    const dim3 g((A.frame.width + 63) / 64, (A.frame.local_rows + 3) / 4);
+    const dim3 g = fsl::row_grid(A.frame), b(256);
     const bool wide = A.frame.wide != 0u; // iteration cap of 2^32 or above: the instantiations counting in 64 bits
 #define FS_LP_IP(K, IPV)                                                                                            \
     case IPV:                                                                                                       \

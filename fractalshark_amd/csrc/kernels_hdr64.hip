@@ -3,7 +3,7 @@
 // CPU twin: Fractal::CalcCpuPerturbationFractalLAV2<uint32_t,double,Disable> (Fractal.cpp:2545-2678) with
 // LAReference::getLA / isLAStageInvalid (LAReference.cpp:1076-1134), LAInfoDeep::Prepare / Evaluate (LAInfoDeep.h:395-420),
 // ATInfo::PerformAT (ATInfo.h:155-188).  Replaces mandel_1xHDR_float_perturb_lav2 as instantiated for HDRFloat<double>
-// (FractalSharkGpuLib/LAKernel.cuh:3-315, GPU_Render.cu:1152-1185).  k_lav2_lit<double> (kernels.hip) stays as the
+// (FractalSharkGpuLib/LAKernel.cuh:3-315, GPU_Render.cu:1152-1185).  k_lav2_lit<double> (kernels_lav2_lit.hip) stays as the
 // operation-by-operation A/B reference (FS_VARIANT_LITERAL) and serves the 64-bit counters and the waypoint-resident orbit.
 //
 // What is different from the literal kernel -- the VALUES of every state are the literal ones, bit for bit except the sign of a
@@ -47,6 +47,7 @@
 #include "at_math.hpp"
 #include "kernels.h"
 #include "kernel_common.hpp"
+#include "launch_dispatch.hpp"
 #include "lav2_common.hpp"
 #ifndef FS_H64_LA_ASM_DEBUG
 #define FS_H64_LA_ASM_DEBUG 0 /* 1 (probe build): the counting instantiation runs the hand-written statements too and tallies their exits by
@@ -671,32 +672,18 @@ template <int Mode, bool kStats, bool kAtInKernel> __global__ void __launch_boun
     }
 }
 
-dim3 tile_grid64(const FsFrame &f) { return dim3((f.width + 31) / 32, (f.local_rows + 7) / 8, 1); } // tile_pixel()
-
 } // namespace
 
 void fsk_lav2_hdr64_fast(const FsLav2ArgsT<double> &A, int mode, bool stats, hipStream_t s)
 {
-    const dim3 g = tile_grid64(A.frame), b(256);
-#define FS_LAUNCH64F(M)                                                                                             \
-    do {                                                                                                            \
-        if (A.at_res && (M) != FS_MODE_PO) {                                                                        \
-            if (stats)                                                                                              \
-                hipLaunchKernelGGL((k_lav2_hdr64<M, true, false>), g, b, 0, s, A);                                  \
-            else                                                                                                    \
-                hipLaunchKernelGGL((k_lav2_hdr64<M, false, false>), g, b, 0, s, A);                                 \
-        } else {                                                                                                    \
-            if (stats)                                                                                              \
-                hipLaunchKernelGGL((k_lav2_hdr64<M, true, true>), g, b, 0, s, A);                                   \
-            else                                                                                                    \
-                hipLaunchKernelGGL((k_lav2_hdr64<M, false, true>), g, b, 0, s, A);                                  \
-        }                                                                                                           \
-    } while (0)
-    if (mode == FS_MODE_FULL)
-        FS_LAUNCH64F(FS_MODE_FULL);
-    else if (mode == FS_MODE_PO)
-        FS_LAUNCH64F(FS_MODE_PO);
-    else
-        FS_LAUNCH64F(FS_MODE_LAO);
-#undef FS_LAUNCH64F
+    const dim3 g = fsl::tile_grid(A.frame), b(256);
+    fsl::with_mode(mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        // kAtInKernel = false: PerformAT ran in a pass of its own (A.at_res); a perturbation-only frame has none
+        fsl::with_bool(A.at_res == nullptr || M == FS_MODE_PO, [&](auto at) {
+            fsl::with_bool(stats, [&](auto st) {
+                hipLaunchKernelGGL((k_lav2_hdr64<M, decltype(st)::value, decltype(at)::value>), g, b, 0, s, A);
+            });
+        });
+    });
 }

@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include <cstdlib>
 #include "kernel_common.hpp"
+#include "launch_dispatch.hpp"
 #include "lav2_common.hpp"
 #include "scaled_runs.hpp"
 
@@ -1467,53 +1468,33 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))
 
 // ------------------------------------------------------------------------------------------------
 // Host-callable launchers (called from renderer_launch.cpp through kernels.h).
-static dim3 tile_grid(const FsFrame &f) { return dim3((f.width + 31) / 32, (f.local_rows + 7) / 8, 1); } // tile_pixel()
-
-uint32_t fsk_lav2_hdr32_slots(const FsFrame &f)
-{
-    return ((f.width + 31u) / 32u) * 4u * ((f.local_rows + 7u) / 8u);
-}
+uint32_t fsk_tile_launch_waves(const FsFrame &f) { return fsl::tile_waves(f); }
 
 void fsk_lav2_hdr32(const FsLav2Args32 &A, int mode, bool stats, int variant, hipStream_t s)
 {
     // A/B flag of fs_set_kernel_variant: the wave-uniform scaled runs' orbit entries through LDS (see the kernel)
     const bool lds_orbit = (variant & FS_VARIANT_FLAG_LDS_ORBIT) != 0;
     variant &= FS_VARIANT_BASE_MASK;
-    const dim3 b(256), g = tile_grid(A.frame);
-#define FS_LAUNCH_FAST(M, SC, LDS)                                                                                  \
-    if (stats) {                                                                                                    \
-        if (gs)                                                                                                     \
-            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, true, SC, LDS, true>), g, b, 0, s, A);                         \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, true, SC, LDS, false>), g, b, 0, s, A);                        \
-    } else {                                                                                                        \
-        if (gs)                                                                                                     \
-            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, false, SC, LDS, true>), g, b, 0, s, A);                        \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_lav2_hdr32_fast<M, false, SC, LDS, false>), g, b, 0, s, A);                       \
+    if (variant == FS_VARIANT_LITERAL) {
+        fsk_lav2_lit32(A, mode, stats, s); // k_lav2_lit<float> lives in kernels_lav2_lit.hip
+        return;
     }
-#define FS_LAUNCH(M)                                                                                                \
-    do {                                                                                                            \
-        if (variant == FS_VARIANT_LITERAL) {                                                                        \
-            fsk_lav2_lit32(A, M, stats, g, b, s); /* k_lav2_lit<float> lives in kernels.hip */                      \
-        } else {                                                                                                    \
-            const bool gs = A.parity == FS_PARITY_GPUSTAGE;                                                         \
-            if (variant == FS_VARIANT_TUNED_NOSCALE) {                                                              \
-                FS_LAUNCH_FAST(M, false, false)                                                                     \
-            } else if (lds_orbit) {                                                                                 \
-                FS_LAUNCH_FAST(M, true, true)                                                                       \
-            } else {                                                                                                \
-                FS_LAUNCH_FAST(M, true, false)                                                                      \
-            }                                                                                                       \
-        }                                                                                                           \
-    } while (0)
-    if (mode == FS_MODE_FULL)
-        FS_LAUNCH(FS_MODE_FULL);
-    else if (mode == FS_MODE_PO)
-        FS_LAUNCH(FS_MODE_PO);
+    const dim3 g = fsl::tile_grid(A.frame), b(256);
+    // (scaled runs, their orbit through LDS): three of the four pairs are built -- there is no LDS orbit without the runs
+    auto launch = [&](auto sc, auto lds) {
+        fsl::with_mode(mode, [&](auto m) {
+            fsl::with_bool(stats, [&](auto st) {
+                fsl::with_bool(A.parity == FS_PARITY_GPUSTAGE, [&](auto gs) {
+                    hipLaunchKernelGGL((k_lav2_hdr32_fast<decltype(m)::value, decltype(st)::value, decltype(sc)::value,
+                                                          decltype(lds)::value, decltype(gs)::value>), g, b, 0, s, A);
+                });
+            });
+        });
+    };
+    if (variant == FS_VARIANT_TUNED_NOSCALE)
+        launch(std::false_type{}, std::false_type{});
+    else if (lds_orbit)
+        launch(std::true_type{}, std::true_type{});
     else
-        FS_LAUNCH(FS_MODE_LAO);
-#undef FS_LAUNCH
-#undef FS_LAUNCH_FAST
+        launch(std::true_type{}, std::false_type{});
 }
-

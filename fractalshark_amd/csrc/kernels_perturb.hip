@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include <cstdlib>
 #include "kernel_common.hpp"
+#include "launch_dispatch.hpp"
 #include "lav2_common.hpp"
 #include "scaled_runs.hpp"
 
@@ -1427,8 +1428,6 @@ __global__ void __launch_bounds__(256) k_perturb_scalar(FsBlaArgsT<F> A)
 
 // ------------------------------------------------------------------------------------------------
 // Host-callable launchers (called from renderer_launch.cpp through kernels.h).
-static dim3 tile_grid(const FsFrame &f) { return dim3((f.width + 31) / 32, (f.local_rows + 7) / 8, 1); } // tile_pixel()
-
 // Grid of the persistent (lane-refilling) launch: as many workgroups as the device holds at once, never more than one
 // wave per tile.  The pixel queue counter is zeroed on the stream right before the launch.
 template <class K> static dim3 persistent_grid(K kernel, const FsFrame &f)
@@ -1457,50 +1456,32 @@ static void launch_perturb_scalar(const FsBlaArgsT<F> &A_in, bool use_bla, bool 
 {
     const FsBlaArgsT<F> &A = A_in;
     // a probe launch covers one lane per tile of the frame
-    const uint32_t ptx = (A.frame.width + 7u) >> 3, pty = (A.frame.local_rows + 7u) >> 3;
-    const dim3 g = A.probe_out ? dim3((ptx + 31) / 32, (pty + 7) / 8, 1) : tile_grid(A.frame), b(256);
-    if (A.frame.wide != 0u) { // iteration cap of 2^32 or above: the instantiation that counts in 64 bits
-        if (use_bla) {
-            if (stats)
-                hipLaunchKernelGGL((k_perturb_scalar<F, true, true, false, false, uint64_t>), g, b, 0, s, A);
-            else
-                hipLaunchKernelGGL((k_perturb_scalar<F, true, false, false, false, uint64_t>), g, b, 0, s, A);
+    const dim3 g = A.probe_out ? fsl::tile_grid((A.frame.width + 7u) >> 3, (A.frame.local_rows + 7u) >> 3) : fsl::tile_grid(A.frame);
+    const dim3 b(256);
+    const bool refill = use_bla && (variant & FS_VARIANT_FLAG_REFILL) != 0;
+    // the device-native table (HDRFloat<float> only; variant 1 keeps the reference-layout records for A/B)
+    const bool native = use_bla && std::is_same<F, float>::value && A.nrec != nullptr &&
+                        (variant & FS_VARIANT_BASE_MASK) != FS_VARIANT_LITERAL;
+    // (this kernel counts steps with 64-bit counters too: see launch_dispatch.hpp)
+    fsl::with_bool(stats, [&](auto st) {
+        constexpr bool kStats = decltype(st)::value;
+        if (A.frame.wide != 0u) { // iteration cap of 2^32 or above: the instantiation that counts in 64 bits
+            fsl::with_bool(use_bla, [&](auto bla) {
+                hipLaunchKernelGGL((k_perturb_scalar<F, decltype(bla)::value, kStats, false, false, uint64_t>), g, b, 0, s, A);
+            });
+        } else if (refill) {
+            (void)hipMemsetAsync(A.queue, 0, sizeof(uint32_t), s);
+            const auto k = k_perturb_scalar<F, true, kStats, true>;
+            hipLaunchKernelGGL(k, persistent_grid(k, A.frame), b, 0, s, A);
+        } else if (native) {
+            if constexpr (std::is_same<F, float>::value)
+                hipLaunchKernelGGL((k_perturb_scalar<F, true, kStats, false, true>), g, b, 0, s, A);
         } else {
-            if (stats)
-                hipLaunchKernelGGL((k_perturb_scalar<F, false, true, false, false, uint64_t>), g, b, 0, s, A);
-            else
-                hipLaunchKernelGGL((k_perturb_scalar<F, false, false, false, false, uint64_t>), g, b, 0, s, A);
+            fsl::with_bool(use_bla, [&](auto bla) {
+                hipLaunchKernelGGL((k_perturb_scalar<F, decltype(bla)::value, kStats, false>), g, b, 0, s, A);
+            });
         }
-        return;
-    }
-    if (use_bla && (variant & FS_VARIANT_FLAG_REFILL) != 0) {
-        (void)hipMemsetAsync(A.queue, 0, sizeof(uint32_t), s);
-        if (stats)
-            hipLaunchKernelGGL((k_perturb_scalar<F, true, true, true>),
-                               persistent_grid(k_perturb_scalar<F, true, true, true>, A.frame), b, 0, s, A);
-        else
-            hipLaunchKernelGGL((k_perturb_scalar<F, true, false, true>),
-                               persistent_grid(k_perturb_scalar<F, true, false, true>, A.frame), b, 0, s, A);
-    } else if (use_bla) {
-        if constexpr (std::is_same<F, float>::value) {
-            if (A.nrec != nullptr && (variant & FS_VARIANT_BASE_MASK) != FS_VARIANT_LITERAL) {
-                if (stats)
-                    hipLaunchKernelGGL((k_perturb_scalar<F, true, true, false, true>), g, b, 0, s, A);
-                else
-                    hipLaunchKernelGGL((k_perturb_scalar<F, true, false, false, true>), g, b, 0, s, A);
-                return;
-            }
-        }
-        if (stats)
-            hipLaunchKernelGGL((k_perturb_scalar<F, true, true, false>), g, b, 0, s, A);
-        else
-            hipLaunchKernelGGL((k_perturb_scalar<F, true, false, false>), g, b, 0, s, A);
-    } else {
-        if (stats)
-            hipLaunchKernelGGL((k_perturb_scalar<F, false, true, false>), g, b, 0, s, A);
-        else
-            hipLaunchKernelGGL((k_perturb_scalar<F, false, false, false>), g, b, 0, s, A);
-    }
+    });
 }
 
 void fsk_perturb_scalar_hdr32(const FsBlaArgs32 &A, bool use_bla, bool stats, int variant, hipStream_t s)

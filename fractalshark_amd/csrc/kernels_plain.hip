@@ -21,6 +21,7 @@
 #include "df32_math.hpp"
 #include "kernels.h"
 #include "kernel_common.hpp"
+#include "launch_dispatch.hpp"
 
 using namespace fs;
 
@@ -102,7 +103,7 @@ __device__ __forceinline__ cx<df32> ldz(const fs_orbit_p2x32 *__restrict__ o, ui
 }
 
 // Sequential access to a SimpleCompression orbit that stays compressed in HBM (fs_set_compressed_orbit_mode 1), T = float /
-// double / CudaDblflt: the plain-type twin of SeqOrbit in kernels.hip (GPUPerturbSingleResults::SeqWorkspace / GetIterSeq /
+// double / CudaDblflt: the plain-type twin of SeqOrbit in seq_orbit.hpp (GPUPerturbSingleResults::SeqWorkspace / GetIterSeq /
 // BinarySearch, Perturb.cuh:160-326).  seek() starts at the last waypoint at or before the index and iterates z = z^2 + c
 // forward in T arithmetic, step() moves one index on: the next waypoint when its index comes up, one iteration otherwise --
 // the operations, in the order, of k_decompress_plain / k_decompress_p2x32, which expand the same waypoints once per upload.
@@ -390,28 +391,19 @@ __global__ void __launch_bounds__(256) k_lav2_plain(FsLav2ArgsPlain A)
 
 template <class T> void launch(const FsLav2ArgsPlain &A, int mode, bool stats, hipStream_t s)
 {
-    const dim3 b(256);
-    const dim3 g((A.frame.width + 31) / 32, (A.frame.local_rows + 7) / 8); // tile_pixel()
-#define FS_LAUNCH(M)                                                                                                    \
-    do {                                                                                                                \
-        if (A.wp != nullptr && A.frame.wide != 0u)                                                                      \
-            hipLaunchKernelGGL((k_lav2_plain<T, M, false, uint64_t, true>), g, b, 0, s, A);                             \
-        else if (A.wp != nullptr)                                                                                       \
-            hipLaunchKernelGGL((k_lav2_plain<T, M, false, uint32_t, true>), g, b, 0, s, A);                             \
-        else if (A.frame.wide != 0u)                                                                                    \
-            hipLaunchKernelGGL((k_lav2_plain<T, M, false, uint64_t>), g, b, 0, s, A);                                   \
-        else if (stats)                                                                                                 \
-            hipLaunchKernelGGL((k_lav2_plain<T, M, true>), g, b, 0, s, A);                                              \
-        else                                                                                                            \
-            hipLaunchKernelGGL((k_lav2_plain<T, M, false>), g, b, 0, s, A);                                             \
-    } while (0)
-    if (mode == FS_MODE_PO)
-        FS_LAUNCH(FS_MODE_PO);
-    else if (mode == FS_MODE_LAO)
-        FS_LAUNCH(FS_MODE_LAO);
-    else
-        FS_LAUNCH(FS_MODE_FULL);
-#undef FS_LAUNCH
+    const dim3 g = fsl::tile_grid(A.frame), b(256);
+    fsl::with_mode(mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (A.wp != nullptr) // waypoint-resident orbit: no step counters
+            fsl::with_bool(A.frame.wide != 0u, [&](auto w) {
+                hipLaunchKernelGGL((k_lav2_plain<T, M, false, fsl::iter_t<decltype(w)::value>, true>), g, b, 0, s, A);
+            });
+        else
+            fsl::with_counting(A.frame, stats, [&](auto c) {
+                using C = decltype(c);
+                hipLaunchKernelGGL((k_lav2_plain<T, M, C::stats, typename C::Iter>), g, b, 0, s, A);
+            });
+    });
 }
 
 } // namespace

@@ -15,6 +15,7 @@
 #include "hdr_math.hpp"
 #include "kernels.h"
 #include "kernel_common.hpp"
+#include "launch_dispatch.hpp"
 
 using namespace fs;
 
@@ -736,8 +737,7 @@ template <bool kStats> __global__ void __launch_bounds__(256) k_scaled_f64_fast(
 
 void fsk_scaled_hdr32(const FsScaledArgs32 &A, bool stats, int variant, hipStream_t s)
 {
-    const dim3 b(256);
-    const dim3 g((A.frame.width + 31) / 32, (A.frame.local_rows + 7) / 8); // tile_pixel(): four 8 x 8 tiles per workgroup
+    const dim3 g = fsl::tile_grid(A.frame), b(256);
     if (A.frame.wide != 0u) { // iteration cap of 2^32 or above: the literal kernel counting in 64 bits
         hipLaunchKernelGGL((k_scaled_hdr32<false, uint64_t>), g, b, 0, s, A);
         return;
@@ -764,18 +764,18 @@ void fsk_scaled_f64(const FsScaledArgsF64 &A, bool stats, int variant, hipStream
 {
     const dim3 b(256);
     if (A.frame.wide != 0u) {
-        const dim3 g((A.frame.width + 63) / 64, (A.frame.local_rows + 3) / 4);
+        const dim3 g = fsl::row_grid(A.frame);
         hipLaunchKernelGGL((k_scaled_f64<false, uint64_t>), g, b, 0, s, A);
         return;
     }
     if (variant == FS_VARIANT_LITERAL) {
-        const dim3 g((A.frame.width + 63) / 64, (A.frame.local_rows + 3) / 4);
+        const dim3 g = fsl::row_grid(A.frame);
         if (stats)
             hipLaunchKernelGGL((k_scaled_f64<true>), g, b, 0, s, A);
         else
             hipLaunchKernelGGL((k_scaled_f64<false>), g, b, 0, s, A);
     } else {
-        const dim3 g((A.frame.width + 31) / 32, (A.frame.local_rows + 7) / 8); // tile_pixel()
+        const dim3 g = fsl::tile_grid(A.frame);
         if (stats)
             hipLaunchKernelGGL((k_scaled_f64_fast<true>), g, b, 0, s, A);
         else

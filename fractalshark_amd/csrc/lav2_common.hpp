@@ -1,6 +1,6 @@
-// lav2_common.hpp -- the few device helpers the LAv2 translation units share (kernels.hip, kernels_hdr64.hip): record ->
-// hreal / hcplx loads, the prepared-orbit access and the pixel -> delta-c mapping.  One definition (round 6: moved out of
-// kernels.hip when the HDRFloat<double> kernel got a translation unit of its own).
+// lav2_common.hpp -- the few device helpers the LAv2 translation units share (kernels_lav2_lit.hip, kernels_hdr64.hip, ...): record
+// -> hreal / hcplx loads, the prepared-orbit entry (made in kernels_orbit_prep.hip and kernels_decompress.hip, read everywhere) and
+// the pixel -> delta-c mapping.  One definition.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,6 +35,23 @@ __device__ __forceinline__ hcplx32 zref_at(const float4 *__restrict__ z, uint32_
 __device__ __forceinline__ hcplx64 zref_at(const FsZ64 *__restrict__ z, uint32_t i)
 {
     return hcplx64{z[i].re, z[i].im, z[i].e};
+}
+// ... and how such an entry is made from the complex value (k_prepare_orbit_*, k_decompress_orbit_*).
+// .w = 2^(8 - 2*exp): with z = Z + dz aligned to Z's exponent, |z|^2 > 256  <=>  re^2 + im^2 > .w  (tuned loop).
+// Overflows to +inf for a tiny Z (never "escaped" there), cannot underflow (orbit values are < 2^9).
+__device__ __forceinline__ float4 zref_pack(const hcplx32 c)
+{
+    return make_float4(c.re, c.im, __int_as_float(c.e), ldexpf(1.0f, 8 - 2 * (c.e < -1000 ? -1000 : c.e)));
+}
+__device__ __forceinline__ FsZ64 zref_pack(const hcplx64 c)
+{
+    FsZ64 z;
+    z.re = c.re;
+    z.im = c.im;
+    z.e = c.e;
+    z.pad_ = 0;
+    z.w = ldexp(1.0, 8 - 2 * (c.e < -500 ? -500 : c.e));
+    return z;
 }
 
 // Pixel -> delta c, Fractal.cpp:2553-2562 (== 2272-2281): `dx * (float)x` goes through HDRFloat(T mant).

@@ -204,7 +204,7 @@ static const uint32_t *cold_tile_order(fs_renderer *r, FsTileSampleArgs &S)
     if (off || !pix_order_wanted(r, S.frame) || S.StepLength == 0u)
         return nullptr;
     S.tiles_x = (S.frame.width + 7u) / 8u, S.tiles_y = (S.frame.local_rows + 7u) / 8u;
-    S.n_slots = ((S.frame.width + 31u) / 32u) * S.tiles_y * 4u; // waves of the frame's launch (tile_grid: 4 tiles per workgroup)
+    S.n_slots = fsk_tile_launch_waves(S.frame);
     const size_t words = (size_t)S.n_slots * sizeof(uint32_t);
     if (buf_reserve(r, {{&r->cold_cost, words}, {&r->cold_order, words}, {&r->cold_work, 2 * words},
                         {&r->cold_temp, fsk_pixel_order_temp_bytes(S.n_slots)}}, kFrame) != hipSuccess) {
@@ -255,10 +255,7 @@ static uint32_t lav2_seq(fs_renderer *r, int type_tag, int mode, int parity, con
         A.at = at;
         A.wp = r->wp_raw, A.n_wp = (uint32_t)r->orbit_size;
         A.cxLow = c_low[0], A.cyLow = c_low[1];
-        if constexpr (sizeof(F) == 4)
-            fsk_lav2_seq(&A, nullptr, kernel_mode(mode), r->stats_on, r->compute);
-        else
-            fsk_lav2_seq(nullptr, &A, kernel_mode(mode), r->stats_on, r->compute);
+        fsk_lav2_seq(A, kernel_mode(mode), r->stats_on, r->compute);
     };
     if (type_tag == FS_T_HDR32)
         launch(0.0f, r->at, r->c_low32);
@@ -288,13 +285,13 @@ static uint32_t lav2_wide(fs_renderer *r, int type_tag, int mode, int parity, co
         fill_lav2<float>(r, A, coords, n_iterations, parity);
         set_orbit_hdr32(r, A);
         A.at = r->at;
-        fsk_lav2_wide(&A, nullptr, kernel_mode(mode), r->stats_on, r->compute);
+        fsk_lav2_wide(A, kernel_mode(mode), r->stats_on, r->compute);
     } else {
         FsLav2ArgsT<double> A;
         fill_lav2<double>(r, A, coords, n_iterations, parity);
         A.zref = r->zref64;
         A.at = r->at64;
-        fsk_lav2_wide(nullptr, &A, kernel_mode(mode), r->stats_on, r->compute);
+        fsk_lav2_wide(A, kernel_mode(mode), r->stats_on, r->compute);
     }
     return (uint32_t)hipGetLastError();
 }
@@ -392,7 +389,7 @@ static uint32_t lav2_hdr32(fs_renderer *r, int mode, int parity, const void *coo
     // every frame after fs_forget_tile_costs, or with FS_VARIANT_NATURAL_TILE_ORDER) runs in natural order.
     const uint32_t tiles_x = (r->width + 7u) / 8u, tiles_y = (r->local_rows + 7u) / 8u;
     const uint32_t n_tiles = tiles_x * tiles_y;
-    const uint32_t n_slots = fsk_lav2_hdr32_slots(A.frame);
+    const uint32_t n_slots = fsk_tile_launch_waves(A.frame);
     const bool tuned = (r->variant & FS_VARIANT_BASE_MASK) != FS_VARIANT_LITERAL;
     const bool record = tuned && n_tiles >= kLav2OrderMinTiles && (r->variant & FS_VARIANT_FLAG_NATURAL_ORDER) == 0;
     if (record) {
@@ -555,7 +552,7 @@ uint32_t fs_render_bla(fs_renderer *r, int type_tag, const void *coords, uint64_
         // tiles whose centre (or a neighbour's) is still running then are launched first -- one per SIMD while there are
         // no more of them than SIMDs -- the rest in their natural order.  Which wave renders which tile changes no pixel.
         const uint32_t tiles_x = (r->width + 7u) / 8u, tiles_y = (r->local_rows + 7u) / 8u;
-        const uint32_t n_slots = ((tiles_x + 3u) / 4u) * 4u * tiles_y; // waves of the launch (tile_grid: 4 tiles per block)
+        const uint32_t n_slots = fsk_tile_launch_waves(A.frame);
         const bool reorder = !use_bla && !r->stats_on && A.frame.wide == 0u && n_iterations >= kTileOrderMinIterations &&
                              n_slots >= kTileOrderMinTiles && (r->variant & FS_VARIANT_FLAG_NATURAL_ORDER) == 0 &&
                              (r->variant & FS_VARIANT_BASE_MASK) == FS_VARIANT_TUNED;

@@ -335,7 +335,7 @@ constexpr int kFloorBits = (127 - kFloorExp) << 23;
 //   patterns below needs a normal number) or when j + 8 is past the orbit.  (Round 8 kept one bound on max(D, C) and divided by
 //   scaled_block_bound's g_k = 4 M_k + 3.8, valid for any G <= 1.4: 2^18 .. 2^21 over seven typical steps, so a body was refused until dz
 //   was 2^-40 and more below Z where 2^-26 is what exactness needs.  One bound with the growth s + 1 came first and its counting launch
-//   said what dc's own term would add: ndz_body_bound in kernels.hip has the figures.)
+//   said what dc's own term would add: ndz_body_bound in kernels_orbit_prep.hip has the figures.)
 //   1. Induction.  fl(a + d) == a whenever |d| <= 2^-26 |a| (argued for ND above).  The fma rounds once, and the product w 2^E is
 //      exact inside it (a power of two; it IS dz in true scale, which need not be representable on its own).  Hypothesis at step m
 //      (m = 0: D <= .x <= 2^-27 lo_j):  max|dz_m| <= A_m D + B_m C <= 2^-26 lo_(j+m), each half within 2^-27 lo_(j+m).

@@ -1,5 +1,5 @@
 // seq_orbit.hpp -- the waypoint cursor: sequential access to a PerturbExtras::SimpleCompression orbit that stays compressed in
-// HBM.  Device code shared by the LAv2 kernels of kernels.hip and the Feature Finder's evaluator (kernels_feature.hip).
+// HBM.  Device code shared by the literal LAv2 kernel (kernels_lav2_lit.hip) and the Feature Finder's evaluator (kernels_feature.hip).
 //
 // The device twin of GPUPerturbSingleResults::SeqWorkspace / GetIterSeq / BinarySearch (Perturb.cuh:160-326) and of the CPU
 // RuntimeDecompressor (PerturbationResultsHelpers.h:35-199).  A cursor holds one orbit value; seek() starts from the

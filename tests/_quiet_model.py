@@ -1,6 +1,6 @@
 """A plain model of what an orbit's upload leaves on the device for the tuned loops: the prepared orbit, the two companions, the compact
-zs2 / zqb of the 16-step body, the NDZ bounds znz (k_prepare_orbit_hdr32 / _hdr64, k_make_quiet_orbit, k_decompress_orbit_hdr32 in
-csrc/kernels.hip) and the scaled kernels' bound word (k_scaled_bounds in csrc/kernels_scaled.hip) -- numpy only, nothing of the product
+zs2 / zqb of the 16-step body, the NDZ bounds znz (k_prepare_orbit_hdr32 / _hdr64, k_make_quiet_orbit in csrc/kernels_orbit_prep.hip,
+k_decompress_orbit_hdr32 in csrc/kernels_decompress.hip) and the scaled kernels' bound word (k_scaled_bounds in csrc/kernels_scaled.hip) -- numpy only, nothing of the product
 imported, written from the DEFINITIONS in the comments there and in csrc/scaled_runs.hpp:
 
   prepared     {re, im, e, 2^(8 - 2 max(e, -1000))}: hc_from_hr of the entry (tests/_ieee_model.py), .w = +inf where it overflows;

@@ -1,4 +1,4 @@
-"""The NDZ body bounds with the growth an NDZ body really has (ndz_body_bound in csrc/kernels.hip; the argument is written out there and
+"""The NDZ body bounds with the growth an NDZ body really has (ndz_body_bound in csrc/kernels_orbit_prep.hip; the argument is written out there and
 under "NDZ" in csrc/scaled_runs.hpp).
 
 An NDZ body of FS_FAST_LOOP_FDU multiplies dz by the entry's 2Z without adding dz to it first.  With D = max|dz| and C = max|dc| where the

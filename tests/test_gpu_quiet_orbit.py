@@ -1,5 +1,5 @@
 """What an orbit's upload leaves on the device for the tuned loops -- the prepared orbit, the two companions, zs2 / zqb of the 16-step body,
-the NDZ bounds znz with their slack (k_prepare_orbit_hdr32, k_make_quiet_orbit, k_decompress_orbit_hdr32 in csrc/kernels.hip), the
+the NDZ bounds znz with their slack (k_prepare_orbit_hdr32, k_make_quiet_orbit, in csrc/kernels_orbit_prep.hip; k_decompress_orbit_hdr32 in csrc/kernels_decompress.hip), the
 HDRFloat<double> prepared orbit and the scaled kernels' bound word (k_scaled_bounds) -- read back (fs_read_quiet_orbit) and held BIT FOR
 BIT against the plain model tests/_quiet_model.py, which tests/test_quiet_model_cpu.py holds against what the bounds are for.  Compared
 as uint32 patterns, so "never" (-0.0) and +inf are patterns like any other.  On every orbit of tests/_quiet_orbits.py:
